@@ -28,16 +28,24 @@ output and the runner re-runs such a call on full-range kernels
 ``.eval()``, so every BatchNorm normalises with the statistics of the video
 being served (per-video segments when a runner batches videos).
 ``--bn eval`` folds BatchNorm into the convs (inference numerics, faster).
-``--dtype bf16`` selects the bf16 serving kernels. After the run, the logits
-of a sample of served videos are recomputed with the fp32 nn.Module, one
-video per forward (``numerics`` in the JSON line).
+``--dtype bf16`` selects the bf16 serving kernels. With ``--full``, after the
+run, the logits of a sample of served videos are recomputed with the fp32
+nn.Module, one video per forward (``numerics`` in the JSON line).
+
+A plain run does what the headline figure needs: set-up, phases 1 and 2
+below, ``--dump-outputs`` if given, the JSON line. ``--full`` adds phase 3,
+the numerics check and the short runs of other configs (``literal`` at 1 GPU,
+``cross_gpu`` at N GPUs). ``--dump-outputs DIR`` writes the logits the last
+timed step's model calls returned (``DIR/logits.npy``, ``video_logits.npy``);
+a video's clips follow from ``--seed`` and its id, so runs with the same
+arguments serve the same inputs.
 
 Phases of one launcher run (``-mi 0``):
 1. warm-up: W steps of videos, all completed before timing starts;
 2. timed: K steps of V videos per GPU enqueued at once (saturation); the
    window runs from the end of warm-up to the completion (stream-synchronised)
    of the last timed video; ``value`` = K*V*N / window;
-3. latency: Poisson arrivals at BASELINE config #5's fixed mean interval
+3. (``--full``) latency: Poisson arrivals at BASELINE config #5's fixed mean interval
    (``--latency-mi``, 10 ms: reference client.py:44) and then at
    ``--latency-load`` x the measured throughput, each for
    ``--latency-seconds``; p50/p99 are enqueue -> result of those requests
@@ -51,8 +59,8 @@ shared by all GPUs, runners pull clips decoded on any GPU over xGMI),
 config #2), ``rnb`` (LargeSmall routing + Batcher step), ``two-stage``
 (BASELINE config #3, RCCL), ``segment`` (BASELINE config #4), ``fused``
 (single-process in-process engine, the upper bound the pipeline is compared
-with). At 1 GPU the literal BASELINE configs #2 and #4 also run briefly
-(``literal`` in the JSON line).
+with). At 1 GPU with ``--full`` the literal BASELINE configs #2 and #4 also
+run briefly (``literal`` in the JSON line).
 
 The reference publishes only 11.30 videos/s (R(2+1)D-18, fp32, one older
 NVIDIA GPU, load-bound at 11.1 req/s offered) and BASELINE.json
@@ -74,8 +82,9 @@ import time
 BASELINE_VIDEOS_PER_S = 11.30
 METRIC = "videos/sec (whole node) + p50/p99 end-to-end latency, R(2+1)D-34 8-frame clips"
 ITERATOR = "rnb_amd.models.r2p1d.model.R2P1DVideoPathIterator"
-LOADER = "rnb_amd.models.r2p1d.model.R2P1DLoader"
+LOADER = "bench.SeededLoader"        # R2P1DLoader, a video's clips fixed by (--seed, id)
 RUNNER = "rnb_amd.models.r2p1d.model.R2P1DRunner"
+DUMP_RUNNER = "bench.DumpingRunner"  # R2P1DRunner that keeps the last step's logits
 
 
 def parse_args(argv=None):
@@ -214,7 +223,26 @@ def parse_args(argv=None):
                          "headline line is printed after them, so keep this bounded")
     ap.add_argument("--trace", type=str, default=None,
                     help="(fused) write a per-kernel time table of the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark "
+                         "measures or checks: the Poisson latency phases (--latency-*), the "
+                         "recomputation of sampled served logits with the fp32 nn.Module "
+                         "(numerics), the literal BASELINE config runs at 1 GPU, the cross-GPU "
+                         "runs at N GPUs and (fused) the eager recomputation of a step's "
+                         "predictions. Without it a run sets up, warms up, times the steps "
+                         "and prints the result line")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step's model calls "
+                         "returned as float32 DIR/<name>.npy: logits.npy (per-clip logits "
+                         "[clips, classes], videos in request order) and video_logits.npy "
+                         "(their per-video sums); fused: predictions.npy (per-video argmax). "
+                         "A video's clips depend on --seed and its id only, so two runs with "
+                         "the same arguments serve the same inputs")
     args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run does only what the headline figure needs
+        args.latency_seconds = 0.0
+        args.check = args.literal = args.cross_gpu_extras = False
     if args.replicas is None:
         args.replicas = 4 if args.pipeline == "whole" else 3
     if args.lanes is None:
@@ -228,7 +256,8 @@ LARGE_CLIPS = 15        # the sampler's large videos (reference sampler.py: [1, 
 def pipeline_config(args, n_gpus: int) -> dict:
     """The pipeline JSON (benchmark.py format) for ``--pipeline``."""
     gpus = list(range(n_gpus))
-    runner = {"model": RUNNER, "start_index": 1, "end_index": 5,
+    runner = {"model": DUMP_RUNNER if getattr(args, "dump_outputs", None) else RUNNER,
+              "start_index": 1, "end_index": 5,
               "max_clips": args.clips_per_batch, "bucket_step": args.bucket_step,
               "max_batch_videos": args.video_batch, "batch_wait_ms": args.batch_wait_ms}
     if args.lanes > 1:
@@ -321,6 +350,9 @@ def pipeline_config(args, n_gpus: int) -> dict:
     if args.slots:
         for st in steps[:-1]:
             st["num_shared_tensors"] = args.slots
+    # a video's clip count and start frames follow from (--seed, video id), not
+    # from which loader process takes it: every run serves the same inputs
+    steps[0]["sample_seed"] = args.seed
     return {"video_path_iterator": ITERATOR, "defaults": defaults, "pipeline": steps}
 
 
@@ -328,8 +360,10 @@ def run_pipeline(args, world: int) -> dict:
     """Rank 0: one launcher run (benchmark.py path) over ``args.gpus`` GPUs."""
     from rnb_amd import launcher
     root = os.path.dirname(os.path.abspath(__file__))
-    out_dir = os.path.join(root, "logs", "bench")
-    os.makedirs(out_dir, exist_ok=True)
+    logs = work_root(root)
+    out_dir = os.path.join(logs, "bench")
+    if root not in sys.path:
+        sys.path.insert(0, root)    # the loader / runner processes import bench.<plugin>
     name = "bench-%s-%s-%s-%dgpu" % (args.pipeline, args.dtype, args.bn, args.gpus)
     cfg_path = os.path.join(out_dir, name + ".json")
     with open(cfg_path, "w") as f:
@@ -341,7 +375,7 @@ def run_pipeline(args, world: int) -> dict:
     largv = ["-c", cfg_path, "-mi", "0", "-v", str(per_step * args.steps),
              "--warmup-videos", str(per_step * args.warmup), "--seed", str(args.seed),
              "--barrier-timeout", str(args.barrier_timeout), "--json-out", res_path,
-             "--log-root", os.path.join(root, "logs")]
+             "--log-root", logs]
     if args.latency_seconds > 0:
         largv += ["--latency-seconds", str(args.latency_seconds),
                   "--latency-load", str(args.latency_load)]
@@ -354,14 +388,198 @@ def run_pipeline(args, world: int) -> dict:
         shutil.rmtree(check_dir, ignore_errors=True)
         os.makedirs(check_dir)
         os.environ["RNB_CHECK_DIR"] = check_dir
+    dump_dir = None
+    if args.dump_outputs:
+        import shutil
+        # the final-layer runners keep the last timed step's logits (request
+        # ids are 1-based, warm-up first) and write them here when they end
+        dump_dir = os.path.join(args.dump_outputs, "parts")
+        shutil.rmtree(dump_dir, ignore_errors=True)
+        os.makedirs(dump_dir)
+        last = per_step * (args.warmup + args.steps)
+        os.environ["RNB_DUMP_DIR"] = os.path.abspath(dump_dir)
+        os.environ["RNB_DUMP_IDS"] = "%d,%d" % (last - per_step + 1, last)
     t0 = time.time()
     res = launcher.run(launcher.build_parser().parse_args(largv))
     res["t_launch"] = t0
     os.environ.pop("RNB_CHECK_DIR", None)
+    os.environ.pop("RNB_DUMP_DIR", None)
+    os.environ.pop("RNB_DUMP_IDS", None)
+    res["dump_dir"] = dump_dir
     res["check_dir"] = check_dir
     res["wall_s"] = time.time() - t0
-    res["config_path"] = os.path.relpath(cfg_path, root)
+    res["config_path"] = os.path.relpath(cfg_path, root) if logs.startswith(root + os.sep) \
+        else cfg_path
     return res
+
+
+def work_root(root: str) -> str:
+    """Where a run writes its pipeline config, job logs, tuning cache and
+    result files: ``logs/`` of the checkout when this user can create and
+    replace files there, else a per-user folder under the system's temporary
+    directory (a read-only checkout, or files another user left)."""
+    import tempfile
+    own = os.path.join(tempfile.gettempdir(), "rnb-logs-%d" % os.getuid())
+    for base in (os.path.join(root, "logs"), own):
+        sub = os.path.join(base, "bench")
+        try:
+            os.makedirs(sub, exist_ok=True)
+            with tempfile.TemporaryFile(dir=base), tempfile.TemporaryFile(dir=sub):
+                pass
+            if all(os.access(os.path.join(sub, f), os.W_OK) for f in os.listdir(sub)):
+                return base
+        except OSError:
+            continue
+    return tempfile.mkdtemp(prefix="rnb-logs-")
+
+
+# Pipeline plugins of the benchmark (named "bench.<class>" in its configs and
+# loaded by every loader / runner process): defined on first use, so that
+# importing this file stays free of torch.
+_PLUGINS = ("SeededLoader", "DumpingRunner")
+DUMP_DIR_ENV, DUMP_IDS_ENV = "RNB_DUMP_DIR", "RNB_DUMP_IDS"
+
+
+def __getattr__(name):
+    if name in _PLUGINS:
+        _define_plugins()
+        return globals()[name]
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+def _define_plugins() -> None:
+    import numpy as np
+    import torch
+    from rnb_amd.models.r2p1d.model import R2P1DLoader, R2P1DRunner
+    from rnb_amd.timecard import TimeCardList
+
+    class SeededLoader(R2P1DLoader):
+        """R2P1DLoader whose sampler is reseeded per video: a video's clip
+        count and start frames follow from (sample_seed, video id), not from
+        which loader process takes it or what that process sampled before, so
+        a run's inputs repeat. The clip-count distribution is the sampler's."""
+
+        def __init__(self, device, sample_seed=0, **kwargs):
+            super().__init__(device, **kwargs)
+            self.sample_seed = int(sample_seed)
+
+        def _sample(self, path, time_card=None):
+            vid, _ = self.decoder.probe(path)
+            self.sampler.rng.seed(self.sample_seed * 1000003 + int(vid))
+            return super()._sample(path, time_card)
+
+    class DumpingRunner(R2P1DRunner):
+        """R2P1DRunner that keeps the logits of the requests RNB_DUMP_IDS =
+        "first,last" names on the GPU (one device copy per call: the next
+        graph replay overwrites the output) and writes them to RNB_DUMP_DIR
+        as ``part_p<pid>.npz`` once the runner has left its loop."""
+
+        def __init__(self, device, **kwargs):
+            super().__init__(device, **kwargs)
+            self._dump_dir = os.environ.get(DUMP_DIR_ENV) or None
+            try:
+                lo, hi = (int(v) for v in os.environ.get(DUMP_IDS_ENV, "").split(","))
+            except ValueError:
+                lo, hi = 1, 0
+            self._dump_lo, self._dump_hi = lo, hi
+            self._dump = []                  # (request id, segment, logits on the GPU)
+
+        def __call__(self, tensors, non_tensors, time_card):
+            out = super().__call__(tensors, non_tensors, time_card)
+            if self._dump_dir and self.end_index == 5 and time_card is not None:
+                self._keep(out[0][0], time_card)
+            return out
+
+        def _keep(self, y, time_card) -> None:
+            cards = (time_card.time_cards if isinstance(time_card, TimeCardList)
+                     else [time_card])
+            if not any(self._dump_lo <= tc.id <= self._dump_hi for tc in cards):
+                return
+            rows = (list(time_card.item_rows) if isinstance(time_card, TimeCardList)
+                    and getattr(time_card, "item_rows", None) else [y.shape[0]])
+            if len(rows) != len(cards):        # Batcher items: several videos per item
+                rows = [tc.num_clips if tc.num_clips is not None else -1 for tc in cards]
+            if min(rows) < 0 or sum(rows) != y.shape[0]:
+                return
+            if self.lanes > 1:                 # y was written on a lane stream
+                torch.cuda.current_stream(self.device).wait_event(self.last_event)
+            keep, off = y.float().clone(), 0
+            for tc, n in zip(cards, rows):
+                if self._dump_lo <= tc.id <= self._dump_hi and n:
+                    self._dump.append((int(tc.id), int(tc.sub_id or 0), keep[off:off + n]))
+                off += n
+
+        def runtime_stats(self) -> dict:
+            self.write_dump()                  # runner.py asks once, after its loop
+            return super().runtime_stats()
+
+        def write_dump(self) -> None:
+            if not self._dump_dir or not self._dump:
+                return
+            kept, self._dump = self._dump, []
+            if self.device.type == "cuda":
+                torch.cuda.synchronize(self.device)   # the copies ran on the runner's stream
+            np.savez(os.path.join(self._dump_dir, "part_p%d.npz" % os.getpid()),
+                     ids=np.asarray([k[0] for k in kept], dtype=np.int64),
+                     subs=np.asarray([k[1] for k in kept], dtype=np.int64),
+                     rows=np.asarray([k[2].shape[0] for k in kept], dtype=np.int64),
+                     logits=torch.cat([k[2] for k in kept]).cpu().numpy().astype(np.float32))
+
+    for cls in (SeededLoader, DumpingRunner):
+        cls.__module__, cls.__qualname__ = __name__, cls.__name__
+        globals()[cls.__name__] = cls
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def write_outputs(out_dir: str, arrays: dict, seed: int) -> dict:
+    """--dump-outputs: ``out_dir/<name>.npy`` in float32, at most
+    DUMP_MAX_BYTES in all; of a larger array a fixed sample of its rows (drawn
+    with ``seed``, in order). Returns what was written, for the JSON line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays))
+    info = {}
+    for name, arr in sorted(arrays.items()):
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        total = arr.shape[0]
+        row_bytes = max(1, arr.nbytes // max(1, total))
+        if arr.nbytes > budget:
+            keep = np.sort(np.random.default_rng(seed).choice(
+                total, size=budget // row_bytes, replace=False))
+            arr = arr[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        info[name] = {"shape": list(arr.shape), "rows_of": total}
+    return info
+
+
+def merge_dump(args, dump_dir: str) -> dict:
+    """Join what the final-layer runner processes kept of the last timed step
+    (DumpingRunner's ``part_p<pid>.npz`` files) in request order (segments
+    of a video in row order) and write it as --dump-outputs promises."""
+    import glob
+    import shutil
+    import numpy as np
+    items = []
+    for path in sorted(glob.glob(os.path.join(dump_dir, "part_p*.npz"))):
+        with np.load(path) as part:
+            logits, off = part["logits"], 0
+            for rid, sub, n in zip(part["ids"], part["subs"], part["rows"]):
+                items.append((int(rid), int(sub), logits[off:off + int(n)]))
+                off += int(n)
+    shutil.rmtree(dump_dir, ignore_errors=True)
+    if not items:
+        return {"error": "the runners kept no outputs of the last timed step"}
+    items.sort(key=lambda it: it[:2])
+    ids = sorted({it[0] for it in items})
+    row = {rid: i for i, rid in enumerate(ids)}
+    videos = np.zeros((len(ids), items[0][2].shape[1]), dtype=np.float32)
+    for rid, _, rows in items:
+        videos[row[rid]] += rows.sum(axis=0)
+    info = write_outputs(args.dump_outputs, {"logits": np.concatenate([it[2] for it in items]),
+                                             "video_logits": videos}, args.seed)
+    return {"dir": args.dump_outputs, "videos": len(ids), "arrays": info}
 
 
 _T_START = time.time()
@@ -399,6 +617,10 @@ def main(argv=None) -> int:
         value = n_videos / window if ok and window > 0 else 0.0
         mi_phase = next((ph for ph in res.get("latency_phases", []) if ph["kind"] == "mi"),
                         None)
+
+        def lat_ms(key):
+            # the Poisson phases run with --full (and --latency-seconds > 0)
+            return round(lat[key], 3) if key in lat else None
         rec = {
             "metric": METRIC, "value": round(value, 2), "unit": "videos/s",
             "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
@@ -412,8 +634,8 @@ def main(argv=None) -> int:
             "dtype": args.dtype,
             "data": "synthetic clips (GPU-decoded, reference sampler clip counts), "
                     "random-init weights",
-            "p50_ms": round(lat.get("p50_ms", float("nan")), 3),
-            "p99_ms": round(lat.get("p99_ms", float("nan")), 3),
+            "full": args.full,
+            "p50_ms": lat_ms("p50_ms"), "p99_ms": lat_ms("p99_ms"),
             "latency_tail_breakdown": lat.get("tail_breakdown"),
             "latency_offered_videos_per_s": round(lat.get("offered_videos_per_s", 0.0), 1),
             "latency_requests": lat.get("count", 0),
@@ -469,6 +691,13 @@ def main(argv=None) -> int:
         timeline = {"start_to_launch": round(res.get("t_launch", _T_START) - _T_START, 2)}
         timeline.update({"headline." + k: v for k, v in (res.get("timeline_s") or {}).items()})
         timeline["headline_total"] = round(res.get("wall_s", 0.0), 2)
+        if res.get("dump_dir"):
+            t_x = time.time()
+            rec["outputs"] = merge_dump(args, res["dump_dir"])
+            timeline["dump_outputs"] = round(time.time() - t_x, 2)
+            if rec["outputs"].get("videos") != args.videos_per_step * args.gpus:
+                print("bench.py: --dump-outputs: %s" % (rec["outputs"],), file=sys.stderr)
+                rc = 1
         t_x = time.time()
         if args.gpus > 1 and args.cross_gpu_extras and args.pipeline == "aggressive":
             rec["cross_gpu"] = run_cross_gpu_extras(args)
@@ -550,7 +779,8 @@ def run_cross_gpu_extras(args) -> dict:
             # refuses send/recv between two ranks of one device
             out[topo] = {"skipped": "RNB_FOLD_GPUS: RCCL edges need distinct GPUs"}
             continue
-        path = os.path.join(root, "logs", "bench", "cross-%s-%dgpu.json" % (topo, args.gpus))
+        path = os.path.join(work_root(root), "bench",
+                            "cross-%s-%dgpu.json" % (topo, args.gpus))
         if os.path.exists(path):
             os.remove(path)                     # never report a previous run's record
         pipe = ["--pipeline", topo]
@@ -565,7 +795,7 @@ def run_cross_gpu_extras(args) -> dict:
                # captures in each extra's setup (4 short steps, padding cost small)
                "--bucket-step", (args.bucket_step if str(args.bucket_step).startswith("geo")
                                  else str(max(int(args.bucket_step), 16))),
-               "--no-check", "--no-cross-gpu-extras", "--json-out", path]
+               "--full", "--no-check", "--no-cross-gpu-extras", "--json-out", path]
         env = {k: v for k, v in os.environ.items()
                if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE",
                             "MASTER_ADDR", "MASTER_PORT", "GROUP_RANK", "ROLE_RANK",
@@ -673,9 +903,9 @@ def run_literal_extras(args) -> dict:
             out[key] = {"skipped": "literal-config time budget spent (%.0f s left)" % budget}
             continue
         t0 = time.time()
-        path = os.path.join(root, "logs", "bench", "literal-%s.json" % key)
+        path = os.path.join(work_root(root), "bench", "literal-%s.json" % key)
         argv = ["--gpus", "1", "--dtype", args.dtype, "--bn", args.bn, "--depth",
-                str(args.depth), "--no-literal"] + extra
+                str(args.depth), "--full", "--no-literal"] + extra
         try:
             sub = _run_sub_bench(argv, path, budget)
             mi = sub.get("latency_mi10") or {}
@@ -869,7 +1099,7 @@ def run_fused(args) -> int:
     # replays returned
     checked = matched = 0
     rep0 = eng.replicas[0]
-    for i, b in enumerate(step_batches[args.warmup][:4]):
+    for i, b in enumerate(step_batches[args.warmup][:4] if args.full else []):
         vids = torch.tensor([vid for vid, st in b for _ in st], dtype=torch.int32,
                             device=device)
         starts = torch.tensor([s for _, st in b for s in st], dtype=torch.int32, device=device)
@@ -890,6 +1120,13 @@ def run_fused(args) -> int:
         got = result_bufs[args.warmup][i][:len(b)]
         checked += len(b)
         matched += int((arg.cpu() == got).sum())
+    outputs = None
+    if args.dump_outputs and args.steps > 0:
+        # the last timed step's per-video predictions, in arrival order per batch
+        last = [buf[:len(b)].numpy() for buf, b in zip(result_bufs[-1], step_batches[-1])]
+        out_dir = args.dump_outputs if world == 1 else \
+            os.path.join(args.dump_outputs, "rank%d" % rank)
+        outputs = write_outputs(out_dir, {"predictions": np.concatenate(last)}, args.seed)
     n_videos = args.steps * vps
     clips = sum(len(st) for sb in step_batches[args.warmup:] for b in sb for _, st in b)
     stats = percentile_stats(np.asarray(lat_ms) / 1e3)
@@ -921,6 +1158,7 @@ def run_fused(args) -> int:
             "effective_tflops": round(flops / 1e12, 1),
             "videos_ok": int(preds_all),
             "videos_checked": checked, "videos_match_eager": matched,
+            "full": args.full, "outputs": outputs,
             "config": {"model": "R(2+1)D-%d" % args.depth,
                        "global_batch": vps * world, "seq_len": 8,
                        "parallelism": "dp%d (replicated runners)" % world,

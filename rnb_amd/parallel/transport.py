@@ -248,6 +248,10 @@ IPC_CHUNK_BYTES = int(os.environ.get("RNB_IPC_CHUNK_MB", "2048")) << 20
 # superseded interprocess events a process keeps waiting for their marker
 # before it synchronises the oldest one (IpcRing._retire)
 RETIRE_MAX = 64
+# the superseded events of every ring of this process, oldest first:
+# (marker, event, ring that counts it) -- one list, so the bound holds per
+# process however many rings it produces or consumes
+_RETIRING: list = []
 
 
 class IpcRing(RingBase):
@@ -343,7 +347,6 @@ class IpcRing(RingBase):
         self.events_opened = 0
         self.events_created = 0
         self.events_destroyed = 0       # created or opened events freed again
-        self._retiring = None           # [(marker, event)] awaiting destruction
         self.stale_event_waits = 0      # stream waits ROCm refused on completed events
         self.gpu_waits = 0              # stream waits ordered on the GPU
         self._dev = None
@@ -377,7 +380,6 @@ class IpcRing(RingBase):
         st["_cid"] = None
         st["_views"] = None
         st["_token"] = None
-        st["_retiring"] = None
         return st
 
     @property
@@ -450,31 +452,30 @@ class IpcRing(RingBase):
         after the first use of its replacement (see the class docstring)."""
         if ev is None:
             return
-        if self._retiring is None:
-            self._retiring = []
         marker = torch.cuda.Event()
         marker.record(stream)
-        self._retiring.append((marker, ev))
+        _RETIRING.append((marker, ev, self))
         self._reap()
 
     def _reap(self, wait_all: bool = False) -> None:
-        """Destroy retired events whose marker completed (all of them, waiting
-        if needed, with ``wait_all``; the oldest when over RETIRE_MAX)."""
-        if not self._retiring:
+        """Destroy this process's retired events whose marker completed (this
+        ring's all, waiting if needed, with ``wait_all``; the oldest of any
+        ring when the process holds more than RETIRE_MAX)."""
+        if not _RETIRING:
             return
         from ..ops import native
         rt = native.runtime()
         keep = []
-        over = len(self._retiring) - RETIRE_MAX
-        for k, (marker, ev) in enumerate(self._retiring):
-            if wait_all or k < over:
+        over = len(_RETIRING) - RETIRE_MAX
+        for k, (marker, ev, ring) in enumerate(_RETIRING):
+            if (wait_all and ring is self) or k < over:
                 marker.synchronize()
             elif not marker.query():
-                keep.append((marker, ev))
+                keep.append((marker, ev, ring))
                 continue
             rt.event_destroy(ev)
-            self.events_destroyed += 1
-        self._retiring = keep
+            ring.events_destroyed += 1
+        _RETIRING[:] = keep
 
     def _release_event(self, cid: int, idx: int):
         """(event, superseded opened event or None) of consumer ``cid``'s

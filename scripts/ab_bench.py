@@ -18,7 +18,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE = ["--warmup", "2", "--no-literal", "--no-check"]
+BASE = ["--full", "--warmup", "2", "--no-literal", "--no-check"]
 
 
 def run(name, env, extra, timeout, idx):

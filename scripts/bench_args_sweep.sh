@@ -20,7 +20,7 @@ for args in "${SW[@]}"; do
   for w in $args; do
     if [[ ${#rest[@]} -eq 0 && $w == *=* && $w != --* ]]; then envs+=("$w"); else rest+=("$w"); fi
   done
-  env "${envs[@]}" timeout -k 10 600 python bench.py --steps "${STEPS:-20}" --warmup 2 \
+  env "${envs[@]}" timeout -k 10 600 python bench.py --full --steps "${STEPS:-20}" --warmup 2 \
     --no-literal --no-check "${rest[@]}" > $log 2>&1
   rc=$?
   kill $hb 2>/dev/null

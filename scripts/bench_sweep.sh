@@ -9,7 +9,7 @@ python -m rnb_amd.build > /dev/null || exit 3
 for cfg in "$@"; do
   set -- $cfg
   name="vb$1_c$2_r$3"
-  timeout -k 10 300 python bench.py --steps 10 --warmup 2 --video-batch $1 \
+  timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --video-batch $1 \
       --clips-per-batch $2 --replicas $3 > gpurun_out/sweep/$name.log 2>&1
   rc=$?
   echo "$name rc=$rc $(grep -o '"value": [0-9.]*, ' gpurun_out/sweep/$name.log) \

@@ -78,11 +78,29 @@ def test_every_shipped_config_parses():
         assert spec.steps
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/config"), reason="reference not mounted")
-def test_reference_configs_parse_and_resolve():
-    """The reference's own JSON files are accepted unchanged."""
-    for name in os.listdir("/root/reference/config"):
-        spec = load_pipeline(os.path.join("/root/reference/config", name))
+def test_reference_configs_parse_and_resolve(tmp_path):
+    """Configs written with the reference's class paths (``models.r2p1d...``,
+    ``batcher.Batcher``: no ``rnb_amd.`` prefix) are accepted unchanged: every
+    shipped config, rewritten to those paths, parses and its classes load."""
+    def legacy(node):
+        if isinstance(node, dict):
+            return {k: legacy(v) for k, v in node.items()}
+        if isinstance(node, list):
+            return [legacy(v) for v in node]
+        if isinstance(node, str) and node.startswith("rnb_amd."):
+            return node[len("rnb_amd."):]
+        return node
+
+    names = sorted(f for f in os.listdir(CONFIGS) if f.endswith(".json"))
+    assert len(names) >= 10
+    for name in names:
+        with open(os.path.join(CONFIGS, name)) as f:
+            cfg = legacy(json.load(f))
+        assert "rnb_amd." not in json.dumps(cfg)
+        path = tmp_path / name
+        path.write_text(json.dumps(cfg))
+        spec = load_pipeline(str(path))
+        assert load_class(spec.video_path_iterator) is not None
         for step in spec.steps:
             assert load_class(step.model) is not None
             for g in step.groups:
