@@ -154,6 +154,39 @@ class R2P1DEngine:
         self.range_guard = (RangeGuard() if backend == "hip" and self.f32 and h3_enabled()
                             and device.type == "cuda"
                             and os.environ.get("RNB_H3_GUARD", "1") != "0" else None)
+        # a guarded call that trips has already applied a running-statistics
+        # step from non-finite sums: the BNs' running buffers live in one flat
+        # tensor, so one copy before a call keeps the pre-call state for
+        # range_fallback to restore (running_shadow, range_fallback(pre=...))
+        self._run_flat: Optional[torch.Tensor] = None
+        self._run_pre: Optional[torch.Tensor] = None
+        # (RNB_RUNNING_SHADOW=0: no copy, a tripped call's step stays; A/B)
+        if (self.range_guard is not None and self.bn_mode == "batch"
+                and os.environ.get("RNB_RUNNING_SHADOW", "1") != "0"):
+            self._flatten_running()
+
+    def _flatten_running(self) -> None:
+        """Re-home every BN's running_mean / running_var as views of one flat
+        fp32 tensor (each padded to 64 floats, so the views keep the 256-byte
+        alignment of separate allocations)."""
+        bns = [op.bn for op in self.ops if op.bn is not None]
+        if not bns:
+            return
+        step = [pad_to(b.channels, 64) for b in bns]
+        flat = torch.zeros(2 * sum(step), dtype=torch.float32, device=self.device)
+        at = 0
+        for b, s in zip(bns, step):
+            for name in ("running_mean", "running_var"):
+                view = flat[at:at + b.channels]
+                view.copy_(getattr(b, name))
+                setattr(b, name, view)
+                at += s
+        self._run_flat = flat
+
+    def running_shadow(self) -> Optional[torch.Tensor]:
+        """A buffer ``forward(running_shadow=...)`` fills with the pre-call
+        running statistics (None: this engine keeps none)."""
+        return None if self._run_flat is None else torch.empty_like(self._run_flat)
 
     # ---------------------------------------------------------------- build
     def _name(self) -> str:
@@ -360,7 +393,8 @@ class R2P1DEngine:
     def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None,
                 packed: bool = False, clip_offsets=None,
                 clip_offsets_dev: Optional[torch.Tensor] = None,
-                out_indirect: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out_indirect: Optional[torch.Tensor] = None,
+                running_shadow: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x: NDHWC boundary tensor (or NCDHW fp32 for backend=module); with
         ``packed``, the stem's pair-packed input (``input_shape(n, True)``).
         ``clip_offsets`` (bn_mode='batch'): clip ranges of the videos in the
@@ -372,7 +406,10 @@ class R2P1DEngine:
         forward can be captured in a HIP graph.
         ``out_indirect`` (``supports_out_indirect`` engines): device int64 [1]
         holding the address the final BatchNorm apply writes to (rows of the
-        returned tensor's shape) -- read when the kernel runs, not here."""
+        returned tensor's shape) -- read when the kernel runs, not here.
+        ``running_shadow`` (from ``running_shadow()``): receives the BNs'
+        running statistics as they are before this call (one copy, first in
+        the stream), for ``range_fallback(pre=...)``."""
         if packed and not self.accepts_packed_input:
             raise ValueError("this engine's first op does not take a packed input")
         if self.backend == "module":
@@ -388,6 +425,8 @@ class R2P1DEngine:
             return torch.zeros(self.output_shape(0), dtype=self.output_dtype(),
                                device=x.device)
         hip = self.backend == "hip"
+        if running_shadow is not None and self._run_flat is not None:
+            running_shadow.copy_(self._run_flat)
         if hip and self.range_guard is not None:
             self.range_guard.activate()       # this engine's h3 launches flag into it
         bufs: Dict[str, torch.Tensor] = {"x": x}
@@ -619,33 +658,43 @@ class R2P1DEngine:
         """Eager forward that honours the h3 range guard: waits for the call,
         and when an h3 conv produced a non-finite value re-runs it on
         full-range kernels (``range_fallback``)."""
-        y = self.forward(x, out=out, clip_offsets=clip_offsets)
+        if self.range_guard is not None and self._run_flat is not None:
+            if self._run_pre is None:
+                self._run_pre = self.running_shadow()
+        y = self.forward(x, out=out, clip_offsets=clip_offsets, running_shadow=self._run_pre)
         if self.range_guard is not None:
             torch.cuda.current_stream(self.device).synchronize()
-            self.range_fallback(x, y, clip_offsets)
+            self.range_fallback(x, y, clip_offsets, pre=self._run_pre)
         return y
 
-    def range_fallback(self, x: torch.Tensor, y: torch.Tensor, clip_offsets=None) -> bool:
+    def range_fallback(self, x: torch.Tensor, y: torch.Tensor, clip_offsets=None,
+                       pre: Optional[torch.Tensor] = None) -> bool:
         """After a completed call on input ``x`` with output ``y``: if this
         engine's h3 range guard tripped, recompute ``y`` in place with every
-        conv on a full-range (non-h3) config and count it; True if it did."""
+        conv on a full-range (non-h3) config and count it; True if it did.
+        ``pre``: the running statistics before that call (the buffer its
+        ``forward(running_shadow=...)`` filled)."""
         g = self.range_guard
         if g is None or not g.tripped():
             return False
         g.reset()
         # the tripped call already applied its BatchNorm running-statistics
-        # step; the re-run would apply a second one: keep the state as the
-        # call left it (one EMA step per call, as the reference's single
-        # forward). (If the tripped call's statistics were non-finite, its
-        # step already poisoned the running buffers -- the pre-call state is
-        # not kept per call.)
-        bns = [op.bn for op in self.ops
-               if op.bn is not None and getattr(op.bn, "update_running", False)
-               and hasattr(op.bn, "running_mean")]
-        snap = [(b.running_mean.clone(), b.running_var.clone()) for b in bns]
+        # step, from sums that may be non-finite: put the pre-call state back
+        # and let the re-run apply the call's single EMA step (one step per
+        # call, as the reference's single forward)
+        snap = None
+        if pre is not None and self._run_flat is not None:
+            self._run_flat.copy_(pre)
+        else:
+            # no pre-call state was kept for this call: keep the state as the
+            # call left it (a non-finite step stays in the running buffers)
+            bns = [op.bn for op in self.ops
+                   if op.bn is not None and getattr(op.bn, "update_running", False)
+                   and hasattr(op.bn, "running_mean")]
+            snap = [(b, b.running_mean.clone(), b.running_var.clone()) for b in bns]
         with full_range():
             z = self.forward(x, clip_offsets=clip_offsets)
-        for b, (rm, rv) in zip(bns, snap):
+        for b, rm, rv in snap or ():
             b.running_mean.copy_(rm)
             b.running_var.copy_(rv)
         y.copy_(z)
@@ -761,6 +810,9 @@ class GraphedEngine:
         self.pool = None
         self.capture_s = 0.0
         self._last = None           # (bucket, n, clip offsets, replay no.) of the last replay
+        # per bucket: the running statistics before the bucket's last replay
+        # (first node of its graph), restored by range_fallback
+        self._run_pre: Dict[int, torch.Tensor] = {}
         self._replays: Dict[int, int] = {}      # replays per bucket
         # intermediate stages: each bucket graph's final BN apply writes through
         # a device-held pointer (int64 [1] per bucket), so a replay can target
@@ -802,7 +854,7 @@ class GraphedEngine:
                                "by a later call (more than one call in flight per engine)" % b)
         _, static_in, static_out = self.graphs[b]
         return self.engine.range_fallback(static_in[:n], static_out[:n] if out is None else out,
-                                          offs)
+                                          offs, pre=self._run_pre.get(b))
 
     def bucket_floor(self, n: int) -> int:
         """Largest bucket <= n (0 if none)."""
@@ -865,6 +917,10 @@ class GraphedEngine:
         if self.indirect_out:
             self._dst[b] = torch.zeros(1, dtype=torch.int64, device=self.device)
             kw["out_indirect"] = self._dst[b]
+        if eng.range_guard is not None:
+            shadow = eng.running_shadow()
+            if shadow is not None:
+                self._run_pre[b] = kw["running_shadow"] = shadow
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=self.pool):
             static_out = eng.forward(static_in, **kw)

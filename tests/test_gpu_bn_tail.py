@@ -249,6 +249,7 @@ def test_engine_input_bn_rows_from_sums(monkeypatch, n, offs):
                      for op in eng.ops if op.bn is not None])
     (y0, c0), (y1, c1) = outs
     assert c0 == 0
+    assert c1 > 0, "no conv computed its input BN rows from the sums"
     scale = y0.abs().max().item()
     assert (y0 - y1).abs().max().item() <= 1e-5 * scale + 1e-6
     for (m0, v0), (m1, v1) in zip(runs[0], runs[1]):

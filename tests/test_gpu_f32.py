@@ -471,21 +471,35 @@ def test_graphed_batch_bn_per_video_matches_eager_and_module():
     dec = SyntheticDecoder(DEV, dtype=torch.float32)
     x = torch.cat([dec.decode(1, [0, 40, 80]), dec.decode(2, [10, 60]), dec.decode(3, [5])])
     offs = [0, 3, 5, 6]                       # 6 clips in the 8-clip bucket
-    r0 = [op.bn.running_mean.clone() for op in g.engine.ops if op.bn is not None]
+    # a common start state: the graph engine's running statistics as its
+    # warm-up and capture forwards left them, copied into the eager engine's
+    g.prepare()
+    gbns = [op.bn for op in g.engine.ops if op.bn is not None]
+    ebns = [op.bn for op in eager.ops if op.bn is not None]
+    assert len(gbns) == len(ebns) > 0
+    for p, q in zip(gbns, ebns):
+        q.running_mean.copy_(p.running_mean)
+        q.running_var.copy_(p.running_var)
+    r0 = [b.running_mean.clone() for b in gbns]
     with torch.no_grad():
         y = g.forward(x, clip_offsets=offs).clone()
         e = eager.forward(x, clip_offsets=offs)
         ref = torch.cat([mod.forward(x[a:b]) for a, b in zip(offs[:-1], offs[1:])])
         y1 = g.forward(x[:3]).clone()         # one video, offsets reset
+        eager.forward(x[:3])
     torch.cuda.synchronize()
     scale = ref.abs().max().item()
     assert (y - e).abs().max().item() <= 1e-5 * scale
     assert (y - ref).abs().max().item() <= 1e-3 * scale
     assert (y1 - y[:3]).abs().max().item() <= 1e-5 * scale
-    # running statistics: graph (device EMA) after capture warm-ups + 2 calls
-    # vs replaying the same per-segment EMA steps on the host
-    bns = [op.bn for op in g.engine.ops if op.bn is not None]
-    assert any((b.running_mean - r).abs().max().item() > 0 for b, r in zip(bns, r0))
+    # running statistics: the graph's device-side update (segment count = the
+    # bucket size, padded with empty videos) vs the eager engine's (segment
+    # count = videos) after the same two calls from the common start state
+    # (against the fp64 module: tests/test_gpu_bn_state.py)
+    assert any((b.running_mean - r).abs().max().item() > 0 for b, r in zip(gbns, r0))
+    for i, (p, q) in enumerate(zip(gbns, ebns)):
+        assert torch.allclose(p.running_mean, q.running_mean, rtol=1e-5, atol=1e-6), i
+        assert torch.allclose(p.running_var, q.running_var, rtol=1e-5, atol=1e-6), i
 
 
 @pytest.mark.parametrize("kind", ["spatial", "temporal"])

@@ -7,7 +7,10 @@ full-range kernels. Checks: inputs of magnitude 2^11 - 2^14 trip the guard on
 every h3 kernel family (direct, split-K, row band, temporal band) while 2^9
 does not; the full-range configs stay within 1e-5 of an fp64 conv at those
 magnitudes; a graphed batch-BN engine whose convs are forced onto h3 configs
-re-runs a tripped call and then matches an fp64 module forward.
+re-runs a tripped call and then matches an fp64 module forward; the BatchNorm
+running statistics after a tripped call (graphed and eager) are those of one
+fp64 forward from the pre-call state, not the non-finite step of the tripped
+launch.
 """
 import pytest
 import torch
@@ -124,6 +127,98 @@ def test_graphed_engine_reruns_tripped_call(monkeypatch):
     torch.cuda.synchronize()
     assert not eng.range_guard.tripped()
     assert not geng.range_fallback()
+
+
+def _force_h3(monkeypatch):
+    """Every conv on its first h3 (non split-K) config, as the tests above."""
+    from rnb_amd.ops import conv_f32
+    from rnb_amd.ops.conv_f32 import ConvLayerF32, is_h3, is_h3k
+    orig = ConvLayerF32._config_for
+
+    def forced(self, x_shape):
+        if conv_f32._FULL_RANGE[0]:
+            return orig(self, x_shape)
+        c = [i for i in self.candidates(x_shape) if is_h3(i) and not is_h3k(i)]
+        if self.tune_with_affine:
+            c = [i for i in c if self.affine_ok(i, x_shape)] or c
+        return c[0]
+    monkeypatch.setattr(ConvLayerF32, "_config_for", forced)
+
+
+@pytest.mark.parametrize("mode", ["graph", "eager"])
+def test_running_statistics_survive_a_range_fallback(mode, monkeypatch):
+    """The tripped launch applies a running-statistics step from non-finite
+    sums before the guard is read. The engine keeps the pre-call statistics
+    (one copy at the head of the bucket graph / of forward_checked), restores
+    them in range_fallback and lets the full-range re-run apply the call's one
+    EMA step: afterwards every BN's running_mean / running_var is finite and
+    equals the fp64 module's after one forward from the pre-call state, and
+    after the next (in-range) call the module's after its second forward.
+    Setup of test_graphed_engine_reruns_tripped_call; bounds of
+    tests/test_gpu_bn_state.py. The in-range replay is also bit-identical to
+    an engine built without the guard (no copy, no flag)."""
+    from rnb_amd.models.r2p1d.engine import GraphedEngine, R2P1DEngine
+    from rnb_amd.models.r2p1d.model import build_network
+    from test_gpu_bn_state import Ref64, running_vs_ref
+    _force_h3(monkeypatch)
+    net = build_network(4, 5, depth=34, seed=3)
+    eng = R2P1DEngine(net, DEV, backend="hip", bn_mode="batch", dtype=torch.float32)
+    assert eng.range_guard is not None
+    n = 2
+    x = _scaled_input(n, (4, 28, 28), eng.in_channels_p, 128, 2.0 ** 13, seed=5)
+    ref = Ref64(net, eng)
+    if mode == "graph":
+        geng = GraphedEngine(eng, 2, buckets=(2,), autotune=False, warmup=1)
+        geng.prepare()
+        torch.cuda.synchronize()
+    bns = [op.bn for op in eng.ops if op.bn is not None]
+    for b in bns:                                              # r0
+        assert torch.isfinite(b.running_mean).all() and torch.isfinite(b.running_var).all()
+    ref.load_running()
+
+    def call(inp):
+        if mode == "graph":
+            static_in, _ = geng.input_buffer(n)
+            static_in[:n].copy_(inp)
+            y = geng.replay(n)
+            torch.cuda.synchronize()
+            tripped = eng.range_guard.tripped()
+            assert geng.range_fallback() == tripped
+        else:
+            before = eng.range_guard.fallbacks
+            with torch.no_grad():
+                y = eng.forward_checked(inp)
+            tripped = eng.range_guard.fallbacks > before
+        torch.cuda.synchronize()
+        assert not eng.range_guard.tripped()
+        return y.clone(), tripped
+
+    y, tripped = call(x)
+    assert tripped and eng.range_guard.fallbacks == 1
+    for i, b in enumerate(bns):
+        assert torch.isfinite(b.running_mean).all(), i
+        assert torch.isfinite(b.running_var).all(), i
+    r = ref.forward(x, [0, n])
+    assert (y.double().cpu() - r).abs().max().item() <= 1e-3 * r.abs().max().item()
+    wm, wv = running_vs_ref(ref.pairs, "after the tripped call")
+    print("%s: running mean %.2e, var %.2e of the bound's scale after the fallback"
+          % (mode, wm, wv))
+    # the same input at 2^8 stays on the h3 kernels: the second EMA step
+    y2, tripped = call(x / 32)
+    assert not tripped and eng.range_guard.fallbacks == 1
+    r2 = ref.forward(x / 32, [0, n])
+    assert (y2.double().cpu() - r2).abs().max().item() <= 1e-3 * r2.abs().max().item()
+    running_vs_ref(ref.pairs, "after the in-range call")
+    if mode == "graph":
+        # keeping the pre-call statistics changes no logit of a call that stays in range
+        monkeypatch.setenv("RNB_H3_GUARD", "0")
+        plain = R2P1DEngine(net, DEV, backend="hip", bn_mode="batch", dtype=torch.float32)
+        monkeypatch.delenv("RNB_H3_GUARD")
+        assert plain.range_guard is None
+        gp = GraphedEngine(plain, 2, buckets=(2,), autotune=False, warmup=1)
+        yp = gp.forward(x / 32).clone()
+        torch.cuda.synchronize()
+        assert torch.equal(yp, y2)
 
 
 def test_bucket_padding_rows_do_not_trip_the_guard(monkeypatch):
