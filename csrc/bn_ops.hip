@@ -15,8 +15,6 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
-#include "bn_tail.h"
-
 static __device__ __forceinline__ float bn_lo(uint32_t u) { return __uint_as_float(u << 16); }
 static __device__ __forceinline__ float bn_hi(uint32_t u) { return __uint_as_float(u & 0xFFFF0000u); }
 static __device__ __forceinline__ uint32_t bn_pack(float a, float b) {
@@ -1029,30 +1027,8 @@ static int bn_apply_rows_per_block(long long M, int C, int rpc) {
   return (int)(R < 1 ? 1 : R);
 }
 
-// ---- BN tail (bn_tail.h): the finalize armed by the host for the next
-// producer launch that supports it, taken (and disarmed) by that launch ----
-static BnTail g_bn_tail = {};
 // block-tiled applies (bn_seg_apply_blk_f32_kernel); 0: the per-thread-row kernels
 static int g_bn_apply_blk = 1;
-// consumer-side scale / shift from sums (bn_tail.h BnAffSums); ss null = off
-static BnAffSums g_bn_aff = {};
-static int g_bn_aff_used = 0;
-const BnAffSums* bn_aff_armed() { return g_bn_aff.ss != nullptr ? &g_bn_aff : nullptr; }
-void bn_aff_mark_used() { g_bn_aff_used = 1; }
-static int g_bn_tail_taken = 0;
-
-BnTail bn_tail_take(long long waves) {
-  BnTail t = g_bn_tail;
-  if (t.ticket == nullptr || waves <= 0 || waves > 0x7FFFFFFF) {
-    t.ticket = nullptr;
-    return t;
-  }
-  t.expect = (int)waves;
-  g_bn_tail.ticket = nullptr;
-  g_bn_tail_taken = 1;
-  return t;
-}
-
 extern "C" {
 
 // Blocks per segment: a fixed 32, so the split of a video's rows -- and with
@@ -1168,49 +1144,7 @@ int rnb_bn_seg_stats_from_sums_f32(double* sums, int sums_c, const int* coffs, i
   return (int)hipGetLastError();
 }
 
-// Arms the BN tail for the next supporting producer launch (bn_tail.h):
-// ticket = device int, zero before the first launch (the tail leaves it zero).
-int rnb_bn_tail_arm(int* ticket, const double* sums, int sums_c, const int* coffs, int nseg,
-                    int rpc, int C, const float* gamma, const float* beta, float eps, float* ss) {
-  if (!ticket || !sums || !coffs || !gamma || !beta || !ss) return -1;
-  if (nseg <= 0 || C <= 0 || sums_c < C || rpc <= 0) return -2;
-  BnTail t = {};
-  t.ticket = ticket;
-  t.nseg = nseg; t.C = C; t.sums_c = sums_c; t.rpc = rpc;
-  t.sums = sums; t.coffs = coffs; t.gamma = gamma; t.beta = beta; t.eps = eps; t.ss = ss;
-  g_bn_tail = t;
-  g_bn_tail_taken = 0;
-  return 0;
-}
-void rnb_bn_tail_disarm() { g_bn_tail.ticket = nullptr; }
 void rnb_bn_set_apply_blk(int on) { g_bn_apply_blk = on; }
-// Arms consumer-side scale / shift (bn_tail.h BnAffSums) for the launches of
-// the next conv whose input BN rows are `ss`; disarm after them.
-int rnb_bn_aff_arm(const double* sums, int sums_c, const int* coffs, int nseg, int rpc, int C,
-                   const float* gamma, const float* beta, float eps, float* ss) {
-  if (!sums || !coffs || !gamma || !beta || !ss) return -1;
-  if (nseg <= 0 || C <= 0 || sums_c < C || rpc <= 0) return -2;
-  BnAffSums a = {};
-  a.sums = sums; a.sums_c = sums_c; a.nseg = nseg; a.rpc = rpc; a.coffs = coffs;
-  a.gamma = gamma; a.beta = beta; a.eps = eps; a.ss = ss;
-  g_bn_aff = a;
-  g_bn_aff_used = 0;
-  return 0;
-}
-void rnb_bn_aff_disarm() { g_bn_aff.ss = nullptr; }
-// 1 when a launch computed the armed rows since the last call (resets)
-int rnb_bn_aff_used() {
-  const int u = g_bn_aff_used;
-  g_bn_aff_used = 0;
-  return u;
-}
-// 1 when a launch took the tail armed last (then its scale / shift rows are
-// written by that launch); resets
-int rnb_bn_tail_taken() {
-  const int t = g_bn_tail_taken;
-  g_bn_tail_taken = 0;
-  return t;
-}
 
 // scale / shift (+ moments) from the epilogue sums only; the sums stay armed
 // for the batched running update (BnRunEntry.sums), which re-arms them

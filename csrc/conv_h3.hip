@@ -67,16 +67,9 @@ __device__ unsigned long long* h3_phase_buf;
 #define H3_PHASE(k) do {} while (0)
 #endif
 
-// consumer-side input BN rows (X6DStats.aff_sums): at most this many videos x
+// consumer-side input BN rows (X6DStats.aff): at most this many videos x
 // channels (the host's RNB_BN_AFF_SUMS_MAX cap)
 #define H3_AFF_SUMS_MAX 2304
-
-// split-K fix-up in the kernel (X6DStats.tick) for configs with at most this
-// many accumulator tiles per wave (the split-K set; bigger tiles would spill)
-#define H3_FIXUP_MAX_TILES 18
-// cache-policy bits of a buffer load / store: sc1 (bypass L1; stores write
-// through and leave no line in the XCD's L2)
-#define H3_SC1 16
 
 // input BatchNorm on load (AFF): per stage, the scale / shift of the step's
 // 32 channels for each clip the tile touches, [clip][sub][scale, shift][16]
@@ -308,13 +301,13 @@ void conv_h3_kernel(const ConvF32Params p, const X6DStats st) {
     t_begin = a;
     t_end = b;
   }
-  // AFF from sums (st.aff_sums): this conv computes the input BN's scale /
+  // AFF from sums (st.aff): this conv computes the input BN's scale /
   // shift rows from the producer's sums itself, with the formulas of
   // bn_seg_ss_from_sums_f32_kernel -- every video's rows into st.in_ss (each
   // block writes the same values; the wait below drains them before step 1's
   // DMA reads them) and step 0's rows straight into its LDS stage, while step
   // 0's activation and weight DMAs are in flight
-  const bool sums_mode = AFF && st.aff_sums != nullptr;
+  const bool sums_mode = AFF && st.aff.sums != nullptr;
   if (t_begin < t_end) issue(t_begin, 0, !sums_mode);
   if constexpr (AFF) {
     if (sums_mode) {
@@ -324,7 +317,7 @@ void conv_h3_kernel(const ConvF32Params p, const X6DStats st) {
       constexpr int NT = 64 * NW;
       constexpr int KG = (H3_AFF_SUMS_MAX + NT - 1) / NT;
       constexpr int KL = (H3_AFF_CLIPS * 64 + NT - 1) / NT;
-      const int E = st.aff_nseg * p.Cin_p;
+      const int E = st.aff.nseg * p.Cin_p;
       double a1[KG + KL], a2[KG + KL];
       float gm[KG + KL], bt[KG + KL];
       int rows[KG + KL], dst[KG + KL];            // dst: -1 none; global index; -2 - LDS index
@@ -351,12 +344,12 @@ void conv_h3_kernel(const ConvF32Params p, const X6DStats st) {
             }
           }
         }
-        const double* sp = st.aff_sums + (size_t)(v < 0 ? 0 : v) * 2 * st.aff_sums_c;
+        const double* sp = st.aff.sums + (size_t)(v < 0 ? 0 : v) * 2 * st.aff.sums_c;
         a1[k] = v >= 0 ? sp[c] : 0.0;
-        a2[k] = v >= 0 ? sp[st.aff_sums_c + c] : 0.0;
-        gm[k] = v >= 0 ? st.aff_gamma[c] : 0.f;
-        bt[k] = v >= 0 ? st.aff_beta[c] : 0.f;
-        rows[k] = v >= 0 ? (st.aff_coffs[v + 1] - st.aff_coffs[v]) * st.aff_rpc : 0;
+        a2[k] = v >= 0 ? sp[st.aff.sums_c + c] : 0.0;
+        gm[k] = v >= 0 ? st.aff.gamma[c] : 0.f;
+        bt[k] = v >= 0 ? st.aff.beta[c] : 0.f;
+        rows[k] = v >= 0 ? (st.aff.coffs[v + 1] - st.aff.coffs[v]) * st.aff.rpc : 0;
       }
       float* ssw = const_cast<float*>(st.in_ss);
       float* l0 = (float*)(lds + ACT_BYTES + W_BYTES);    // step 0's stage (slot 0)
@@ -370,7 +363,7 @@ void conv_h3_kernel(const ConvF32Params p, const X6DStats st) {
           mu = (float)m;
           va = (float)fmax(a2[k] / (double)rows[k] - m * m, 0.0);
         }
-        const float sc = rows[k] > 0 ? gm[k] * rsqrtf(va + st.aff_eps) : 0.f;
+        const float sc = rows[k] > 0 ? gm[k] * rsqrtf(va + st.aff.eps) : 0.f;
         const float sh = rows[k] > 0 ? bt[k] - mu * sc : 0.f;
         if (dst[k] >= 0) {
           const int v = dst[k] / p.Cin_p, c = dst[k] - v * p.Cin_p;
@@ -412,11 +405,6 @@ void conv_h3_kernel(const ConvF32Params p, const X6DStats st) {
 #pragma unroll
     for (int tc = 0; tc < TC; ++tc) acc[tp][tc] *= out_scale;     // exact: a power of two
   if (ksplit > 1) {                 // raw partial sums -> ws[kidx][m][c]
-    // in-kernel finish (st.tick): the partials go out sc1 (write-through,
-    // no line left in this XCD's L2) for the tile's last block to read sc1
-    // from any XCD -- the counter form of the inter-workgroup hand-off
-    // without an agent-scope fence (the guide's split-K recipe)
-    const bool fix = st.tick != nullptr && TP * TC <= H3_FIXUP_MAX_TILES;
     const uint32_t ws_bytes = (uint32_t)min((long long)ksplit * p.M * p.Cout_p * 4, 0x7FFFFF00LL);
     const __amdgpu_buffer_rsrc_t wsr =
         __builtin_amdgcn_make_buffer_rsrc((void*)st.ws, (short)0, ws_bytes, 0x00020000);
@@ -429,58 +417,13 @@ void conv_h3_kernel(const ConvF32Params p, const X6DStats st) {
         const uint32_t off = (m < p.M && c < p.Cout_p)
                                  ? (uint32_t)((((long long)kidx * p.M + m) * p.Cout_p + c) * 4)
                                  : X6D_INVALID;
-        if (fix)
-          __builtin_amdgcn_raw_buffer_store_b128(acc[tp][tc], wsr, off, 0, H3_SC1);
-        else
-          __builtin_amdgcn_raw_buffer_store_b128(acc[tp][tc], wsr, off, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(acc[tp][tc], wsr, off, 0, 0);
       }
     }
-    // x6d_splitk_reduce_kernel finishes (or, TP x TC > 18, the fix-up would
-    // cost the non-split form of this config registers: not built)
-    if (!fix) return;
-    // serial fix-up: the tile's last-arriving block sums the partials in
-    // split order -- the reduce kernel's order -- and runs the epilogue
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's partial: performed
-    __syncthreads();
-    int* flag = (int*)lds;                     // no DMA in flight (loop's last wait)
-    if (threadIdx.x == 0) *flag = atomicAdd(st.tick + wgid, 1) == ksplit - 1;
-    __syncthreads();
-    const bool last = *flag != 0;
-    __syncthreads();                           // every wave read the flag (the epilogue reuses lds)
-    if (!last) {
-      bn_tail_run(st.tail);
-      return;
-    }
-    if (threadIdx.x == 0) atomicExch(st.tick + wgid, 0);   // re-armed for the next launch
-#pragma unroll
-    for (int tc = 0; tc < TC; ++tc) {
-      const int c = c0 + (wc * TC + tc) * 16 + 4 * fq;
-      const float4 b4 = *(const float4*)(p.bias + c);
-#pragma unroll
-      for (int tp = 0; tp < TP; ++tp) {
-        const int m = p0 + (wp * TP + tp) * 16 + frow;
-        x6f32x4 v = (x6f32x4){b4.x, b4.y, b4.z, b4.w};
-        if (m < p.M && c < p.Cout_p) {
-          for (int k0 = 0; k0 < ksplit; k0 += 4) {     // 4 partials in flight
-            x6f32x4 part[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-              part[u] = k0 + u < ksplit
-                            ? __builtin_amdgcn_raw_buffer_load_b128(
-                                  wsr, (uint32_t)((((long long)(k0 + u) * p.M + m) * p.Cout_p + c) * 4),
-                                  0, H3_SC1)
-                            : (x6f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v += part[u];
-          }
-        }
-        acc[tp][tc] = v;
-      }
-    }
+    return;                         // x6d_splitk_reduce_kernel finishes
   }
   x6d_epilogue<TP, TC, NW, C_TILE, ST>(p, st, acc, p0, p.M, p0 + P_TILE, c0, wp, wc, lane, lds,
                                        NS * BUF);
-  bn_tail_run(st.tail);
 }
 
 // ===========================================================================
@@ -1186,7 +1129,7 @@ void conv_h3t_kernel(const ConvF32Params p, const X6DStats st) {
 // host side: config table + launcher (C ABI, ctypes)
 // ---------------------------------------------------------------------------
 struct ConvH3Config {
-  int p_tile, c_tile, threads, fixup;        // fixup: in-kernel split-K finish built
+  int p_tile, c_tile, threads;
   void (*kernel)(const ConvF32Params, const X6DStats);
   void (*kernel_st)(const ConvF32Params, const X6DStats);
   void (*kernel_aff)(const ConvF32Params, const X6DStats);       // + input BN on load
@@ -1194,7 +1137,7 @@ struct ConvH3Config {
 };
 
 #define H3CFG(TP, TC, WP, WC, MINB, NPROD)                                     \
-  {WP * TP * 16, WC * TC * 16, 64 * WP * WC, (TP) * (TC) <= H3_FIXUP_MAX_TILES,  \
+  {WP * TP * 16, WC * TC * 16, 64 * WP * WC,                                    \
    conv_h3_kernel<TP, TC, WP, WC, MINB, false, NPROD, false>,                   \
    conv_h3_kernel<TP, TC, WP, WC, MINB, true, NPROD, false>,                    \
    conv_h3_kernel<TP, TC, WP, WC, MINB, false, NPROD, true>,                    \
@@ -1221,7 +1164,36 @@ static const int kNumH3Configs = sizeof(kH3Configs) / sizeof(kH3Configs[0]);
 // memory of the engine being run or captured (rnb_h3_set_range_flag), or null
 static int* g_h3_range_flag = nullptr;
 
+// consumer-side scale / shift from sums (x6d_common.h BnAffSums), armed by
+// the host around the consumer's launches (rnb_bn_aff_arm): a launch whose
+// in_ss is the armed `ss` computes the rows; ss null = off. Process-global:
+// the host thread that arms it launches the conv (runner lanes launch from
+// the runner's one thread).
+static BnAffSums g_bn_aff = {};
+static int g_bn_aff_used = 0;
+
 extern "C" {
+
+// Arms consumer-side scale / shift for the launches of the next conv whose
+// input BN rows are `ss`; disarm after them.
+int rnb_bn_aff_arm(const double* sums, int sums_c, const int* coffs, int nseg, int rpc, int C,
+                   const float* gamma, const float* beta, float eps, float* ss) {
+  if (!sums || !coffs || !gamma || !beta || !ss) return -1;
+  if (nseg <= 0 || C <= 0 || sums_c < C || rpc <= 0) return -2;
+  BnAffSums a = {};
+  a.sums = sums; a.sums_c = sums_c; a.nseg = nseg; a.rpc = rpc; a.coffs = coffs;
+  a.gamma = gamma; a.beta = beta; a.eps = eps; a.ss = ss;
+  g_bn_aff = a;
+  g_bn_aff_used = 0;
+  return 0;
+}
+void rnb_bn_aff_disarm() { g_bn_aff.ss = nullptr; }
+// 1 when a launch computed the armed rows since the last call (resets)
+int rnb_bn_aff_used() {
+  const int u = g_bn_aff_used;
+  g_bn_aff_used = 0;
+  return u;
+}
 
 void rnb_h3_set_range_flag(int* flag) { g_h3_range_flag = flag; }
 int* rnb_h3_range_flag() { return g_h3_range_flag; }
@@ -1252,8 +1224,7 @@ int rnb_conv_h3_affine_ok(int config_id, int cin_p, int rows_per_clip) {
 
 int rnb_conv_h3_launch(const ConvF32Params* pp, int config_id, hipStream_t stream, double* sums,
                        const int* clip_seg, int stats_c, int ksplit, float* ws, float in_scale,
-                       float out_scale, const float* in_ss, const int* in_seg, int* tick,
-                       int tick_cap) {
+                       float out_scale, const float* in_ss, const int* in_seg) {
   if (config_id < 0 || config_id >= kNumH3Configs) return -1;
   ConvF32Params p = *pp;
   const ConvH3Config& cfg = kH3Configs[config_id];
@@ -1296,39 +1267,20 @@ int rnb_conv_h3_launch(const ConvF32Params* pp, int config_id, hipStream_t strea
   const bool aff = in_ss != nullptr;
   if (aff && (!in_seg || !rnb_conv_h3_affine_ok(config_id, p.Cin_p, p.To * p.Ho * p.Wo)))
     return -16;
-  if (const BnAffSums* a = aff ? bn_aff_armed() : nullptr) {
-    if (a->ss == in_ss) {                      // this conv computes its input BN rows
-      if (a->sums_c < p.Cin_p || (long long)a->nseg * p.Cin_p > H3_AFF_SUMS_MAX) return -18;
-      st.aff_sums = a->sums;
-      st.aff_sums_c = a->sums_c;
-      st.aff_nseg = a->nseg;
-      st.aff_rpc = a->rpc;
-      st.aff_coffs = a->coffs;
-      st.aff_gamma = a->gamma;
-      st.aff_beta = a->beta;
-      st.aff_eps = a->eps;
-      bn_aff_mark_used();
-    }
+  if (aff && g_bn_aff.ss == in_ss) {           // this conv computes its input BN rows
+    if (g_bn_aff.sums_c < p.Cin_p || (long long)g_bn_aff.nseg * p.Cin_p > H3_AFF_SUMS_MAX)
+      return -18;
+    st.aff = g_bn_aff;
+    g_bn_aff_used = 1;
   }
   if (ksplit > 1) {
     if (!ws || ksplit > 16) return -14;
     st.ksplit = ksplit;
     st.ws = ws;
-    if (tick && cfg.fixup) {
-      // serial fix-up in the kernel (X6DStats.tick): one dispatch
-      if (blocks > tick_cap) return -17;
-      st.tick = tick;
-      st.tail = bn_tail_take(blocks * ksplit * (cfg.threads / 64));
-      hipLaunchKernelGGL(aff ? (sums ? cfg.kernel_aff_st : cfg.kernel_aff)
-                             : (sums ? cfg.kernel_st : cfg.kernel),
-                         dim3((unsigned)(blocks * ksplit)), dim3(cfg.threads), 0, stream, p, st);
-      return (int)hipGetLastError();
-    }
     hipLaunchKernelGGL(aff ? cfg.kernel_aff : cfg.kernel, dim3((unsigned)(blocks * ksplit)),
                        dim3(cfg.threads), 0, stream, p, st);
     return rnb_x6d_splitk_reduce(&p, &st, stream);
   }
-  st.tail = bn_tail_take(blocks * (cfg.threads / 64));
   hipLaunchKernelGGL(aff ? (sums ? cfg.kernel_aff_st : cfg.kernel_aff)
                          : (sums ? cfg.kernel_st : cfg.kernel),
                      dim3((unsigned)blocks), dim3(cfg.threads), 0, stream, p, st);

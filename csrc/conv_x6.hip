@@ -343,7 +343,6 @@ __global__ __launch_bounds__(512) void x6d_splitk_reduce_kernel(const ConvF32Par
       }
     }
   }
-  bn_tail_run(st.tail);                 // BN finalize folded in (bn_tail.h)
 }
 
 // ===========================================================================
@@ -558,11 +557,8 @@ int rnb_x6d_splitk_reduce(const ConvF32Params* p, const X6DStats* st, hipStream_
   const int rpt = 4;                     // rows per thread: many threads, short chains
   const int rows_per_clip = p->To * p->Ho * p->Wo;
   const long long gx = (p->Cout_p / 4 + 63) / 64, gy = (p->M + 8 * rpt - 1) / (8 * rpt);
-  X6DStats s = *st;
-  // the BN tail rides on the kernel that writes the sums (8 waves per block)
-  s.tail = s.sums != nullptr ? bn_tail_take(gx * gy * 8) : BnTail{};
   hipLaunchKernelGGL(x6d_splitk_reduce_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(64, 8), 0,
-                     stream, *p, s, rpt, rows_per_clip);
+                     stream, *p, *st, rpt, rows_per_clip);
   return (int)hipGetLastError();
 }
 

@@ -7,7 +7,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "bn_tail.h"
 #include "conv_f32_common.h"
 #include "x6_common.h"
 
@@ -44,6 +43,22 @@ static __device__ __forceinline__ void x6d_dma16(const x6d_u32x4& rsrc, uint32_t
                : "memory");
 }
 
+// BN scale / shift computed by the CONSUMING conv from the producer's epilogue
+// sums (the h3 direct kernel's input BN on load, X6DStats.aff): every block
+// writes the rows of all nseg videos into `ss` (identical values from every
+// block), drains its stores and then DMAs them as it does a finalize's rows --
+// the finalize dispatch is gone and its latency overlaps the consumer's start.
+// Armed by the host around the consumer's launches (rnb_bn_aff_arm, conv_h3.hip).
+struct BnAffSums {
+  const double* sums;        // [nseg][2][sums_c]; null (X6DStats.aff) = off
+  int sums_c, nseg, rpc;
+  const int* coffs;          // [nseg + 1] clip offsets
+  const float* gamma;
+  const float* beta;
+  float eps;
+  float* ss;                 // [nseg][2][C] out (C = the consumer's Cin_p): the launch's in_ss
+};
+
 // training-mode BN statistics of the output, accumulated in the epilogue
 // (as the Winograd kernels' WinoParams.out_stats): per video and channel the
 // fp64 sum and sum of squares of the stored values
@@ -71,20 +86,9 @@ struct X6DStats {
   // the ReLU, which would hide a NaN) sets *oflag = 1 (a plain vector store to
   // host-coherent memory; the host re-runs the call on full-range kernels)
   int* oflag = nullptr;
-  // conv_h3.hip split-K only: per-tile arrival counters (zero between
-  // launches): the last of a tile's ksplit blocks sums the partials and runs
-  // the epilogue itself (no x6d_splitk_reduce_kernel dispatch). Null = off.
-  int* tick = nullptr;
-  // BN finalize folded into this launch (bn_tail.h); ticket null = off
-  BnTail tail = {};
   // conv_h3.hip AFF only: the input BN's scale / shift rows computed here into
-  // in_ss from the producer's sums (bn_tail.h BnAffSums); null = off
-  const double* aff_sums = nullptr;
-  int aff_sums_c = 0, aff_nseg = 0, aff_rpc = 0;
-  const int* aff_coffs = nullptr;
-  const float* aff_gamma = nullptr;
-  const float* aff_beta = nullptr;
-  float aff_eps = 0.f;
+  // in_ss from the producer's sums; aff.sums null = off
+  BnAffSums aff = {};
 };
 
 // true when any element of v is +-inf or NaN (v_cmp_class: sNaN, qNaN, -inf, +inf)

@@ -503,13 +503,7 @@ class R2P1DEngine:
         pending = None               # deferred (scale_shift, clip_seg) for the next conv
         free_after = self._free_after
         from ...ops import bn as bn_mod
-        # BN tail (csrc/bn_tail.h): a deferred BN's finalize folded into its
-        # producer conv when videos x channels <= this (the last wave walks
-        # them 512 at a time); 0 = a separate finalize dispatch per BN
-        # (opt-in: per-wave tickets on one address serialise at the memory
-        # side, +0.46 ms per one-clip forward, profiles/r6_ab_bn_tail_fixup.txt)
-        tail_max = int(os.environ.get("RNB_BN_TAIL_MAX", "0")) if hip else 0
-        # consumer-side scale / shift (csrc/bn_tail.h BnAffSums): a deferred BN
+        # consumer-side scale / shift (csrc/x6d_common.h BnAffSums): a deferred BN
         # whose consumer is an h3 direct config with BN on load, videos x
         # channels <= this, has its rows computed by that conv from the sums
         # (no finalize dispatch); 0 = off
@@ -573,26 +567,7 @@ class R2P1DEngine:
                     if coffs is None and self.f32:
                         coffs = torch.tensor([0, x.shape[0]], dtype=torch.int32,
                                              device=x.device)
-                    tail_ss = None
-                    if sums is not None and tail_max > 0 and bn_mod._RUN_SINK[0] is not None:
-                        yshape = tuple(op.layer.out_shape(src.shape))
-                        if (defer and self._defer_ok[i]
-                                and self.ops[i + 1].layer.accepts_input_affine(yshape)
-                                and (coffs.numel() - 1) * op.bn.channels_p <= tail_max):
-                            # the finalize rides on the producer's last launch (BN tail)
-                            tail_ss, kw["bn_tail"] = op.bn.tail_args(
-                                coffs, sums, yshape[1] * yshape[2] * yshape[3])
                     y = consume(lambda: op.layer.forward_hip(src, None, **kw))
-                    if tail_ss is not None:
-                        from ...ops.native import kernels as _kn
-                        if tuple(y.shape) != yshape:
-                            raise RuntimeError("%s: output %s, predicted %s" % (
-                                op.layer.name, tuple(y.shape), yshape))
-                        if not _kn().bn_tail_taken():
-                            _kn().bn_tail_disarm()     # this config's kernel has no tail
-                            tail_ss = None
-                        else:
-                            self.bn_tails = getattr(self, "bn_tails", 0) + 1
                     # segments in clip units: the BN kernels scale the clip
                     # offsets by the layer's rows per clip (T*H*W)
                     thw = y.shape[1] * y.shape[2] * y.shape[3]
@@ -602,13 +577,10 @@ class R2P1DEngine:
                         # statistics now; normalise + ReLU inside the next conv
                         if clip_seg is None:
                             clip_seg = self._clip_segments(coffs, x.shape[0], x.device)
-                        if tail_ss is not None:
-                            bn_mod._RUN_SINK[0].append((op.bn, sums, thw))
-                            pending = (tail_ss, clip_seg)
-                        elif (sums is not None and aff_max > 0 and bn_mod._RUN_SINK[0] is not None
-                              and coffs.numel() - 1 <= aff_videos
-                              and (coffs.numel() - 1) * op.bn.channels_p <= aff_max
-                              and self.ops[i + 1].layer.takes_sums_affine(y.shape)):
+                        if (sums is not None and aff_max > 0 and bn_mod._RUN_SINK[0] is not None
+                                and coffs.numel() - 1 <= aff_videos
+                                and (coffs.numel() - 1) * op.bn.channels_p <= aff_max
+                                and self.ops[i + 1].layer.takes_sums_affine(y.shape)):
                             # the consuming h3 direct conv computes the rows
                             ss, pending_aff = op.bn.aff_args(coffs, sums, thw)
                             bn_mod._RUN_SINK[0].append((op.bn, sums, thw))

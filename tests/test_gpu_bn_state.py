@@ -5,7 +5,7 @@ elsewhere; this file checks the state around them: the running statistics
 after a sequence of bucket-graph replays (every running-update route, with
 bucket padding and empty videos), the per-video epilogue sums and running
 accumulators re-armed after every use, the consumer-side scale / shift rows
-(csrc/bn_tail.h BnAffSums) under graphs, and the from-sums finalize kernels
+(csrc/x6d_common.h BnAffSums) under graphs, and the from-sums finalize kernels
 on badly centred data. The reference is a deep copy of the network in fp64,
 training mode, on the CPU, run once per video in video order -- what the
 reference project's one-video forwards do.
