@@ -7,6 +7,9 @@
 //  * rnb_preprocess      uint8 NFHWC3 -> normalised bf16 NDHWC8 (channels 3..7
 //                        zero), the fused form of the reference's
 //                        .float().permute() + slot copy.
+//  * rnb_nv12_to_clip /  decoder surfaces (NV12) or uploaded file spans (planar
+//    rnb_yuv420_to_clip  I420 of .y4m files, raw NV12) -> scaled, colour-
+//                        converted, normalised clips in the slot layout.
 //  * rnb_stem_pack       NDHWC8 -> zero-bordered pixel-pair-packed layout of
 //                        the stem conv (ops/conv.StemConv).
 //  * rnb_preprocess_packed  rnb_preprocess + rnb_stem_pack in one pass: uint8
@@ -226,6 +229,61 @@ __global__ __launch_bounds__(256) void nv12_clip_kernel(const uint8_t* __restric
   g = fminf(fmaxf(g, 0.f), 255.f) * a.scale[1] + a.shift[1];
   b = fminf(fmaxf(b, 0.f), 255.f) * a.scale[2] + a.shift[2];
   if (a.bf16) {
+    uint16_t* o = (uint16_t*)out + i * 8;
+    *(uint4*)o = make_uint4(nv12_bf_bits(r) | (nv12_bf_bits(g) << 16), nv12_bf_bits(b), 0u, 0u);
+  } else {
+    *(float4*)((float*)out + i * 4) = make_float4(r, g, b, 0.f);
+  }
+}
+
+// Planar / semi-planar YUV 4:2:0 frames inside an uploaded byte buffer (file
+// spans of a .y4m video, or raw NV12 dumps) -> the same normalised clips.
+// Frame f of clip c starts at byte offs[c] + f * frame_stride; its Y, U and V
+// samples start y_off / u_off / v_off bytes further on, with their own row
+// strides, and chroma samples are c_step bytes apart (1: planar I420, 2:
+// interleaved NV12 with v_off = u_off + 1). A Y4M frame is "FRAME\n" + payload,
+// so none of these bases is aligned to more than a byte: every source access
+// is a byte load (nv12_sample), and only the output side is vectorised. The
+// launcher checked every span against the buffer length.
+#define YUV420_MAX_CLIPS 32
+struct Yuv420ClipArgs {
+  Nv12ClipArgs g;                          // geometry, crop, normalisation, dtype
+  int F, y_stride, u_stride, v_stride, c_step;
+  long long frame_stride, y_off, u_off, v_off;
+  long long offs[YUV420_MAX_CLIPS];        // per-clip base (FROM_ARRAY: unused)
+};
+
+template <bool FROM_ARRAY>
+__global__ __launch_bounds__(256) void yuv420_clip_kernel(const uint8_t* __restrict__ buf,
+                                                          const long long* __restrict__ offs,
+                                                          void* __restrict__ out,
+                                                          Yuv420ClipArgs a) {
+  // grid = (pixel blocks of one frame, F, nclips): frame and clip are uniform
+  // per block, so the base offset is one scalar load and no thread divides a
+  // 64-bit pixel index (the cost of a flat grid: two such divisions per pixel)
+  const int ohw = a.g.out_w * a.g.out_h;
+  const int p = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (p >= ohw) return;
+  const int f = (int)blockIdx.y, clip = (int)blockIdx.z;
+  const long long i = ((long long)clip * a.F + f) * ohw + p;
+  const int oy = p / a.g.out_w, ox = p - oy * a.g.out_w;
+  const uint8_t* fr = buf + (FROM_ARRAY ? offs[clip] : a.offs[clip]) + f * a.frame_stride;
+  // the arithmetic below is nv12_clip_kernel's, expression for expression
+  const float sx = a.g.crop_x + ((float)ox + 0.5f) * (a.g.crop_w / (float)a.g.out_w) - 0.5f;
+  const float sy = a.g.crop_y + ((float)oy + 0.5f) * (a.g.crop_h / (float)a.g.out_h) - 0.5f;
+  const float yv = nv12_sample(fr + a.y_off, a.g.src_w, a.g.src_h, a.y_stride, 1, 0, sx, sy);
+  const float cx = (sx + 0.5f) * 0.5f - 0.5f, cy = (sy + 0.5f) * 0.5f - 0.5f;
+  const int cw = a.g.src_w / 2, ch = a.g.src_h / 2;
+  const float u = nv12_sample(fr + a.u_off, cw, ch, a.u_stride, a.c_step, 0, cx, cy) - 128.f;
+  const float v = nv12_sample(fr + a.v_off, cw, ch, a.v_stride, a.c_step, 0, cx, cy) - 128.f;
+  const float yy = 1.164f * (yv - 16.f);
+  float r = yy + 1.596f * v;
+  float g = yy - 0.392f * u - 0.813f * v;
+  float b = yy + 2.017f * u;
+  r = fminf(fmaxf(r, 0.f), 255.f) * a.g.scale[0] + a.g.shift[0];
+  g = fminf(fmaxf(g, 0.f), 255.f) * a.g.scale[1] + a.g.shift[1];
+  b = fminf(fmaxf(b, 0.f), 255.f) * a.g.scale[2] + a.g.shift[2];
+  if (a.g.bf16) {
     uint16_t* o = (uint16_t*)out + i * 8;
     *(uint4*)o = make_uint4(nv12_bf_bits(r) | (nv12_bf_bits(g) << 16), nv12_bf_bits(b), 0u, 0u);
   } else {
@@ -599,6 +657,60 @@ int rnb_nv12_to_clip(const void* nv12, void* out, long long frames, int src_w, i
   const long long npix = frames * out_w * out_h;
   hipLaunchKernelGGL(nv12_clip_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0,
                      stream, (const uint8_t*)nv12, out, npix, a);
+  return (int)hipGetLastError();
+}
+
+// buf: buf_len uploaded bytes; clip c's F frames start at offs[c] (host copy,
+// checked here) and are frame_stride bytes apart; plane_off / plane_stride:
+// byte offset within a frame and row stride of Y, U, V; c_step: bytes between
+// chroma samples (1 planar, 2 interleaved). out: [nclips][F][oh][ow][4] fp32 or
+// [..][8] bf16. Up to YUV420_MAX_CLIPS offsets travel in the kernel arguments;
+// more need offs_dev, the same table in device memory. -4: a frame or a span
+// would reach outside its frame stride / the buffer (nothing is launched).
+int rnb_yuv420_to_clip(const void* buf, long long buf_len, const long long* offs,
+                       const void* offs_dev, int nclips, int F, int src_w, int src_h,
+                       long long frame_stride, const long long* plane_off,
+                       const int* plane_stride, int c_step, void* out, int out_w, int out_h,
+                       const float* crop, const float* mean, const float* stdv, int bf16,
+                       hipStream_t stream) {
+  if (nclips <= 0) return 0;
+  if (F <= 0 || src_w < 2 || src_h < 2 || src_w % 2 || src_h % 2 || out_w <= 0 || out_h <= 0)
+    return -2;
+  if (((uintptr_t)out & 15u) != 0 || (c_step != 1 && c_step != 2)) return -2;
+  if (nclips > YUV420_MAX_CLIPS && !offs_dev) return -3;
+  // every byte nv12_sample can touch lies inside its frame (int indexing there)
+  if (frame_stride <= 0 || frame_stride > 0x7FFFFFFFLL) return -4;
+  const int cw = src_w / 2, ch = src_h / 2;
+  for (int p = 0; p < 3; ++p) {
+    if (plane_off[p] < 0 || plane_stride[p] <= 0) return -4;
+    const long long row = p == 0 ? src_w : (long long)(cw - 1) * c_step + 1;
+    const long long rows = p == 0 ? src_h : ch;
+    if (plane_off[p] + (rows - 1) * plane_stride[p] + row > frame_stride) return -4;
+  }
+  for (int c = 0; c < nclips; ++c)
+    if (offs[c] < 0 || offs[c] + (long long)F * frame_stride > buf_len) return -4;
+  const long long ohw = (long long)out_w * out_h;
+  if (ohw > 0x7FFFFF00LL || F > 65535 || nclips > 65535) return -2;    // grid limits
+  Yuv420ClipArgs a;
+  a.g.src_w = src_w; a.g.src_h = src_h; a.g.out_w = out_w; a.g.out_h = out_h;
+  a.g.crop_x = crop[0]; a.g.crop_y = crop[1]; a.g.crop_w = crop[2]; a.g.crop_h = crop[3];
+  for (int c = 0; c < 3; ++c) {
+    a.g.scale[c] = 1.0f / (255.0f * stdv[c]);
+    a.g.shift[c] = -mean[c] / stdv[c];
+  }
+  a.g.bf16 = bf16;
+  a.F = F; a.c_step = c_step; a.frame_stride = frame_stride;
+  a.y_off = plane_off[0]; a.u_off = plane_off[1]; a.v_off = plane_off[2];
+  a.y_stride = plane_stride[0]; a.u_stride = plane_stride[1]; a.v_stride = plane_stride[2];
+  const bool in_args = nclips <= YUV420_MAX_CLIPS;
+  for (int c = 0; c < YUV420_MAX_CLIPS; ++c) a.offs[c] = in_args && c < nclips ? offs[c] : 0;
+  const dim3 grid((unsigned)((ohw + 255) / 256), (unsigned)F, (unsigned)nclips);
+  if (in_args)
+    hipLaunchKernelGGL(yuv420_clip_kernel<false>, grid, dim3(256), 0, stream,
+                       (const uint8_t*)buf, (const long long*)nullptr, out, a);
+  else
+    hipLaunchKernelGGL(yuv420_clip_kernel<true>, grid, dim3(256), 0, stream,
+                       (const uint8_t*)buf, (const long long*)offs_dev, out, a);
   return (int)hipGetLastError();
 }
 

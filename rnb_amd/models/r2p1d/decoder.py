@@ -10,7 +10,10 @@ decoder's output goes through in NVVL: colour conversion and scaling to
 112x112 (``nv12_to_clip`` HIP kernel). ``synthetic-rgb`` generates 112x112 RGB
 frames directly (``clipgen`` + ``preprocess``). ``NpyDecoder`` is a real-I/O backend that
 reads pre-decoded ``uint8 [frames, H, W, 3]`` ``.npy`` files (memory-mapped,
-so only the sampled frames are read) and uploads them.
+so only the sampled frames are read) and uploads them. ``Y4mDecoder`` reads raw
+YUV4MPEG2 (``.y4m``) files at their source resolution: it uploads only the
+sampled frames' file spans and scales / colour-converts them on the GPU
+(``yuv420_to_clip`` HIP kernel, the planar-chroma sibling of ``nv12_to_clip``).
 
 Every decoder returns NDHWC clips normalised with the Kinetics mean/std:
 ``fp32 [n, 8, 112, 112, 4]`` (reference precision) or ``bf16 [n, 8, 112, 112, 8]``
@@ -18,13 +21,16 @@ Every decoder returns NDHWC clips normalised with the Kinetics mean/std:
 """
 from __future__ import annotations
 
+import mmap
 import os
+from collections import OrderedDict
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ...ops import video as vops
+from ...utils import y4m
 from ...video_path_provider import parse_synthetic_path
 
 
@@ -152,8 +158,199 @@ class NpyDecoder(Decoder):
         return self._decode_surface(t, out)
 
 
+class _UploadEntry:
+    """One request's staging: pinned host bytes, their device copy, and the
+    event recorded behind the kernel that reads the device copy."""
+
+    def __init__(self, nbytes: int, device: torch.device):
+        self.pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        self.host = self.pinned.numpy()
+        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.event = torch.cuda.Event()
+        self.in_flight = False
+
+    def acquire(self) -> None:
+        """The copies and the kernel of this entry's last request are done."""
+        if self.in_flight:
+            self.event.synchronize()
+            self.in_flight = False
+
+
+class Y4mDecoder(Decoder):
+    """Raw YUV4MPEG2 (``.y4m``) videos at their source resolution.
+
+    ``probe`` memory-maps the file and parses its header (``utils/y4m.py``):
+    8-bit 4:2:0 only, i.e. no ``C`` field or ``C420`` / ``C420jpeg`` /
+    ``C420mpeg2`` / ``C420paldv``. These differ in chroma siting; all are
+    sampled with the kernel's centred siting (chroma sample centres at 2x + 0.5
+    luma pixels, exact for ``C420jpeg``; the co-sited variants are read half a
+    luma pixel off horizontally, as NVVL's scaler does not distinguish them
+    either). Everything else raises ``ValueError`` naming file and field.
+
+    ``decode`` treats each clip's F consecutive frames as one contiguous span
+    of the file: it copies the span into a pinned staging buffer, checks the
+    ``FRAME`` marker of every frame, issues one asynchronous upload per clip
+    and then one ``yuv420_to_clip`` launch (scale, BT.601, normalise) straight
+    into ``out``. Staging and upload buffers form a ring of ``depth`` requests
+    owned by the decoder, sized on first use for ``max(n, 15)`` clips and
+    regrown for larger frames; an entry is reused once the event recorded
+    behind its kernel has completed (waited for if not), so a warm decoder
+    neither pins nor allocates. On a CPU device the spans go to the op's CPU
+    mirror.
+
+    ``crop``: ``"full"`` scales the whole frame to the output (what the
+    synthetic NV12 path does), ``"center"`` the centred square of the short
+    side."""
+
+    WARMUP_W, WARMUP_H = vops.SOURCE_W, vops.SOURCE_H
+    MAX_OPEN = 64            # memory maps kept open (least recently used first out)
+
+    def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
+                 width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full"):
+        if crop not in ("full", "center"):
+            raise ValueError("Y4mDecoder: crop must be 'full' or 'center', got %r" % (crop,))
+        if depth < 1:
+            raise ValueError("Y4mDecoder: ring depth must be >= 1, got %r" % (depth,))
+        self.device = device
+        self.F, self.H, self.W = clip_length, height, width
+        self.dtype = dtype
+        self.depth = int(depth)
+        self.crop = crop
+        self._ids = {}
+        self._videos = {}          # video id -> (path, Y4mHeader)
+        self._maps = OrderedDict()  # video id -> (mmap, uint8 view), LRU
+        self._ring: List[_UploadEntry] = []
+        self._ring_bytes = 0
+        self._next = 0
+
+    # -- files ------------------------------------------------------------
+    def _map(self, vid: int, path: str):
+        got = self._maps.get(vid)
+        if got is not None:
+            self._maps.move_to_end(vid)
+            return got
+        with open(path, "rb") as fp:
+            mm = mmap.mmap(fp.fileno(), 0, access=mmap.ACCESS_READ)
+        got = (mm, np.frombuffer(mm, dtype=np.uint8))
+        self._maps[vid] = got
+        while len(self._maps) > self.MAX_OPEN:
+            self._maps.popitem(last=False)       # unmapped once its views are gone
+        return got
+
+    def probe(self, path):
+        vid = self._ids.get(path)
+        if vid is not None:
+            return vid, self._videos[vid][1].num_frames
+        if os.path.getsize(path) == 0:
+            raise ValueError("%s: empty file (field 'magic')" % path)
+        vid = len(self._ids)
+        mm, _ = self._map(vid, path)
+        try:
+            hdr = y4m.read_header(path, data=mm)
+        except ValueError:
+            del self._maps[vid]
+            raise
+        self._ids[path] = vid
+        self._videos[vid] = (path, hdr)
+        return vid, hdr.num_frames
+
+    def _crop_box(self, hdr):
+        if self.crop == "full":
+            return None
+        side = min(hdr.width, hdr.height)
+        return ((hdr.width - side) / 2.0, (hdr.height - side) / 2.0, float(side), float(side))
+
+    # -- ring ---------------------------------------------------------------
+    def _entry(self, nbytes: int) -> _UploadEntry:
+        if nbytes > self._ring_bytes or not self._ring:
+            for e in self._ring:
+                e.acquire()                      # nothing in flight reads the old buffers
+            self._ring_bytes = max(nbytes, self._ring_bytes)
+            self._ring = [_UploadEntry(self._ring_bytes, self.device)
+                          for _ in range(self.depth)]
+            self._next = 0
+        e = self._ring[self._next]
+        self._next = (self._next + 1) % self.depth
+        e.acquire()
+        return e
+
+    def _out(self, n: int, out):
+        if out is not None:
+            return out
+        C = vops.IN_CHANNELS_P_F32 if self.dtype == torch.float32 else vops.IN_CHANNELS_P
+        return torch.empty((n, self.F, self.H, self.W, C), dtype=self.dtype, device=self.device)
+
+    def warmup(self, n: int) -> None:
+        """Run the clip kernel on a zeroed upload buffer (no file needed)."""
+        if self.device.type != "cuda":
+            return
+        W, H = self.WARMUP_W, self.WARMUP_H
+        stride = len(y4m.FRAME_MARKER) + vops.nv12_frame_bytes(W, H)
+        for i in range(n):
+            e = self._entry(15 * self.F * stride)
+            e.dev[:self.F * stride].zero_()
+            vops.yuv420_to_clip(e.dev, [0], self.F, W, H, stride,
+                                vops.i420_planes(W, H, len(y4m.FRAME_MARKER)), self.W,
+                                self.H, dtype=self.dtype, out=self._out(1, None))
+            e.event.record(torch.cuda.current_stream(self.device))
+            e.in_flight = True
+
+    # -- decode ---------------------------------------------------------------
+    def decode(self, vid, starts, out=None):
+        n = len(starts)
+        if n == 0:
+            return self.empty()
+        got = self._videos.get(vid)
+        if got is None:
+            raise KeyError("video id %r was not probed" % (vid,))
+        path, hdr = got
+        _, data = self._map(vid, path)
+        span = self.F * hdr.frame_stride
+        marker = np.frombuffer(y4m.FRAME_MARKER, dtype=np.uint8)
+        for s in starts:
+            if s < 0 or s + self.F > hdr.num_frames:
+                raise ValueError("%s: clip at frame %d (+%d) is outside the %d frames"
+                                 % (path, s, self.F, hdr.num_frames))
+        planes = vops.i420_planes(hdr.width, hdr.height, len(y4m.FRAME_MARKER))
+        offsets = [i * span for i in range(n)]
+        cuda = self.device.type == "cuda"
+        if cuda:
+            entry = self._entry(max(n, 15) * span)
+            host, buf = entry.host, entry.dev
+        else:
+            host = np.empty(n * span, dtype=np.uint8)
+            buf = torch.from_numpy(host)
+        try:
+            for i, s in enumerate(starts):
+                a = hdr.frame_offset(s)
+                dst = host[i * span:(i + 1) * span]
+                np.copyto(dst, data[a:a + span])
+                heads = dst.reshape(self.F, hdr.frame_stride)[:, :len(marker)]
+                if not (heads == marker).all():
+                    bad = int(np.nonzero((heads != marker).any(axis=1))[0][0])
+                    raise ValueError("%s: frame %d does not start with a bare FRAME marker "
+                                     "(field 'FRAME': %r); frame parameters are not supported"
+                                     % (path, s + bad, bytes(heads[bad])))
+                if cuda:     # this clip uploads while the next one is staged
+                    buf[i * span:(i + 1) * span].copy_(
+                        entry.pinned[i * span:(i + 1) * span], non_blocking=True)
+            out = self._out(n, out)
+            vops.yuv420_to_clip(buf[:n * span], offsets, self.F, hdr.width, hdr.height,
+                                hdr.frame_stride, planes, self.W, self.H,
+                                crop=self._crop_box(hdr), dtype=self.dtype, out=out)
+        finally:
+            if cuda:     # also behind the uploads of a request that raised
+                entry.event.record(torch.cuda.current_stream(self.device))
+                entry.in_flight = True
+        return out
+
+
 def make_decoder(backend: str, device: torch.device, clip_length=8, height=112, width=112,
-                 dtype=torch.bfloat16) -> Decoder:
+                 dtype=torch.bfloat16, decoder_args: Optional[dict] = None) -> Decoder:
+    """``decoder_args``: backend-specific constructor arguments (``y4m``:
+    ``depth``, ``crop``); the other backends take none and ignore it."""
+    if backend == "y4m":
+        return Y4mDecoder(device, clip_length, height, width, dtype, **(decoder_args or {}))
     if backend in ("synthetic", "synthetic-nv12"):
         return SyntheticDecoder(device, clip_length, height, width, dtype, source="nv12")
     if backend == "synthetic-rgb":
@@ -162,6 +359,6 @@ def make_decoder(backend: str, device: torch.device, clip_length=8, height=112, 
         return NpyDecoder(device, clip_length, height, width, dtype)
     if backend in ("rocdecode", "nvvl"):
         raise RuntimeError("decoder backend %r is not available on this system "
-                           "(no rocDecode/VCN library installed); use 'synthetic' "
-                           "or 'npy'" % backend)
+                           "(no rocDecode/VCN library installed); use 'synthetic', "
+                           "'y4m' or 'npy'" % backend)
     raise ValueError("unknown decoder backend %r" % backend)

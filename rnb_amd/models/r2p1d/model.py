@@ -480,13 +480,14 @@ class R2P1DLoader(RunnerModel):
 
     def __init__(self, device, num_clips_population=(1, 15), num_clips_weights=(10, 1),
                  decoder="synthetic", seed=None, max_clips=DEFAULT_MAX_CLIPS,
-                 warmup=3, dtype=None, **unused):
+                 warmup=3, dtype=None, decoder_args=None, **unused):
         super().__init__(device)
         self.sampler = R2P1DSampler(clip_length=CLIP_SHAPE[0],
                                     num_clips_population=num_clips_population,
                                     num_clips_weights=num_clips_weights, seed=seed)
         self.dtype = _dtype(dtype)
-        self.decoder = make_decoder(decoder, device, *CLIP_SHAPE, dtype=self.dtype)
+        self.decoder = make_decoder(decoder, device, *CLIP_SHAPE, dtype=self.dtype,
+                                    decoder_args=decoder_args)
         self.max_clips = max_clips
         self.decoder.warmup(warmup)
         if device.type == "cuda":
@@ -560,11 +561,11 @@ class R2P1DSingleStep(RunnerModel):
                  block_type=None, num_clips_population=(1, 15), num_clips_weights=(10, 1),
                  decoder="synthetic", seed=None, model_seed=0, backend="auto",
                  bn_mode=None, ckpt_path=None, max_clips=DEFAULT_MAX_CLIPS, warmup=3,
-                 use_graphs=True, autotune=True, dtype=None, **unused):
+                 use_graphs=True, autotune=True, dtype=None, decoder_args=None, **unused):
         super().__init__(device)
         self.loader = R2P1DLoader(device, num_clips_population, num_clips_weights,
                                   decoder=decoder, seed=seed, max_clips=max_clips,
-                                  warmup=warmup, dtype=dtype)
+                                  warmup=warmup, dtype=dtype, decoder_args=decoder_args)
         self.runner = R2P1DRunner(device, 1, 5, num_classes,
                                   layer_sizes=layer_sizes, depth=depth, backend=backend,
                                   bn_mode=bn_mode, seed=model_seed, ckpt_path=ckpt_path,

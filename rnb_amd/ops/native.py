@@ -206,6 +206,18 @@ class Kernels:
                                          ctypes.POINTER(ctypes.c_float),
                                          ctypes.POINTER(ctypes.c_float), ctypes.c_int,
                                          ctypes.c_void_p]
+        lib.rnb_yuv420_to_clip.argtypes = [ctypes.c_void_p, ctypes.c_longlong,
+                                           ctypes.POINTER(ctypes.c_longlong), ctypes.c_void_p,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_longlong,
+                                           ctypes.POINTER(ctypes.c_longlong),
+                                           ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_float),
+                                           ctypes.POINTER(ctypes.c_float),
+                                           ctypes.POINTER(ctypes.c_float), ctypes.c_int,
+                                           ctypes.c_void_p]
+        lib.rnb_yuv420_to_clip.restype = ctypes.c_int
         lib.rnb_preprocess.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
                                        ctypes.POINTER(ctypes.c_float),
                                        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
@@ -783,6 +795,24 @@ class Kernels:
         s = (ctypes.c_float * 3)(*std)
         _check(self.lib.rnb_nv12_to_clip(in_ptr, out_ptr, frames, src_w, src_h, out_w, out_h,
                                          c, m, s, 1 if bf16 else 0, stream), "nv12_to_clip")
+
+    def yuv420_to_clip(self, buf_ptr, buf_len, offsets, offsets_dev_ptr, F, src_w, src_h,
+                       frame_stride, plane_offsets, plane_strides, c_step, out_ptr, out_w,
+                       out_h, crop, mean, std, bf16, stream):
+        """``offsets``: the per-clip byte offsets on the host (checked against
+        ``buf_len`` by the launcher); ``offsets_dev_ptr``: the same table in
+        device memory, needed for more than 32 clips (else None)."""
+        n = len(offsets)
+        offs = (ctypes.c_longlong * max(1, n))(*offsets)
+        po = (ctypes.c_longlong * 3)(*plane_offsets)
+        ps = (ctypes.c_int * 3)(*plane_strides)
+        c = (ctypes.c_float * 4)(*crop)
+        m = (ctypes.c_float * 3)(*mean)
+        s = (ctypes.c_float * 3)(*std)
+        _check(self.lib.rnb_yuv420_to_clip(buf_ptr, buf_len, offs, offsets_dev_ptr, n, F,
+                                           src_w, src_h, frame_stride, po, ps, c_step,
+                                           out_ptr, out_w, out_h, c, m, s, 1 if bf16 else 0,
+                                           stream), "yuv420_to_clip")
 
     def preprocess(self, in_ptr, out_ptr, npix, mean, std, stream):
         m = (ctypes.c_float * 3)(*mean)

@@ -6,7 +6,7 @@ mirror (the mirrors are what the numerics tests compare the kernels with).
 from __future__ import annotations
 
 import math
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -175,25 +175,115 @@ def nv12_to_clip(nv12: torch.Tensor, src_w: int, src_h: int, out_w: int = 112,
         return out
     y_plane = nv12[:, :src_h].float()
     uv = nv12[:, src_h:].float().view(frames, src_h // 2, src_w // 2, 2)
+    return _planes_to_clip(y_plane, uv[..., 0], uv[..., 1], shape, crop, dtype, mean, std, out)
+
+
+def _planes_to_clip(y_plane, u_plane, v_plane, shape, crop, dtype, mean, std, out):
+    """CPU mirror shared by ``nv12_to_clip`` and ``yuv420_to_clip``: float Y
+    [frames, h, w] and U, V [frames, h/2, w/2] planes -> ``shape`` =
+    [..., out_h, out_w, C] normalised frames."""
+    out_h, out_w = shape[-3], shape[-2]
     ox = torch.arange(out_w, dtype=torch.float32)
     oy = torch.arange(out_h, dtype=torch.float32)
     sx = crop[0] + (ox + 0.5) * (crop[2] / out_w) - 0.5
     sy = crop[1] + (oy + 0.5) * (crop[3] / out_h) - 0.5
     yv = _bilinear_torch(y_plane, sx, sy)
     cx, cy = (sx + 0.5) * 0.5 - 0.5, (sy + 0.5) * 0.5 - 0.5
-    u = _bilinear_torch(uv[..., 0], cx, cy) - 128.0
-    v = _bilinear_torch(uv[..., 1], cx, cy) - 128.0
+    u = _bilinear_torch(u_plane, cx, cy) - 128.0
+    v = _bilinear_torch(v_plane, cx, cy) - 128.0
     yy = 1.164 * (yv - 16.0)
     rgb = torch.stack([yy + 1.596 * v, yy - 0.392 * u - 0.813 * v, yy + 2.017 * u], dim=-1)
     scale, shift = _norm32(mean, std)
     rgb = rgb.clamp(0.0, 255.0) * scale + shift
     res = torch.zeros(shape, dtype=torch.float32)
-    res[..., :3] = rgb
+    res.view(-1, out_h, out_w, shape[-1])[..., :3] = rgb
     res = res.to(dtype)
     if out is not None:
         out.copy_(res.view(out.shape))
         return out
     return res
+
+
+class YuvPlanes(NamedTuple):
+    """Where a frame's 4:2:0 samples lie, in bytes from the frame's start:
+    offsets and row strides of the Y, U and V planes, and the distance between
+    chroma samples (1: planar, 2: interleaved UV with ``v = u + 1``)."""
+    y: int
+    u: int
+    v: int
+    y_stride: int
+    u_stride: int
+    v_stride: int
+    c_step: int = 1
+
+
+def i420_planes(W: int, H: int, header: int = 0) -> YuvPlanes:
+    """Planar I420 (Y, then U, then V) behind ``header`` bytes, e.g. the 6-byte
+    ``FRAME\\n`` marker of a YUV4MPEG2 frame."""
+    return YuvPlanes(header, header + W * H, header + W * H + (W // 2) * (H // 2),
+                     W, W // 2, W // 2, 1)
+
+
+def nv12_planes(W: int, H: int, header: int = 0) -> YuvPlanes:
+    """NV12 (Y, then interleaved UV rows of W bytes) behind ``header`` bytes."""
+    return YuvPlanes(header, header + W * H, header + W * H + 1, W, W, W, 2)
+
+
+def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: int,
+                   frame_stride: int, planes: YuvPlanes, out_w: int = 112, out_h: int = 112,
+                   crop=None, dtype=torch.float32, mean=KINETICS_MEAN, std=KINETICS_STD,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """4:2:0 frames inside a byte buffer -> normalised NDHWC clips
+    [n, F, out_h, out_w, C] (fp32 C=4 / bf16 C=8), with ``nv12_to_clip``'s
+    arithmetic. ``buf`` is a flat uint8 tensor (uploaded file spans); clip ``c``
+    is the ``F`` frames that start at byte ``clip_offsets[c]`` and lie
+    ``frame_stride`` bytes apart; ``planes`` (``YuvPlanes``) locates the samples
+    within a frame. No alignment of any offset is assumed. One kernel launch
+    for all clips; every span is checked against ``buf`` before it."""
+    offsets = [int(o) for o in (clip_offsets.tolist() if isinstance(clip_offsets, torch.Tensor)
+                                else clip_offsets)]
+    n = len(offsets)
+    planes = YuvPlanes(*planes)
+    crop = tuple(float(c) for c in (crop or (0, 0, src_w, src_h)))
+    C = IN_CHANNELS_P_F32 if dtype == torch.float32 else IN_CHANNELS_P
+    shape = (n, F, out_h, out_w, C)
+    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
+        raise ValueError("yuv420_to_clip: buf must be a flat contiguous uint8 tensor")
+    if out is not None and (out.dtype != dtype or not out.is_contiguous()
+                            or out.numel() != math.prod(shape)):
+        raise ValueError("yuv420_to_clip: out must be contiguous %s %s" % (dtype, shape))
+    if buf.is_cuda:
+        from .native import kernels
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=buf.device)
+        table = None
+        if n > 32:          # past the kernel-argument table: offsets in device memory
+            table = clip_offsets if isinstance(clip_offsets, torch.Tensor) else \
+                torch.tensor(offsets, dtype=torch.int64)
+            table = table.to(device=buf.device, dtype=torch.int64).contiguous()
+        kernels().yuv420_to_clip(buf.data_ptr(), buf.numel(), offsets,
+                                 None if table is None else table.data_ptr(), F, src_w,
+                                 src_h, frame_stride, planes[:3], planes[3:6], planes.c_step,
+                                 out.data_ptr(), out_w, out_h, crop, mean, std,
+                                 dtype == torch.bfloat16,
+                                 torch.cuda.current_stream(buf.device).cuda_stream)
+        return out
+    if src_w % 2 or src_h % 2 or planes.c_step not in (1, 2):
+        raise ValueError("yuv420_to_clip: even frame sizes and a chroma step of 1 or 2")
+    if any(o < 0 or o + F * frame_stride > buf.numel() for o in offsets):
+        raise ValueError("yuv420_to_clip: a clip span lies outside the buffer")
+    cw, ch = src_w // 2, src_h // 2
+    base = (torch.tensor(offsets, dtype=torch.int64).view(n, 1)
+            + torch.arange(F, dtype=torch.int64).view(1, F) * frame_stride).view(-1, 1, 1)
+
+    def gather(off, stride, rows, cols, step):
+        idx = base + off + torch.arange(rows).view(1, rows, 1) * stride \
+            + torch.arange(cols).view(1, 1, cols) * step
+        return buf[idx].float()
+    return _planes_to_clip(gather(planes.y, planes.y_stride, src_h, src_w, 1),
+                           gather(planes.u, planes.u_stride, ch, cw, planes.c_step),
+                           gather(planes.v, planes.v_stride, ch, cw, planes.c_step),
+                           shape, crop, dtype, mean, std, out)
 
 
 def preprocess(frames_u8: torch.Tensor, mean=KINETICS_MEAN, std=KINETICS_STD,

@@ -1,0 +1,141 @@
+"""Time the y4m decode path per 15-clip request at 340x256 (GPU required).
+
+  * kernel: ``yuv420_clip_kernel`` on I420 frames behind FRAME markers next to
+    ``nv12_clip_kernel`` on the same pixels as NV12, alternating, device events
+    around ``--reps`` back-to-back launches per round;
+  * host: ``Y4mDecoder.decode`` next to ``NpyDecoder.decode`` on files written
+    to a temporary directory and read once before (warm page cache): time of
+    the call itself, and of the call plus a device synchronise.
+
+    python scripts/y4m_decode_bench.py --out profiles/y4m_decode.txt
+"""
+import argparse
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from rnb_amd.models.r2p1d.decoder import NpyDecoder, Y4mDecoder  # noqa: E402
+from rnb_amd.ops import video as vops  # noqa: E402
+from rnb_amd.utils import y4m  # noqa: E402
+
+W, H, F, CLIPS = vops.SOURCE_W, vops.SOURCE_H, 8, 15
+
+
+def event_ms(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def kernels(dev, dtype, reps, rounds, lines):
+    rng = np.random.default_rng(0)
+    stride = 6 + vops.nv12_frame_bytes(W, H)
+    i420 = torch.from_numpy(rng.integers(0, 256, (CLIPS * F, stride), dtype=np.uint8))
+    y = i420[:, 6:6 + W * H].reshape(-1, H, W)
+    u = i420[:, 6 + W * H:6 + W * H * 5 // 4].reshape(-1, H // 2, W // 2)
+    v = i420[:, 6 + W * H * 5 // 4:].reshape(-1, H // 2, W // 2)
+    nv = torch.cat([y, torch.stack([u, v], dim=-1).reshape(-1, H // 2, W)], dim=1).contiguous()
+    buf, nvd = i420.reshape(-1).to(dev), nv.to(dev)
+    offs = [c * F * stride for c in range(CLIPS)]
+    C = 4 if dtype == torch.float32 else 8
+    out = torch.empty((CLIPS, F, 112, 112, C), dtype=dtype, device=dev)
+    planes = vops.i420_planes(W, H, 6)
+
+    def new():
+        vops.yuv420_to_clip(buf, offs, F, W, H, stride, planes, dtype=dtype, out=out)
+
+    def old():
+        vops.nv12_to_clip(nvd, W, H, dtype=dtype, out=out)
+    new()
+    a = out.clone()
+    old()
+    diff = (a.float() - out.float()).abs().max().item()
+    for fn in (new, old):
+        event_ms(fn, reps)                                # warm
+    t_new, t_old = [], []
+    for _ in range(rounds):
+        t_new.append(event_ms(new, reps))
+        t_old.append(event_ms(old, reps))
+    src = CLIPS * F * stride
+    dst = out.numel() * out.element_size()
+    for name, t in (("yuv420_clip_kernel", t_new), ("nv12_clip_kernel  ", t_old)):
+        med = statistics.median(t)
+        lines.append("%s %s: median %.2f us/launch (min %.2f, max %.2f over %d rounds of %d); "
+                     "%.0f GB/s of %d source + %d output bytes"
+                     % (name, str(dtype).split(".")[1], med * 1e3, min(t) * 1e3, max(t) * 1e3,
+                        rounds, reps, (src + dst) / med / 1e6, src, dst))
+    lines.append("max |yuv420 - nv12| on the same pixels: %g" % diff)
+
+
+def host(dev, dtype, reqs, lines):
+    rng = np.random.default_rng(1)
+    frames = 300
+    starts = [20 * c for c in range(CLIPS)]
+    with tempfile.TemporaryDirectory() as d:
+        py, pn = os.path.join(d, "v.y4m"), os.path.join(d, "v.npy")
+        y4m.write_y4m(py, [(rng.integers(0, 256, (H, W), dtype=np.uint8),
+                            rng.integers(0, 256, (H // 2, W // 2), dtype=np.uint8),
+                            rng.integers(0, 256, (H // 2, W // 2), dtype=np.uint8))
+                           for _ in range(frames)])
+        np.save(pn, rng.integers(0, 256, (frames, 112, 112, 3), dtype=np.uint8))
+        for p in (py, pn):
+            with open(p, "rb") as fp:                      # warm the page cache
+                while fp.read(1 << 24):
+                    pass
+        C = 4 if dtype == torch.float32 else 8
+        out = torch.empty((CLIPS, F, 112, 112, C), dtype=dtype, device=dev)
+        for name, dec, path in (("Y4mDecoder.decode (340x256 y4m)", Y4mDecoder(dev, dtype=dtype), py),
+                                ("NpyDecoder.decode (112x112 npy)", NpyDecoder(dev, dtype=dtype), pn)):
+            vid, _ = dec.probe(path)
+            for _ in range(5):
+                dec.decode(vid, starts, out=out)
+            torch.cuda.synchronize()
+            call, total = [], []
+            for _ in range(reqs):
+                t0 = time.perf_counter()
+                dec.decode(vid, starts, out=out)
+                t1 = time.perf_counter()
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                call.append((t1 - t0) * 1e3)
+                total.append((t2 - t0) * 1e3)
+            lines.append("%s %s: host call median %.3f ms (min %.3f, max %.3f), call + sync "
+                         "median %.3f ms, %d requests of %d clips"
+                         % (name, str(dtype).split(".")[1], statistics.median(call), min(call),
+                            max(call), statistics.median(total), reqs, CLIPS))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--requests", type=int, default=40)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("y4m_decode_bench: needs a GPU")
+    dev = torch.device("cuda:0")
+    lines = ["y4m decode path, per 15-clip request at %dx%d -> 112x112 (%s)"
+             % (W, H, torch.cuda.get_device_name(0))]
+    for dtype in (torch.float32, torch.bfloat16):
+        kernels(dev, dtype, args.reps, args.rounds, lines)
+    host(dev, torch.float32, args.requests, lines)
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if args.out:
+        with open(args.out, "w") as fp:
+            fp.write(text)
+
+
+if __name__ == "__main__":
+    main()
