@@ -1,0 +1,156 @@
+// GPU half of the MJPEG decode backend: dequantise + 8x8 inverse DCT of the
+// frame records the host entropy decoder (jpeg_entropy.cpp) produced.
+//
+//  * rnb_jpeg_idct   nframes records (uint16 qt[3][64], then int16 quantised
+//                    coefficients, 64 per block in natural order: Y blocks
+//                    row-major over the padded 2*mh x 2*mw grid, then Cb, then
+//                    Cr; see jpeg_entropy.cpp) -> 8-bit planar I420 frames at
+//                    the padded size: Y [16*mh][16*mw], Cb and Cr
+//                    [8*mh][8*mw], 384*mw*mh bytes per frame. Per sample:
+//                    coefficient x table entry, separable 8-point IDCT in
+//                    fp32, + 128, round to nearest, clamp to [0, 255].
+//
+// Every address is a function of (frame, block, line) and the geometry the
+// launcher validated, never of a coefficient: corrupt coefficients give wrong
+// pixels, not wrong addresses. Every byte of the surface's nframes frames is
+// written, the padding rows and columns included.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// kJpegBasis[x][u] = c(u) / 2 * cos((2x + 1) u pi / 16), c(0) = 1/sqrt(2)
+__device__ __attribute__((aligned(16))) const float kJpegBasis[8][8] = {
+    {0.35355339f, 0.49039264f, 0.46193977f, 0.41573481f, 0.35355339f, 0.27778512f, 0.19134172f, 0.09754516f},
+    {0.35355339f, 0.41573481f, 0.19134172f, -0.09754516f, -0.35355339f, -0.49039264f, -0.46193977f, -0.27778512f},
+    {0.35355339f, 0.27778512f, -0.19134172f, -0.49039264f, -0.35355339f, 0.09754516f, 0.46193977f, 0.41573481f},
+    {0.35355339f, 0.09754516f, -0.46193977f, -0.27778512f, 0.35355339f, 0.41573481f, -0.19134172f, -0.49039264f},
+    {0.35355339f, -0.09754516f, -0.46193977f, 0.27778512f, 0.35355339f, -0.41573481f, -0.19134172f, 0.49039264f},
+    {0.35355339f, -0.27778512f, -0.19134172f, 0.49039264f, -0.35355339f, -0.09754516f, 0.46193977f, -0.41573481f},
+    {0.35355339f, -0.41573481f, 0.19134172f, 0.09754516f, -0.35355339f, 0.49039264f, -0.46193977f, 0.27778512f},
+    {0.35355339f, -0.49039264f, 0.46193977f, -0.41573481f, 0.35355339f, -0.27778512f, 0.19134172f, -0.09754516f},
+};
+
+#define JPEG_BLOCKS_PER_WG 32      // 8 threads per 8x8 block, 256 threads
+// LDS image of one block's half-transformed values: 8 rows of 8 floats, rows
+// 12 floats apart and blocks 100 floats apart, so that the 16-byte writes of a
+// block's 8 lanes and the (broadcast) 16-byte reads of a wave's 8 blocks fall
+// on distinct 4-bank slots
+#define JPEG_ROW_STRIDE 12
+#define JPEG_BLK_STRIDE 100
+
+struct JpegIdctArgs {
+  long long record_bytes;
+  long long total_blocks;          // nframes * 6 * mw * mh
+  int mw, mh;
+};
+
+static __device__ __forceinline__ uint32_t jpeg_sample(float s) {
+  // + 128, round to nearest (ties to even), clamp
+  return (uint32_t)min(max(__float2int_rn(s + 128.f), 0), 255);
+}
+
+// One thread per 8-sample line, 8 threads per block. Thread j first holds
+// coefficient row j (one aligned 16-byte load, plus the 16 bytes of its
+// component's table row), dequantises it and transforms it along the row in
+// registers; the 8x8 intermediate goes through LDS; thread x then transforms
+// along the columns for output row x and ends with 8 adjacent samples, written
+// with one 8-byte store. Blocks that are neighbours in x are neighbours in the
+// record, so a wave's stores form 64-byte runs per row.
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const uint8_t* __restrict__ rec,
+                                                        uint8_t* __restrict__ surf,
+                                                        JpegIdctArgs a) {
+  __shared__ __attribute__((aligned(16))) float lds[JPEG_BLOCKS_PER_WG * JPEG_BLK_STRIDE];
+  const int t = (int)threadIdx.x;
+  const int line = t & 7, lb = t >> 3;
+  const long long gb = (long long)blockIdx.x * JPEG_BLOCKS_PER_WG + lb;
+  const bool live = gb < a.total_blocks;
+  const int n = a.mw * a.mh;                     // MCUs per frame
+  const int per_frame = 6 * n;
+  const long long frame = live ? gb / per_frame : 0;
+  const int b = live ? (int)(gb - frame * per_frame) : 0;
+  const int comp = b < 4 * n ? 0 : (b < 5 * n ? 1 : 2);
+  float* tile = lds + lb * JPEG_BLK_STRIDE;
+  if (live) {
+    const uint8_t* r = rec + frame * a.record_bytes;
+    const uint4 cw = *(const uint4*)(r + 384 + (long long)b * 128 + line * 16);
+    const uint4 qw = *(const uint4*)(r + comp * 128 + line * 16);
+    const uint32_t cs[4] = {cw.x, cw.y, cw.z, cw.w}, qs[4] = {qw.x, qw.y, qw.z, qw.w};
+    float f[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {                // |coef * q| < 2^24: exact in fp32
+      f[2 * i] = (float)(int)(int16_t)(cs[i] & 0xFFFFu) * (float)(qs[i] & 0xFFFFu);
+      f[2 * i + 1] = (float)(int)(int16_t)(cs[i] >> 16) * (float)(qs[i] >> 16);
+    }
+    float h[8];
+#pragma unroll
+    for (int y = 0; y < 8; ++y) {
+      float s = 0.f;
+#pragma unroll
+      for (int v = 0; v < 8; ++v) s += f[v] * kJpegBasis[y][v];
+      h[y] = s;
+    }
+    float4* row = (float4*)(tile + line * JPEG_ROW_STRIDE);
+    row[0] = make_float4(h[0], h[1], h[2], h[3]);
+    row[1] = make_float4(h[4], h[5], h[6], h[7]);
+  }
+  __syncthreads();
+  if (!live) return;
+  const float4 b0 = *(const float4*)&kJpegBasis[line][0];
+  const float4 b1 = *(const float4*)&kJpegBasis[line][4];
+  const float bu[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const float4 lo = *(const float4*)(tile + u * JPEG_ROW_STRIDE);
+    const float4 hi = *(const float4*)(tile + u * JPEG_ROW_STRIDE + 4);
+    s[0] += bu[u] * lo.x; s[1] += bu[u] * lo.y; s[2] += bu[u] * lo.z; s[3] += bu[u] * lo.w;
+    s[4] += bu[u] * hi.x; s[5] += bu[u] * hi.y; s[6] += bu[u] * hi.z; s[7] += bu[u] * hi.w;
+  }
+  const uint32_t w0 = jpeg_sample(s[0]) | (jpeg_sample(s[1]) << 8) | (jpeg_sample(s[2]) << 16) |
+                      (jpeg_sample(s[3]) << 24);
+  const uint32_t w1 = jpeg_sample(s[4]) | (jpeg_sample(s[5]) << 8) | (jpeg_sample(s[6]) << 16) |
+                      (jpeg_sample(s[7]) << 24);
+  // block -> plane position (all from the geometry)
+  int pb = b, cols = 2 * a.mw;
+  long long plane = 0;
+  if (comp) {
+    pb = b - (3 + comp) * n;
+    cols = a.mw;
+    plane = (long long)(192 + 64 * comp) * n;    // 256 n (Cb), 320 n (Cr)
+  }
+  const int by = pb / cols, bx = pb - by * cols;
+  uint8_t* dst = surf + frame * (384LL * n) + plane + ((long long)by * 8 + line) * (8 * cols) +
+                 bx * 8;
+  *(uint2*)dst = make_uint2(w0, w1);
+}
+
+extern "C" {
+
+// rec: nframes records record_bytes apart (rec_len bytes in all); surf:
+// surf_len bytes, receives nframes frames of 384*mw*mh bytes. -2: bad shape or
+// alignment; -4: a record or a frame would reach outside its buffer (nothing
+// is launched).
+int rnb_jpeg_idct(const void* rec, long long rec_len, long long record_bytes, int nframes,
+                  int mw, int mh, void* surf, long long surf_len, hipStream_t stream) {
+  if (nframes == 0) return 0;
+  if (nframes < 0 || mw < 1 || mh < 1 || mw > 4096 || mh > 4096) return -2;
+  const long long n = (long long)mw * mh;
+  if (((uintptr_t)rec & 15u) != 0 || ((uintptr_t)surf & 7u) != 0 || record_bytes % 16 != 0)
+    return -2;
+  if (record_bytes < 384 + 768 * n) return -4;
+  if (rec_len < 0 || surf_len < 0 || record_bytes > rec_len / nframes ||
+      384 * n > surf_len / nframes)
+    return -4;
+  const long long total = 6 * n * nframes;
+  const long long groups = (total + JPEG_BLOCKS_PER_WG - 1) / JPEG_BLOCKS_PER_WG;
+  if (groups > 0x7FFFFFFFLL) return -2;
+  JpegIdctArgs a;
+  a.record_bytes = record_bytes;
+  a.total_blocks = total;
+  a.mw = mw;
+  a.mh = mh;
+  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)groups), dim3(256), 0, stream,
+                     (const uint8_t*)rec, (uint8_t*)surf, a);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -253,7 +253,9 @@ struct Yuv420ClipArgs {
   long long offs[YUV420_MAX_CLIPS];        // per-clip base (FROM_ARRAY: unused)
 };
 
-template <bool FROM_ARRAY>
+// JFIF: full-range JFIF YCbCr (what JPEG frames hold) instead of the video-range
+// BT.601 matrix; the chroma planes of an odd-sized frame then round up.
+template <bool FROM_ARRAY, bool JFIF>
 __global__ __launch_bounds__(256) void yuv420_clip_kernel(const uint8_t* __restrict__ buf,
                                                           const long long* __restrict__ offs,
                                                           void* __restrict__ out,
@@ -273,13 +275,14 @@ __global__ __launch_bounds__(256) void yuv420_clip_kernel(const uint8_t* __restr
   const float sy = a.g.crop_y + ((float)oy + 0.5f) * (a.g.crop_h / (float)a.g.out_h) - 0.5f;
   const float yv = nv12_sample(fr + a.y_off, a.g.src_w, a.g.src_h, a.y_stride, 1, 0, sx, sy);
   const float cx = (sx + 0.5f) * 0.5f - 0.5f, cy = (sy + 0.5f) * 0.5f - 0.5f;
-  const int cw = a.g.src_w / 2, ch = a.g.src_h / 2;
+  const int cw = JFIF ? (a.g.src_w + 1) / 2 : a.g.src_w / 2;
+  const int ch = JFIF ? (a.g.src_h + 1) / 2 : a.g.src_h / 2;
   const float u = nv12_sample(fr + a.u_off, cw, ch, a.u_stride, a.c_step, 0, cx, cy) - 128.f;
   const float v = nv12_sample(fr + a.v_off, cw, ch, a.v_stride, a.c_step, 0, cx, cy) - 128.f;
-  const float yy = 1.164f * (yv - 16.f);
-  float r = yy + 1.596f * v;
-  float g = yy - 0.392f * u - 0.813f * v;
-  float b = yy + 2.017f * u;
+  const float yy = JFIF ? yv : 1.164f * (yv - 16.f);
+  float r = yy + (JFIF ? 1.402f : 1.596f) * v;
+  float g = yy - (JFIF ? 0.344136f : 0.392f) * u - (JFIF ? 0.714136f : 0.813f) * v;
+  float b = yy + (JFIF ? 1.772f : 2.017f) * u;
   r = fminf(fmaxf(r, 0.f), 255.f) * a.g.scale[0] + a.g.shift[0];
   g = fminf(fmaxf(g, 0.f), 255.f) * a.g.scale[1] + a.g.shift[1];
   b = fminf(fmaxf(b, 0.f), 255.f) * a.g.scale[2] + a.g.shift[2];
@@ -667,20 +670,23 @@ int rnb_nv12_to_clip(const void* nv12, void* out, long long frames, int src_w, i
 // [..][8] bf16. Up to YUV420_MAX_CLIPS offsets travel in the kernel arguments;
 // more need offs_dev, the same table in device memory. -4: a frame or a span
 // would reach outside its frame stride / the buffer (nothing is launched).
+// matrix: 0 BT.601 video range (even frame sizes), 1 full-range JFIF (any size;
+// chroma planes of ceil(w / 2) x ceil(h / 2)).
 int rnb_yuv420_to_clip(const void* buf, long long buf_len, const long long* offs,
                        const void* offs_dev, int nclips, int F, int src_w, int src_h,
                        long long frame_stride, const long long* plane_off,
                        const int* plane_stride, int c_step, void* out, int out_w, int out_h,
                        const float* crop, const float* mean, const float* stdv, int bf16,
-                       hipStream_t stream) {
+                       int matrix, hipStream_t stream) {
   if (nclips <= 0) return 0;
-  if (F <= 0 || src_w < 2 || src_h < 2 || src_w % 2 || src_h % 2 || out_w <= 0 || out_h <= 0)
-    return -2;
+  if (matrix != 0 && matrix != 1) return -2;
+  if (F <= 0 || src_w < 1 || src_h < 1 || out_w <= 0 || out_h <= 0) return -2;
+  if (matrix == 0 && (src_w % 2 || src_h % 2)) return -2;
   if (((uintptr_t)out & 15u) != 0 || (c_step != 1 && c_step != 2)) return -2;
   if (nclips > YUV420_MAX_CLIPS && !offs_dev) return -3;
   // every byte nv12_sample can touch lies inside its frame (int indexing there)
   if (frame_stride <= 0 || frame_stride > 0x7FFFFFFFLL) return -4;
-  const int cw = src_w / 2, ch = src_h / 2;
+  const int cw = (src_w + matrix) / 2, ch = (src_h + matrix) / 2;
   for (int p = 0; p < 3; ++p) {
     if (plane_off[p] < 0 || plane_stride[p] <= 0) return -4;
     const long long row = p == 0 ? src_w : (long long)(cw - 1) * c_step + 1;
@@ -705,12 +711,10 @@ int rnb_yuv420_to_clip(const void* buf, long long buf_len, const long long* offs
   const bool in_args = nclips <= YUV420_MAX_CLIPS;
   for (int c = 0; c < YUV420_MAX_CLIPS; ++c) a.offs[c] = in_args && c < nclips ? offs[c] : 0;
   const dim3 grid((unsigned)((ohw + 255) / 256), (unsigned)F, (unsigned)nclips);
-  if (in_args)
-    hipLaunchKernelGGL(yuv420_clip_kernel<false>, grid, dim3(256), 0, stream,
-                       (const uint8_t*)buf, (const long long*)nullptr, out, a);
-  else
-    hipLaunchKernelGGL(yuv420_clip_kernel<true>, grid, dim3(256), 0, stream,
-                       (const uint8_t*)buf, (const long long*)offs_dev, out, a);
+  auto kernel = in_args ? (matrix ? yuv420_clip_kernel<false, true> : yuv420_clip_kernel<false, false>)
+                        : (matrix ? yuv420_clip_kernel<true, true> : yuv420_clip_kernel<true, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (const uint8_t*)buf,
+                     in_args ? (const long long*)nullptr : (const long long*)offs_dev, out, a);
   return (int)hipGetLastError();
 }
 

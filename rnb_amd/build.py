@@ -29,9 +29,11 @@ LIBRARIES = {
                            "video_ops.hip", "bn_ops.hip", "conv_halo_ws.hip", "conv21.hip",
                            "conv_f32.hip", "conv_wino_f32.hip", "conv_wino_x6.hip",
                            "conv_x6.hip", "conv_h3.hip", "conv_h3stem.hip", "conv_h3p.hip",
-                           "conv_h3w.hip"],
+                           "conv_h3w.hip", "jpeg_ops.hip"],
                           [], []),
     "librnb_runtime.so": (["runtime.cpp"], [], []),
+    # host-only C++ (no HIP headers): the MJPEG entropy decoder
+    "librnb_jpeg.so": (["jpeg_entropy.cpp"], [], ["-pthread"]),
     "librnb_tracer.so": (["tracer.cpp"], [], ["-L%s/lib" % ROCM, "-lrocprofiler-sdk",
                                                "-Wl,-rpath,%s/lib" % ROCM]),
 }

@@ -14,6 +14,10 @@ so only the sampled frames are read) and uploads them. ``Y4mDecoder`` reads raw
 YUV4MPEG2 (``.y4m``) files at their source resolution: it uploads only the
 sampled frames' file spans and scales / colour-converts them on the GPU
 (``yuv420_to_clip`` HIP kernel, the planar-chroma sibling of ``nv12_to_clip``).
+``MjpegDecoder`` reads Motion-JPEG streams (``.mjpeg``), the one compressed
+format decoded here: Huffman decode on the host (``librnb_jpeg.so``), then
+dequantisation and inverse DCT (``jpeg_idct`` HIP kernel) and the same
+``yuv420_to_clip`` kernel with the full-range JFIF matrix on the GPU.
 
 Every decoder returns NDHWC clips normalised with the Kinetics mean/std:
 ``fp32 [n, 8, 112, 112, 4]`` (reference precision) or ``bf16 [n, 8, 112, 112, 8]``
@@ -30,7 +34,7 @@ import numpy as np
 import torch
 
 from ...ops import video as vops
-from ...utils import y4m
+from ...utils import mjpeg, y4m
 from ...video_path_provider import parse_synthetic_path
 
 
@@ -176,48 +180,28 @@ class _UploadEntry:
             self.in_flight = False
 
 
-class Y4mDecoder(Decoder):
-    """Raw YUV4MPEG2 (``.y4m``) videos at their source resolution.
-
-    ``probe`` memory-maps the file and parses its header (``utils/y4m.py``):
-    8-bit 4:2:0 only, i.e. no ``C`` field or ``C420`` / ``C420jpeg`` /
-    ``C420mpeg2`` / ``C420paldv``. These differ in chroma siting; all are
-    sampled with the kernel's centred siting (chroma sample centres at 2x + 0.5
-    luma pixels, exact for ``C420jpeg``; the co-sited variants are read half a
-    luma pixel off horizontally, as NVVL's scaler does not distinguish them
-    either). Everything else raises ``ValueError`` naming file and field.
-
-    ``decode`` treats each clip's F consecutive frames as one contiguous span
-    of the file: it copies the span into a pinned staging buffer, checks the
-    ``FRAME`` marker of every frame, issues one asynchronous upload per clip
-    and then one ``yuv420_to_clip`` launch (scale, BT.601, normalise) straight
-    into ``out``. Staging and upload buffers form a ring of ``depth`` requests
-    owned by the decoder, sized on first use for ``max(n, 15)`` clips and
-    regrown for larger frames; an entry is reused once the event recorded
-    behind its kernel has completed (waited for if not), so a warm decoder
-    neither pins nor allocates. On a CPU device the spans go to the op's CPU
-    mirror.
-
-    ``crop``: ``"full"`` scales the whole frame to the output (what the
-    synthetic NV12 path does), ``"center"`` the centred square of the short
-    side."""
+class _StagedFileDecoder(Decoder):
+    """What the file-backed decoders that upload bytes share: an LRU of memory
+    maps, and a ring of ``depth`` pinned staging / device upload buffers
+    (``_UploadEntry``) ordered by HIP events."""
 
     WARMUP_W, WARMUP_H = vops.SOURCE_W, vops.SOURCE_H
     MAX_OPEN = 64            # memory maps kept open (least recently used first out)
 
     def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
                  width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full"):
+        name = type(self).__name__
         if crop not in ("full", "center"):
-            raise ValueError("Y4mDecoder: crop must be 'full' or 'center', got %r" % (crop,))
+            raise ValueError("%s: crop must be 'full' or 'center', got %r" % (name, crop))
         if depth < 1:
-            raise ValueError("Y4mDecoder: ring depth must be >= 1, got %r" % (depth,))
+            raise ValueError("%s: ring depth must be >= 1, got %r" % (name, depth))
         self.device = device
         self.F, self.H, self.W = clip_length, height, width
         self.dtype = dtype
         self.depth = int(depth)
         self.crop = crop
         self._ids = {}
-        self._videos = {}          # video id -> (path, Y4mHeader)
+        self._videos = {}          # video id -> (path, header / index)
         self._maps = OrderedDict()  # video id -> (mmap, uint8 view), LRU
         self._ring: List[_UploadEntry] = []
         self._ring_bytes = 0
@@ -236,23 +220,6 @@ class Y4mDecoder(Decoder):
         while len(self._maps) > self.MAX_OPEN:
             self._maps.popitem(last=False)       # unmapped once its views are gone
         return got
-
-    def probe(self, path):
-        vid = self._ids.get(path)
-        if vid is not None:
-            return vid, self._videos[vid][1].num_frames
-        if os.path.getsize(path) == 0:
-            raise ValueError("%s: empty file (field 'magic')" % path)
-        vid = len(self._ids)
-        mm, _ = self._map(vid, path)
-        try:
-            hdr = y4m.read_header(path, data=mm)
-        except ValueError:
-            del self._maps[vid]
-            raise
-        self._ids[path] = vid
-        self._videos[vid] = (path, hdr)
-        return vid, hdr.num_frames
 
     def _crop_box(self, hdr):
         if self.crop == "full":
@@ -279,6 +246,50 @@ class Y4mDecoder(Decoder):
             return out
         C = vops.IN_CHANNELS_P_F32 if self.dtype == torch.float32 else vops.IN_CHANNELS_P
         return torch.empty((n, self.F, self.H, self.W, C), dtype=self.dtype, device=self.device)
+
+
+class Y4mDecoder(_StagedFileDecoder):
+    """Raw YUV4MPEG2 (``.y4m``) videos at their source resolution.
+
+    ``probe`` memory-maps the file and parses its header (``utils/y4m.py``):
+    8-bit 4:2:0 only, i.e. no ``C`` field or ``C420`` / ``C420jpeg`` /
+    ``C420mpeg2`` / ``C420paldv``. These differ in chroma siting; all are
+    sampled with the kernel's centred siting (chroma sample centres at 2x + 0.5
+    luma pixels, exact for ``C420jpeg``; the co-sited variants are read half a
+    luma pixel off horizontally, as NVVL's scaler does not distinguish them
+    either). Everything else raises ``ValueError`` naming file and field.
+
+    ``decode`` treats each clip's F consecutive frames as one contiguous span
+    of the file: it copies the span into a pinned staging buffer, checks the
+    ``FRAME`` marker of every frame, issues one asynchronous upload per clip
+    and then one ``yuv420_to_clip`` launch (scale, BT.601, normalise) straight
+    into ``out``. Staging and upload buffers form a ring of ``depth`` requests
+    owned by the decoder, sized on first use for ``max(n, 15)`` clips and
+    regrown for larger frames; an entry is reused once the event recorded
+    behind its kernel has completed (waited for if not), so a warm decoder
+    neither pins nor allocates. On a CPU device the spans go to the op's CPU
+    mirror.
+
+    ``crop``: ``"full"`` scales the whole frame to the output (what the
+    synthetic NV12 path does), ``"center"`` the centred square of the short
+    side."""
+
+    def probe(self, path):
+        vid = self._ids.get(path)
+        if vid is not None:
+            return vid, self._videos[vid][1].num_frames
+        if os.path.getsize(path) == 0:
+            raise ValueError("%s: empty file (field 'magic')" % path)
+        vid = len(self._ids)
+        mm, _ = self._map(vid, path)
+        try:
+            hdr = y4m.read_header(path, data=mm)
+        except ValueError:
+            del self._maps[vid]
+            raise
+        self._ids[path] = vid
+        self._videos[vid] = (path, hdr)
+        return vid, hdr.num_frames
 
     def warmup(self, n: int) -> None:
         """Run the clip kernel on a zeroed upload buffer (no file needed)."""
@@ -345,12 +356,138 @@ class Y4mDecoder(Decoder):
         return out
 
 
+class MjpegDecoder(_StagedFileDecoder):
+    """Motion-JPEG streams (``.mjpeg`` / ``.mjpg``: JPEG frames back to back)
+    at their source resolution, split the way a hardware decoder splits it:
+    the serial entropy decode on the host, the per-sample arithmetic on the GPU.
+
+    ``probe`` memory-maps the file and indexes it (``utils/mjpeg.py``,
+    ``rnb_mjpeg_index``): baseline sequential Huffman JPEG, 8-bit, 4:2:0, one
+    scan, all frames of one size; anything else raises ``ValueError`` naming
+    file, frame and field. AVI / MOV containers, progressive JPEG, 4:2:2, 4:4:4
+    and grayscale are not read, and there is no Huffman decoding on the GPU.
+
+    ``decode`` entropy-decodes each clip's F frames (``librnb_jpeg.so``, on
+    ``threads`` host threads with the GIL released) straight into a pinned
+    staging entry as frame records of quantised coefficients, and uploads a
+    clip while the next one decodes. One ``jpeg_idct`` launch turns the records
+    into 8-bit I420 planes in a device surface the decoder owns, and one
+    ``yuv420_to_clip(matrix="jfif")`` launch scales, converts (full-range JFIF
+    YCbCr) and normalises them straight into ``out``; the frame's true size goes
+    to that kernel, so the MCU padding is never sampled. The staging ring and
+    its event discipline are ``Y4mDecoder``'s. On a CPU device the records go
+    to the ops' CPU mirrors.
+
+    ``crop`` as for ``Y4mDecoder``; ``threads``: 1-16 entropy-decode threads."""
+
+    def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
+                 width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full",
+                 threads: int = 4):
+        if isinstance(threads, bool) or not isinstance(threads, int) or not 1 <= threads <= 16:
+            raise ValueError("MjpegDecoder: threads must be an integer in 1..16, got %r"
+                             % (threads,))
+        if isinstance(depth, bool) or not isinstance(depth, int):
+            raise ValueError("MjpegDecoder: ring depth must be an integer, got %r" % (depth,))
+        super().__init__(device, clip_length, height, width, dtype, depth, crop)
+        self.threads = threads
+        self._surface = None       # device I420 planes of the request being decoded
+
+    def probe(self, path):
+        vid = self._ids.get(path)
+        if vid is not None:
+            return vid, self._videos[vid][1].num_frames
+        if os.path.getsize(path) == 0:
+            raise ValueError("%s: empty file (field 'SOI')" % path)
+        vid = len(self._ids)
+        _, data = self._map(vid, path)
+        try:
+            idx = mjpeg.read_index(path, data=data)
+        except ValueError:
+            del self._maps[vid]
+            raise
+        self._ids[path] = vid
+        self._videos[vid] = (path, idx)
+        return vid, idx.num_frames
+
+    def _planes(self, nframes: int, frame_bytes: int) -> torch.Tensor:
+        # one surface, reused: its uses are ordered on the stream
+        need = nframes * frame_bytes
+        if self._surface is None or self._surface.numel() < need:
+            self._surface = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._surface
+
+    def _to_clips(self, records, n, W, H, mw, mh, crop, out):
+        fbytes = 384 * mw * mh
+        surf = vops.jpeg_idct(records, n * self.F, mw, mh,
+                              out=self._planes(max(n, 15) * self.F, fbytes)
+                              if self.device.type == "cuda" else None)
+        return vops.yuv420_to_clip(surf, [i * self.F * fbytes for i in range(n)], self.F, W, H,
+                                   fbytes, vops.jpeg_surface_planes(mw, mh), self.W, self.H,
+                                   crop=crop, dtype=self.dtype, out=out, matrix="jfif")
+
+    def warmup(self, n: int) -> None:
+        """Run both kernels on a zeroed record buffer (no file needed)."""
+        if self.device.type != "cuda":
+            return
+        W, H = self.WARMUP_W, self.WARMUP_H
+        mw, mh, rb = mjpeg.geometry(W, H)
+        for i in range(n):
+            e = self._entry(15 * self.F * rb)
+            e.dev[:self.F * rb].zero_()
+            try:
+                self._to_clips(e.dev[:self.F * rb], 1, W, H, mw, mh, None, self._out(1, None))
+            finally:
+                e.event.record(torch.cuda.current_stream(self.device))
+                e.in_flight = True
+
+    def decode(self, vid, starts, out=None):
+        n = len(starts)
+        if n == 0:
+            return self.empty()
+        got = self._videos.get(vid)
+        if got is None:
+            raise KeyError("video id %r was not probed" % (vid,))
+        path, idx = got
+        _, data = self._map(vid, path)
+        for s in starts:
+            if s < 0 or s + self.F > idx.num_frames:
+                raise ValueError("%s: clip at frame %d (+%d) is outside the %d frames"
+                                 % (path, s, self.F, idx.num_frames))
+        span = self.F * idx.record_bytes
+        cuda = self.device.type == "cuda"
+        if cuda:
+            entry = self._entry(max(n, 15) * span)
+            host, buf = entry.host, entry.dev
+        else:
+            host = np.empty(n * span, dtype=np.uint8)
+            buf = torch.from_numpy(host)
+        try:
+            for i, s in enumerate(starts):
+                mjpeg.entropy_decode(data, idx.offsets[s:s + self.F], idx.lengths[s:s + self.F],
+                                     host[i * span:(i + 1) * span], idx.record_bytes,
+                                     self.threads, name=path)
+                if cuda:     # this clip uploads while the next one decodes
+                    buf[i * span:(i + 1) * span].copy_(
+                        entry.pinned[i * span:(i + 1) * span], non_blocking=True)
+            out = self._out(n, out)
+            self._to_clips(buf[:n * span], n, idx.width, idx.height, idx.mw, idx.mh,
+                           self._crop_box(idx), out)
+        finally:
+            if cuda:     # also behind the uploads of a request that raised
+                entry.event.record(torch.cuda.current_stream(self.device))
+                entry.in_flight = True
+        return out
+
+
 def make_decoder(backend: str, device: torch.device, clip_length=8, height=112, width=112,
                  dtype=torch.bfloat16, decoder_args: Optional[dict] = None) -> Decoder:
     """``decoder_args``: backend-specific constructor arguments (``y4m``:
-    ``depth``, ``crop``); the other backends take none and ignore it."""
+    ``depth``, ``crop``; ``mjpeg``: ``depth``, ``crop``, ``threads``); the other
+    backends take none and ignore it."""
     if backend == "y4m":
         return Y4mDecoder(device, clip_length, height, width, dtype, **(decoder_args or {}))
+    if backend == "mjpeg":
+        return MjpegDecoder(device, clip_length, height, width, dtype, **(decoder_args or {}))
     if backend in ("synthetic", "synthetic-nv12"):
         return SyntheticDecoder(device, clip_length, height, width, dtype, source="nv12")
     if backend == "synthetic-rgb":
@@ -360,5 +497,5 @@ def make_decoder(backend: str, device: torch.device, clip_length=8, height=112, 
     if backend in ("rocdecode", "nvvl"):
         raise RuntimeError("decoder backend %r is not available on this system "
                            "(no rocDecode/VCN library installed); use 'synthetic', "
-                           "'y4m' or 'npy'" % backend)
+                           "'y4m', 'mjpeg' or 'npy'" % backend)
     raise ValueError("unknown decoder backend %r" % backend)

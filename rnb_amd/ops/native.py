@@ -216,8 +216,12 @@ class Kernels:
                                            ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_float), ctypes.c_int,
-                                           ctypes.c_void_p]
+                                           ctypes.c_int, ctypes.c_void_p]
         lib.rnb_yuv420_to_clip.restype = ctypes.c_int
+        lib.rnb_jpeg_idct.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong,
+                                      ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
+        lib.rnb_jpeg_idct.restype = ctypes.c_int
         lib.rnb_preprocess.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
                                        ctypes.POINTER(ctypes.c_float),
                                        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
@@ -798,10 +802,11 @@ class Kernels:
 
     def yuv420_to_clip(self, buf_ptr, buf_len, offsets, offsets_dev_ptr, F, src_w, src_h,
                        frame_stride, plane_offsets, plane_strides, c_step, out_ptr, out_w,
-                       out_h, crop, mean, std, bf16, stream):
+                       out_h, crop, mean, std, bf16, stream, matrix=0):
         """``offsets``: the per-clip byte offsets on the host (checked against
         ``buf_len`` by the launcher); ``offsets_dev_ptr``: the same table in
-        device memory, needed for more than 32 clips (else None)."""
+        device memory, needed for more than 32 clips (else None). ``matrix``:
+        0 BT.601 video range, 1 full-range JFIF."""
         n = len(offsets)
         offs = (ctypes.c_longlong * max(1, n))(*offsets)
         po = (ctypes.c_longlong * 3)(*plane_offsets)
@@ -812,7 +817,14 @@ class Kernels:
         _check(self.lib.rnb_yuv420_to_clip(buf_ptr, buf_len, offs, offsets_dev_ptr, n, F,
                                            src_w, src_h, frame_stride, po, ps, c_step,
                                            out_ptr, out_w, out_h, c, m, s, 1 if bf16 else 0,
-                                           stream), "yuv420_to_clip")
+                                           int(matrix), stream), "yuv420_to_clip")
+
+    def jpeg_idct(self, rec_ptr, rec_len, record_bytes, nframes, mw, mh, surf_ptr, surf_len,
+                  stream):
+        """Frame records -> padded I420 surface; the launcher checks both
+        lengths against (mw, mh, nframes) before it launches."""
+        _check(self.lib.rnb_jpeg_idct(rec_ptr, rec_len, record_bytes, nframes, mw, mh,
+                                      surf_ptr, surf_len, stream), "jpeg_idct")
 
     def preprocess(self, in_ptr, out_ptr, npix, mean, std, stream):
         m = (ctypes.c_float * 3)(*mean)
@@ -836,6 +848,58 @@ class Kernels:
                      stream):
         _check(self.lib.rnb_video_reduce(logits_ptr, offsets_ptr, sums_ptr, argmax_ptr,
                                          nvid, ncls, stream), "video_reduce")
+
+
+class Jpeg:
+    """Typed wrappers over librnb_jpeg.so (host entropy decoder; no GPU needed)."""
+
+    def __init__(self):
+        lib = _load("librnb_jpeg.so")
+        self.lib = lib
+        ll, vp = ctypes.c_longlong, ctypes.c_void_p
+        lib.rnb_jpeg_error_name.argtypes = [ctypes.c_int]
+        lib.rnb_jpeg_error_name.restype = ctypes.c_char_p
+        lib.rnb_mjpeg_index.argtypes = [vp, ll, vp, vp, ll, ctypes.POINTER(ctypes.c_int)]
+        lib.rnb_mjpeg_index.restype = ll
+        lib.rnb_jpeg_decode_frames.argtypes = [vp, ll, vp, vp, ctypes.c_int, vp, ll,
+                                               ctypes.c_int]
+        lib.rnb_jpeg_decode_frames.restype = ctypes.c_int
+
+    def error_name(self, code: int) -> str:
+        return self.lib.rnb_jpeg_error_name(int(code)).decode()
+
+    def index(self, buf):
+        """``buf``: contiguous uint8 numpy array. Returns (width, height, restart
+        interval, offsets int64, lengths int64), or (field, frame) on a refusal."""
+        import numpy as np
+        info = (ctypes.c_int * 4)()
+        n = self.lib.rnb_mjpeg_index(buf.ctypes.data, buf.size, None, None, 0, info)
+        if n >= 0:
+            offs, lens = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+            n = self.lib.rnb_mjpeg_index(buf.ctypes.data, buf.size, offs.ctypes.data,
+                                         lens.ctypes.data, n, info)
+        if n < 0:
+            return self.error_name(n), int(info[2])
+        return int(info[0]), int(info[1]), int(info[3]), offs, lens
+
+    def decode_frames_rc(self, buf, offsets, lengths, out, record_bytes, threads=1) -> int:
+        """The launcher's return code: 0 or a negative refusal (ctypes releases
+        the GIL for the call). ``out``: flat uint8 array of >= n * record_bytes."""
+        import numpy as np
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        lens = np.ascontiguousarray(lengths, dtype=np.int64)
+        n = int(offs.size)
+        if lens.size != n or out.size < n * record_bytes or not out.flags.c_contiguous \
+                or not buf.flags.c_contiguous:
+            raise ValueError("jpeg decode_frames: table / output sizes do not fit")
+        return int(self.lib.rnb_jpeg_decode_frames(buf.ctypes.data, buf.size, offs.ctypes.data,
+                                                   lens.ctypes.data, n, out.ctypes.data,
+                                                   int(record_bytes), int(threads)))
+
+    def decode_frames(self, buf, offsets, lengths, out, record_bytes, threads=1):
+        """None, or the field name of the refusal."""
+        rc = self.decode_frames_rc(buf, offsets, lengths, out, record_bytes, threads)
+        return None if rc == 0 else self.error_name(rc)
 
 
 class Runtime:
@@ -1008,6 +1072,7 @@ class Runtime:
 
 _kernels: Optional[Kernels] = None
 _runtime: Optional[Runtime] = None
+_jpeg: Optional[Jpeg] = None
 
 
 def kernels() -> Kernels:
@@ -1015,6 +1080,13 @@ def kernels() -> Kernels:
     if _kernels is None:
         _kernels = Kernels()
     return _kernels
+
+
+def jpeg() -> Jpeg:
+    global _jpeg
+    if _jpeg is None:
+        _jpeg = Jpeg()
+    return _jpeg
 
 
 def runtime() -> Runtime:

@@ -178,10 +178,15 @@ def nv12_to_clip(nv12: torch.Tensor, src_w: int, src_h: int, out_w: int = 112,
     return _planes_to_clip(y_plane, uv[..., 0], uv[..., 1], shape, crop, dtype, mean, std, out)
 
 
-def _planes_to_clip(y_plane, u_plane, v_plane, shape, crop, dtype, mean, std, out):
+MATRICES = ("bt601", "jfif")
+
+
+def _planes_to_clip(y_plane, u_plane, v_plane, shape, crop, dtype, mean, std, out,
+                    matrix="bt601"):
     """CPU mirror shared by ``nv12_to_clip`` and ``yuv420_to_clip``: float Y
     [frames, h, w] and U, V [frames, h/2, w/2] planes -> ``shape`` =
-    [..., out_h, out_w, C] normalised frames."""
+    [..., out_h, out_w, C] normalised frames. ``matrix``: ``"bt601"`` (video
+    range) or ``"jfif"`` (full-range JFIF YCbCr)."""
     out_h, out_w = shape[-3], shape[-2]
     ox = torch.arange(out_w, dtype=torch.float32)
     oy = torch.arange(out_h, dtype=torch.float32)
@@ -191,8 +196,12 @@ def _planes_to_clip(y_plane, u_plane, v_plane, shape, crop, dtype, mean, std, ou
     cx, cy = (sx + 0.5) * 0.5 - 0.5, (sy + 0.5) * 0.5 - 0.5
     u = _bilinear_torch(u_plane, cx, cy) - 128.0
     v = _bilinear_torch(v_plane, cx, cy) - 128.0
-    yy = 1.164 * (yv - 16.0)
-    rgb = torch.stack([yy + 1.596 * v, yy - 0.392 * u - 0.813 * v, yy + 2.017 * u], dim=-1)
+    if matrix == "jfif":
+        rgb = torch.stack([yv + 1.402 * v, yv - 0.344136 * u - 0.714136 * v, yv + 1.772 * u],
+                          dim=-1)
+    else:
+        yy = 1.164 * (yv - 16.0)
+        rgb = torch.stack([yy + 1.596 * v, yy - 0.392 * u - 0.813 * v, yy + 2.017 * u], dim=-1)
     scale, shift = _norm32(mean, std)
     rgb = rgb.clamp(0.0, 255.0) * scale + shift
     res = torch.zeros(shape, dtype=torch.float32)
@@ -232,14 +241,22 @@ def nv12_planes(W: int, H: int, header: int = 0) -> YuvPlanes:
 def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: int,
                    frame_stride: int, planes: YuvPlanes, out_w: int = 112, out_h: int = 112,
                    crop=None, dtype=torch.float32, mean=KINETICS_MEAN, std=KINETICS_STD,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, matrix: str = "bt601") -> torch.Tensor:
     """4:2:0 frames inside a byte buffer -> normalised NDHWC clips
     [n, F, out_h, out_w, C] (fp32 C=4 / bf16 C=8), with ``nv12_to_clip``'s
     arithmetic. ``buf`` is a flat uint8 tensor (uploaded file spans); clip ``c``
     is the ``F`` frames that start at byte ``clip_offsets[c]`` and lie
     ``frame_stride`` bytes apart; ``planes`` (``YuvPlanes``) locates the samples
     within a frame. No alignment of any offset is assumed. One kernel launch
-    for all clips; every span is checked against ``buf`` before it."""
+    for all clips; every span is checked against ``buf`` before it.
+    ``matrix="bt601"`` is ``nv12_to_clip``'s video-range matrix and needs even
+    frame sizes; ``matrix="jfif"`` is the full-range JFIF YCbCr of JPEG frames
+    (R = Y + 1.402 (Cr - 128), G = Y - 0.344136 (Cb - 128) - 0.714136 (Cr - 128),
+    B = Y + 1.772 (Cb - 128)) and takes any size, with chroma planes of
+    ceil(w / 2) x ceil(h / 2)."""
+    if matrix not in MATRICES:
+        raise ValueError("yuv420_to_clip: matrix must be one of %s, got %r" % (MATRICES, matrix))
+    jfif = matrix == "jfif"
     offsets = [int(o) for o in (clip_offsets.tolist() if isinstance(clip_offsets, torch.Tensor)
                                 else clip_offsets)]
     n = len(offsets)
@@ -266,13 +283,14 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
                                  src_h, frame_stride, planes[:3], planes[3:6], planes.c_step,
                                  out.data_ptr(), out_w, out_h, crop, mean, std,
                                  dtype == torch.bfloat16,
-                                 torch.cuda.current_stream(buf.device).cuda_stream)
+                                 torch.cuda.current_stream(buf.device).cuda_stream,
+                                 matrix=1 if jfif else 0)
         return out
-    if src_w % 2 or src_h % 2 or planes.c_step not in (1, 2):
+    if (not jfif and (src_w % 2 or src_h % 2)) or planes.c_step not in (1, 2):
         raise ValueError("yuv420_to_clip: even frame sizes and a chroma step of 1 or 2")
     if any(o < 0 or o + F * frame_stride > buf.numel() for o in offsets):
         raise ValueError("yuv420_to_clip: a clip span lies outside the buffer")
-    cw, ch = src_w // 2, src_h // 2
+    cw, ch = (src_w + jfif) // 2, (src_h + jfif) // 2
     base = (torch.tensor(offsets, dtype=torch.int64).view(n, 1)
             + torch.arange(F, dtype=torch.int64).view(1, F) * frame_stride).view(-1, 1, 1)
 
@@ -283,7 +301,69 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
     return _planes_to_clip(gather(planes.y, planes.y_stride, src_h, src_w, 1),
                            gather(planes.u, planes.u_stride, ch, cw, planes.c_step),
                            gather(planes.v, planes.v_stride, ch, cw, planes.c_step),
-                           shape, crop, dtype, mean, std, out)
+                           shape, crop, dtype, mean, std, out, matrix)
+
+
+# ---------------------------------------------------------------------------
+# MJPEG frame records (utils/mjpeg.py) -> padded I420 surfaces
+# ---------------------------------------------------------------------------
+def jpeg_surface_planes(mw: int, mh: int) -> YuvPlanes:
+    """Where ``jpeg_idct`` puts a frame's planes (frame stride ``384 mw mh``)."""
+    n = mw * mh
+    return YuvPlanes(0, 256 * n, 320 * n, 16 * mw, 8 * mw, 8 * mw, 1)
+
+
+def jpeg_idct(records: torch.Tensor, nframes: int, mw: int, mh: int,
+              out: Optional[torch.Tensor] = None,
+              record_bytes: Optional[int] = None) -> torch.Tensor:
+    """Dequantise + 8x8 inverse DCT of ``nframes`` frame records (flat uint8
+    tensor, ``record_bytes`` apart, default ``384 + 768 mw mh``; layout in
+    ``utils/mjpeg.py``) into 8-bit planar frames at the padded size: per frame
+    Y [16 mh, 16 mw], then Cb and Cr [8 mh, 8 mw], ``384 mw mh`` bytes. ``out``:
+    a flat uint8 surface to write into (the result is its leading part). fp32
+    arithmetic, + 128, round to nearest, clamp. On the GPU one
+    ``jpeg_idct_kernel`` launch, after the launcher checked both buffers
+    against the geometry; on the CPU a torch mirror."""
+    n = mw * mh
+    rb = 384 + 768 * n if record_bytes is None else int(record_bytes)
+    need = nframes * 384 * n
+    if records.dtype != torch.uint8 or records.dim() != 1 or not records.is_contiguous():
+        raise ValueError("jpeg_idct: records must be a flat contiguous uint8 tensor")
+    if out is not None and (out.dtype != torch.uint8 or out.dim() != 1
+                            or not out.is_contiguous() or out.device != records.device):
+        raise ValueError("jpeg_idct: out must be a flat contiguous uint8 tensor on %s"
+                         % (records.device,))
+    if records.is_cuda:
+        from .native import kernels
+        if out is None:
+            out = torch.empty(need, dtype=torch.uint8, device=records.device)
+        kernels().jpeg_idct(records.data_ptr(), records.numel(), rb, nframes, mw, mh,
+                            out.data_ptr(), out.numel(),
+                            torch.cuda.current_stream(records.device).cuda_stream)
+        return out[:need]
+    if mw < 1 or mh < 1 or rb < 384 + 768 * n or nframes * rb > records.numel() \
+            or (out is not None and out.numel() < need):
+        raise ValueError("jpeg_idct: a record or a frame lies outside its buffer")
+    rec = records[:nframes * rb].view(nframes, rb)
+    qt = rec[:, :384].contiguous().view(torch.int16).view(nframes, 3, 1, 64).float()
+    co = rec[:, 384:384 + 768 * n].contiguous().view(torch.int16).view(nframes, 6 * n, 64).float()
+    u = torch.arange(8, dtype=torch.float64)
+    basis = 0.5 * torch.cos((2.0 * u.view(8, 1) + 1.0) * u.view(1, 8) * math.pi / 16.0)
+    basis[:, 0] *= math.sqrt(0.5)
+    basis = basis.float()                                   # [x][u], as the kernel's table
+    planes = []
+    for c, (lo, hi, rows, cols) in enumerate(((0, 4 * n, 2 * mh, 2 * mw),
+                                              (4 * n, 5 * n, mh, mw), (5 * n, 6 * n, mh, mw))):
+        f = (co[:, lo:hi] * qt[:, c]).view(nframes, -1, 8, 8)           # [frame, block, u, v]
+        s = torch.einsum("xu,fbuv,yv->fbxy", basis, f, basis) + 128.0
+        s = s.round().clamp(0, 255).to(torch.uint8)
+        planes.append(s.view(nframes, rows, cols, 8, 8).permute(0, 1, 3, 2, 4)
+                      .reshape(nframes, -1))
+    res = torch.cat(planes, dim=1).reshape(-1)
+    if out is not None:
+        out[:need].copy_(res)
+        return out[:need]
+    return res
 
 
 def preprocess(frames_u8: torch.Tensor, mean=KINETICS_MEAN, std=KINETICS_STD,
