@@ -4,7 +4,10 @@
 // concatenated JPEG frames and Huffman-decodes sampled frames into "frame
 // records" of quantised coefficients, which the GPU (jpeg_idct_kernel in
 // jpeg_ops.hip) dequantises and transforms. Plain C++17 behind a C ABI: no HIP,
-// no PyTorch, loads on a machine without a GPU.
+// no PyTorch, loads on a machine without a GPU. The decode loop itself lives in
+// jpeg_huff.h, shared with the GPU kernel (jpeg_huff.hip); for that kernel this
+// file also packs scans into scan records (rnb_jpeg_pack_scans) and mirrors the
+// kernel on the host (rnb_jpeg_decode_scans_host).
 //
 // Read: baseline sequential Huffman (SOF0), 8-bit samples, three components
 // sampled 2x2 / 1x1 / 1x1 (4:2:0) in one interleaved scan, up to 4 + 4 Huffman
@@ -30,47 +33,11 @@
 #include <thread>
 #include <vector>
 
+#include "jpeg_huff.h"
+
+using namespace jpeg_huff;   // codes, tables, bit reader, decode_block / decode_interval
+
 namespace {
-
-enum {
-  E_OK = 0,
-  E_ARG = -1,          // null pointer, negative length, bad thread / frame count
-  E_TRUNCATED = -2,    // data ends inside a segment or inside the scan
-  E_SOI = -3,          // frame does not start with SOI
-  E_SOF = -4,          // progressive / extended / lossless frame (SOF1-3, 5-7, 9-15)
-  E_ARITHMETIC = -5,   // arithmetic coding (SOF9-11, 13-15, DAC)
-  E_PRECISION = -6,    // sample precision other than 8 bits
-  E_QT16 = -7,         // 16-bit quantisation table
-  E_COMPONENTS = -8,   // component count other than 3
-  E_SAMPLING = -9,     // sampling factors other than 2x2, 1x1, 1x1
-  E_MULTISCAN = -10,   // more than one scan, or a scan that is not all three components
-  E_SIZE_CHANGE = -11, // frame size differs from the first frame's
-  E_HUFFMAN = -12,     // a code that matches no entry / an invalid table
-  E_RUN = -13,         // zero run past coefficient 63
-  E_RESTART = -14,     // missing or wrong RSTn
-  E_MARKER = -15,      // malformed marker segment
-  E_EOI = -16,         // no EOI behind the scan
-  E_TABLE = -17,       // scan refers to a table the frame did not define
-  E_RECORD = -18,      // record_bytes too small for the frame
-  E_DC_RANGE = -19,    // DC category > 11 or predictor outside int16
-  E_SIZE = -20,        // zero width or height
-};
-
-const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                             12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                             58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-constexpr int LOOK = 9;
-
-struct Huff {
-  bool set = false;
-  uint8_t vals[256];
-  int maxcode[18];      // largest code of each length, -1 if none
-  int valptr[17];
-  int mincode[17];
-  uint16_t lut[1 << LOOK];   // (length << 8) | symbol for codes of <= LOOK bits, else 0
-};
 
 struct Frame {
   int w = 0, h = 0;
@@ -78,40 +45,30 @@ struct Frame {
   int restart = 0;
   bool qset[4] = {false, false, false, false};
   uint16_t qt[4][64];
-  Huff dc[4], ac[4];
+  Huff dc[4], ac[4];           // built with TABLES_BUILD
+  bool rawset[2][4];           // [class][id]: the DHT segment as it stands, for the packer
+  uint8_t raw[2][4][SR_TABLE]; // 16 counts + values, zero padded
   long long scan_begin = 0;   // first entropy-coded byte
+  long long scan_end = 0;     // the FF of the marker that ends the scan
   long long frame_end = 0;    // one past EOI
+  Frame() {
+    for (int i = 0; i < 4; ++i) {
+      dc[i].set = ac[i].set = 0;
+      rawset[0][i] = rawset[1][i] = false;
+    }
+  }
 };
 
-int build_huff(const uint8_t* bits, const uint8_t* vals, int nvals, Huff& h) {
-  int code = 0, k = 0;
-  for (int i = 0; i < (1 << LOOK); ++i) h.lut[i] = 0;
-  for (int l = 1; l <= 16; ++l) {
-    h.valptr[l] = k;
-    h.mincode[l] = code;
-    for (int i = 0; i < bits[l]; ++i, ++k, ++code) {
-      if (code >= (1 << l)) return E_HUFFMAN;          // over-subscribed code
-      if (l <= LOOK) {
-        const int lo = code << (LOOK - l), n = 1 << (LOOK - l);
-        for (int j = 0; j < n; ++j) h.lut[lo + j] = (uint16_t)((l << 8) | vals[k]);
-      }
-    }
-    h.maxcode[l] = bits[l] ? code - 1 : -1;
-    code <<= 1;
-  }
-  h.maxcode[17] = 0x7FFFFFFF;
-  if (k != nvals) return E_HUFFMAN;
-  memset(h.vals, 0, sizeof h.vals);
-  memcpy(h.vals, vals, (size_t)nvals);
-  h.set = true;
-  return E_OK;
-}
+// what parse_frame does with a DHT segment: nothing (the index), build the
+// decode tables (the host decoder), or keep the segment's bytes (the packer,
+// which does no Huffman work); the scan's tables must exist in the latter two
+enum { TABLES_NONE = 0, TABLES_BUILD = 1, TABLES_RAW = 2 };
 
 inline int rd16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
 // Parse one frame that starts at p[0] (SOI); n bytes are readable. Walks the
 // marker segments by their lengths and the scan up to EOI.
-int parse_frame(const uint8_t* p, long long n, Frame& f, bool tables) {
+int parse_frame(const uint8_t* p, long long n, Frame& f, int tables) {
   if (n < 4) return n < 2 || (p[0] == 0xFF && p[1] == 0xD8) ? E_TRUNCATED : E_SOI;
   if (p[0] != 0xFF || p[1] != 0xD8) return E_SOI;
   long long pos = 2;
@@ -163,9 +120,15 @@ int parse_frame(const uint8_t* p, long long n, Frame& f, bool tables) {
         bits[0] = 0;
         for (int l = 1; l <= 16; ++l) total += (bits[l] = s[o + l]);
         if (total > 256 || o + 17 + total > body) return E_MARKER;
-        if (tables) {
-          const int rc = build_huff(bits, s + o + 17, total, tc ? f.ac[th] : f.dc[th]);
+        if (tables == TABLES_BUILD) {
+          const int rc = build_huff(bits + 1, s + o + 17, total, tc ? f.ac[th] : f.dc[th]);
           if (rc) return rc;
+        } else if (tables == TABLES_RAW) {
+          uint8_t* r = f.raw[tc][th];
+          memset(r, 0, SR_TABLE);
+          memcpy(r, bits + 1, 16);
+          memcpy(r + 16, s + o + 17, (size_t)total);
+          f.rawset[tc][th] = true;
         }
         o += 17 + total;
       }
@@ -199,7 +162,9 @@ int parse_frame(const uint8_t* p, long long n, Frame& f, bool tables) {
         f.ta[c] = s[2 + 2 * c] & 15;
         if (f.td[c] > 3 || f.ta[c] > 3) return E_MARKER;
         if (!f.qset[f.tq[c]]) return E_TABLE;
-        if (tables && (!f.dc[f.td[c]].set || !f.ac[f.ta[c]].set)) return E_TABLE;
+        if (tables == TABLES_BUILD && (!f.dc[f.td[c]].set || !f.ac[f.ta[c]].set)) return E_TABLE;
+        if (tables == TABLES_RAW && (!f.rawset[0][f.td[c]] || !f.rawset[1][f.ta[c]]))
+          return E_TABLE;
       }
       if (s[7] != 0 || s[8] != 63 || s[9] != 0) return E_MULTISCAN;   // spectral selection
       have_sos = true;
@@ -214,6 +179,7 @@ int parse_frame(const uint8_t* p, long long n, Frame& f, bool tables) {
         const int b = p[pos + 1];
         if (b == 0x00 || (b >= 0xD0 && b <= 0xD7)) { pos += 2; continue; }
         if (b == 0xFF) { pos += 1; continue; }
+        f.scan_end = pos;
         break;                                         // a marker: handled by the outer loop
       }
       continue;
@@ -223,109 +189,12 @@ int parse_frame(const uint8_t* p, long long n, Frame& f, bool tables) {
   }
 }
 
-struct Bits {
-  const uint8_t* p;
-  long long pos, end;
-  uint64_t acc = 0;   // next bit is the top one
-  int n = 0;          // bits in acc
-  int fake = 0;       // zero bits appended behind the data (at a marker / the end)
-  bool marker = false;
-
-  void fill() {
-    while (n <= 56) {
-      unsigned b = 0;
-      if (!marker && pos < end) {
-        b = p[pos];
-        if (b == 0xFF) {
-          if (pos + 1 >= end) {
-            marker = true;
-          } else if (p[pos + 1] == 0x00) {
-            pos += 2;
-          } else if (p[pos + 1] == 0xFF) {
-            pos += 1;
-            continue;
-          } else {
-            marker = true;
-          }
-        } else {
-          pos += 1;
-        }
-      } else {
-        marker = true;
-      }
-      if (marker) {
-        b = 0;
-        if (fake < (1 << 20)) fake += 8;
-      }
-      acc |= (uint64_t)b << (56 - n);
-      n += 8;
-    }
-  }
-  inline unsigned peek(int k) const { return (unsigned)(acc >> (64 - k)); }
-  inline void skip(int k) { acc <<= k; n -= k; }
-  inline bool overrun() const { return n < fake; }
-};
-
-inline int decode_symbol(Bits& b, const Huff& h) {
-  const unsigned e = h.lut[b.peek(LOOK)];
-  if (e) {
-    b.skip(e >> 8);
-    return e & 0xFF;
-  }
-  int l = LOOK + 1;
-  int code = (int)b.peek(l);
-  while (l <= 16 && code > h.maxcode[l]) {
-    ++l;
-    if (l <= 16) code = (int)b.peek(l);
-  }
-  if (l > 16) return E_HUFFMAN;
-  b.skip(l);
-  const int idx = h.valptr[l] + code - h.mincode[l];
-  if (idx < 0 || idx > 255) return E_HUFFMAN;
-  return h.vals[idx];
-}
-
-inline int receive_extend(Bits& b, int s) {
-  const int v = (int)b.peek(s);
-  b.skip(s);
-  return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
-}
-
-int decode_block(Bits& b, const Huff& dc, const Huff& ac, int& pred, int16_t* blk) {
-  memset(blk, 0, 128);
-  if (b.n < 32) b.fill();
-  int s = decode_symbol(b, dc);
-  if (s < 0) return s;
-  if (s > 11) return E_DC_RANGE;
-  if (s) pred += receive_extend(b, s);
-  if (pred < -32768 || pred > 32767) return E_DC_RANGE;
-  blk[0] = (int16_t)pred;
-  for (int k = 1; k < 64;) {
-    if (b.n < 32) b.fill();
-    const int rs = decode_symbol(b, ac);
-    if (rs < 0) return rs;
-    const int r = rs >> 4;
-    s = rs & 15;
-    if (s == 0) {
-      if (r != 15) break;                  // EOB
-      if (k + 15 > 63) return E_RUN;       // ZRL: 16 zeros at k .. k + 15
-      k += 16;
-      continue;
-    }
-    k += r;
-    if (k > 63) return E_RUN;
-    blk[kZigzag[k]] = (int16_t)receive_extend(b, s);
-    ++k;
-  }
-  return b.overrun() ? E_TRUNCATED : E_OK;
-}
-
 // one frame -> one record; rec has room for 384 + 768 * mw * mh bytes
 int decode_frame(const uint8_t* p, long long n, int want_w, int want_h, uint8_t* rec,
                  long long record_bytes, int* dims) {
   std::vector<Frame> holder(1);            // ~14 KB of tables: off the thread's stack
   Frame& f = holder[0];
-  int rc = parse_frame(p, n, f, true);
+  int rc = parse_frame(p, n, f, TABLES_BUILD);
   if (rc) return rc;
   if (dims) { dims[0] = f.w; dims[1] = f.h; }
   if (want_w > 0 && (f.w != want_w || f.h != want_h)) return E_SIZE_CHANGE;
@@ -334,40 +203,27 @@ int decode_frame(const uint8_t* p, long long n, int want_w, int want_h, uint8_t*
   uint16_t* qt = (uint16_t*)rec;
   for (int c = 0; c < 3; ++c) memcpy(qt + 64 * c, f.qt[f.tq[c]], 128);
   int16_t* coef = (int16_t*)(rec + 384);      // every block is visited and zeroed first
-  Bits b;
-  b.p = p;
-  b.pos = f.scan_begin;
-  b.end = n;
-  int pred[3] = {0, 0, 0};
+  Tables t;
+  for (int c = 0; c < 3; ++c) {
+    t.dc[c] = &f.dc[f.td[c]];
+    t.ac[c] = &f.ac[f.ta[c]];
+  }
   const long long nmcu = mw * mh;
+  const long long per = f.restart ? f.restart : nmcu;
+  long long pos = f.scan_begin;
   int next_rst = 0;
-  long long in_interval = 0;
-  for (long long m = 0; m < nmcu; ++m) {
-    if (f.restart && in_interval == f.restart) {
-      b.fill();
-      // the marker follows the byte the interval ended in
-      if (!b.marker || b.n - b.fake >= 8 || b.overrun()) return E_RESTART;
-      if (b.pos + 1 >= b.end || p[b.pos] != 0xFF || p[b.pos + 1] != 0xD0 + next_rst)
-        return E_RESTART;
-      b.pos += 2;
-      b.acc = 0; b.n = 0; b.fake = 0; b.marker = false;
-      next_rst = (next_rst + 1) & 7;
-      pred[0] = pred[1] = pred[2] = 0;
-      in_interval = 0;
-    }
-    ++in_interval;
-    const long long my = m / mw, mx = m - my * mw;
-    for (int v = 0; v < 2; ++v)
-      for (int h = 0; h < 2; ++h) {
-        int16_t* blk = coef + 64 * ((2 * my + v) * (2 * mw) + 2 * mx + h);
-        rc = decode_block(b, f.dc[f.td[0]], f.ac[f.ta[0]], pred[0], blk);
-        if (rc) return rc;
-      }
-    for (int c = 1; c < 3; ++c) {
-      int16_t* blk = coef + 64 * ((3 + c) * nmcu + m);
-      rc = decode_block(b, f.dc[f.td[c]], f.ac[f.ta[c]], pred[c], blk);
-      if (rc) return rc;
-    }
+  for (long long m0 = 0; m0 < nmcu; m0 += per) {
+    Bits b;
+    rc = decode_interval(b, p, pos, n, t, m0, nmcu - m0 < per ? nmcu - m0 : per, mw, nmcu, coef,
+                         false);
+    if (rc) return rc;
+    if (m0 + per >= nmcu) break;
+    // the marker follows the byte the interval ended in
+    if (!interval_ended(b)) return E_RESTART;
+    if (b.pos + 1 >= b.end || p[b.pos] != 0xFF || p[b.pos + 1] != 0xD0 + next_rst)
+      return E_RESTART;
+    pos = b.pos + 2;
+    next_rst = (next_rst + 1) & 7;
   }
   return E_OK;
 }
@@ -399,6 +255,7 @@ const char* rnb_jpeg_error_name(int code) {
     case E_RECORD: return "record";
     case E_DC_RANGE: return "dc_range";
     case E_SIZE: return "dimensions";
+    case E_SCANREC: return "scan record";
     default: return "unknown";
   }
 }
@@ -418,7 +275,7 @@ long long rnb_mjpeg_index(const uint8_t* data, long long len, long long* offs, l
     holder[0] = Frame();
     Frame& f = holder[0];
     info[2] = (int)count;
-    const int rc = parse_frame(data + pos, len - pos, f, false);
+    const int rc = parse_frame(data + pos, len - pos, f, TABLES_NONE);
     if (rc) return rc;
     if (count == 0) {
       info[0] = f.w; info[1] = f.h; info[3] = f.restart;
@@ -471,6 +328,148 @@ int rnb_jpeg_decode_frames(const uint8_t* data, long long len, const long long* 
   }
   for (int i = 0; i < nframes; ++i)
     if (codes[(size_t)i]) return codes[(size_t)i];
+  return E_OK;
+}
+
+// Pack the scans of nframes frames into scan records (layout: jpeg_huff.h) for
+// the interval decoders, back to back in out[0 .. out_cap). Per frame:
+// parse_frame with its refusals, then one walk over the scan for RSTn markers,
+// which must number D0, D1, ... cyclically and be exactly ceil(nmcu / DRI) - 1
+// (E_RESTART otherwise). No Huffman work. scan_offs receives nframes + 1 byte
+// offsets into out (record i is [scan_offs[i], scan_offs[i + 1]), 16-byte
+// aligned). want_w / want_h: the size every frame must have (0: the first
+// frame's). info[0..2] = width, height, index of the frame a refusal is in.
+// Returns the number of bytes written, or a negative code (E_RECORD: out_cap
+// is too small).
+long long rnb_jpeg_pack_scans(const uint8_t* data, long long len, const long long* frame_offs,
+                              const long long* frame_lens, int nframes, uint8_t* out,
+                              long long out_cap, long long* scan_offs, int want_w, int want_h,
+                              int* info) {
+  if (!data || !frame_offs || !frame_lens || !out || !scan_offs || !info || len < 0 ||
+      nframes < 0 || out_cap < 0 || want_w < 0 || want_h < 0 || ((uintptr_t)out & 15u) != 0)
+    return E_ARG;
+  info[0] = want_w; info[1] = want_h; info[2] = 0;
+  for (int i = 0; i < nframes; ++i)
+    if (frame_offs[i] < 0 || frame_lens[i] < 0 || frame_offs[i] > len ||
+        frame_lens[i] > len - frame_offs[i])
+      return E_ARG;
+  std::vector<Frame> holder(1);
+  long long at = 0;
+  scan_offs[0] = 0;
+  for (int i = 0; i < nframes; ++i) {
+    info[2] = i;
+    holder[0] = Frame();
+    Frame& f = holder[0];
+    const uint8_t* p = data + frame_offs[i];
+    const int rc = parse_frame(p, frame_lens[i], f, TABLES_RAW);
+    if (rc) return rc;
+    if (info[0] == 0) { info[0] = f.w; info[1] = f.h; }
+    if (f.w != info[0] || f.h != info[1]) return E_SIZE_CHANGE;
+    const long long nmcu = (long long)((f.w + 15) / 16) * ((f.h + 15) / 16);
+    const long long per = f.restart && f.restart < nmcu ? f.restart : nmcu;
+    const long long n_int = (nmcu + per - 1) / per;
+    const long long scan_len = f.scan_end - f.scan_begin;
+    if (scan_len < 0 || scan_len > 0x7FFFFFFFLL) return E_ARG;
+    const long long size = (SR_SPANS + 8 * n_int + scan_len + 15) & ~15LL;
+    if (size > out_cap - at) return E_RECORD;
+    uint8_t* rec = out + at;
+    for (int c = 0; c < 3; ++c) {
+      memcpy(rec + 128 * c, f.qt[f.tq[c]], 128);
+      memcpy(rec + SR_HUFF + SR_TABLE * (2 * c), f.raw[0][f.td[c]], SR_TABLE);
+      memcpy(rec + SR_HUFF + SR_TABLE * (2 * c + 1), f.raw[1][f.ta[c]], SR_TABLE);
+    }
+    const uint32_t head[4] = {(uint32_t)n_int, (uint32_t)per, (uint32_t)scan_len, 0u};
+    memcpy(rec + SR_HEADER, head, 16);
+    uint8_t* spans = rec + SR_SPANS;
+    const uint8_t* scan = p + f.scan_begin;
+    // the bytes in front of a marker that are FF are fill bytes, not data
+    auto put_span = [&](long long k, long long begin, long long end) {
+      while (end > begin && scan[end - 1] == 0xFF) --end;
+      const uint32_t be[2] = {(uint32_t)begin, (uint32_t)end};
+      memcpy(spans + 8 * k, be, 8);
+    };
+    long long pos = 0, start = 0, k = 0;
+    while (pos < scan_len) {
+      const uint8_t* q = (const uint8_t*)memchr(scan + pos, 0xFF, (size_t)(scan_len - pos));
+      if (!q) break;
+      pos = q - scan;
+      const int b = scan[pos + 1];          // the scan ends in front of a marker: readable
+      if (b >= 0xD0 && b <= 0xD7) {
+        if (b - 0xD0 != (int)(k & 7) || k + 1 >= n_int) return E_RESTART;
+        put_span(k, start, pos);
+        ++k;
+        pos += 2;
+        start = pos;
+      } else {
+        pos += b == 0x00 ? 2 : 1;           // stuffing / a fill byte
+      }
+    }
+    if (k != n_int - 1) return E_RESTART;
+    put_span(k, start, scan_len);
+    uint8_t* body = spans + 8 * n_int;
+    memcpy(body, scan, (size_t)scan_len);
+    memset(body + scan_len, 0, (size_t)(size - (SR_SPANS + 8 * n_int + scan_len)));
+    at += size;
+    scan_offs[i + 1] = at;
+  }
+  return at;
+}
+
+// The GPU interval decoder's host mirror: nframes scan records (record i at
+// scans[scan_offs[i] .. scan_offs[i + 1])) into frame records record_bytes
+// apart in out, with what jpeg_huff_kernel does in the same order: the tables
+// are built from the record, qt is copied, every interval is decoded with
+// decode_record_interval, and status[i] is 0 or the code of the frame's
+// lowest-numbered failing interval (E_SCANREC / E_HUFFMAN for a record or a
+// table that is refused as a whole: all blocks zero then). Every block of
+// every record is written. Returns 0, or E_ARG when a buffer, an offset or an
+// alignment is refused (nothing is written then).
+int rnb_jpeg_decode_scans_host(const uint8_t* scans, long long scans_len,
+                               const long long* scan_offs, int nframes, int mw, int mh,
+                               uint8_t* out, long long out_len, long long record_bytes,
+                               int* status) {
+  if (nframes == 0) return E_OK;
+  if (!scans || !scan_offs || !out || !status || nframes < 0 || mw < 1 || mh < 1 || mw > 4096 ||
+      mh > 4096 || scans_len < 0 || out_len < 0)
+    return E_ARG;
+  const long long nmcu = (long long)mw * mh;
+  if (((uintptr_t)out & 15u) != 0 || record_bytes % 16 != 0 || record_bytes < 384 + 768 * nmcu ||
+      record_bytes > out_len / nframes)
+    return E_ARG;
+  if (scan_offs[0] < 0 || scan_offs[nframes] > scans_len) return E_ARG;
+  for (int i = 0; i < nframes; ++i)
+    if (scan_offs[i] % 16 != 0 || scan_offs[i + 1] - scan_offs[i] < SR_SPANS + 8) return E_ARG;
+  std::vector<Huff> tabs(6);
+  for (int i = 0; i < nframes; ++i) {
+    const uint8_t* rec = scans + scan_offs[i];
+    uint8_t* dst = out + (long long)i * record_bytes;
+    int16_t* coef = (int16_t*)(dst + 384);
+    ScanHeader h;
+    int rc = scan_record_check(rec, scan_offs[i + 1] - scan_offs[i], nmcu, h);
+    memcpy(dst, rec, 384);
+    Tables t;
+    for (int k = 0; k < 6 && !rc; ++k) {
+      const uint8_t* tb = rec + SR_HUFF + SR_TABLE * k;
+      int total = 0;
+      for (int l = 0; l < 16; ++l) total += tb[l];
+      tabs[(size_t)k].set = 0;
+      rc = build_huff(tb, tb + 16, total, tabs[(size_t)k]);
+    }
+    for (int c = 0; c < 3; ++c) {
+      t.dc[c] = &tabs[(size_t)(2 * c)];
+      t.ac[c] = &tabs[(size_t)(2 * c + 1)];
+    }
+    if (rc) {
+      memset(coef, 0, (size_t)(768 * nmcu));
+      status[i] = rc;
+      continue;
+    }
+    status[i] = E_OK;
+    for (long long v = 0; v < (long long)h.n_intervals; ++v) {
+      rc = decode_record_interval(rec, h, v, t, mw, nmcu, coef);
+      if (rc && !status[i]) status[i] = rc;
+    }
+  }
   return E_OK;
 }
 

@@ -172,6 +172,7 @@ class _UploadEntry:
         self.dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
         self.event = torch.cuda.Event()
         self.in_flight = False
+        self.pending = None      # MjpegDecoder(entropy="gpu"): status words not yet looked at
 
     def acquire(self) -> None:
         """The copies and the kernel of this entry's last request are done."""
@@ -365,7 +366,7 @@ class MjpegDecoder(_StagedFileDecoder):
     ``rnb_mjpeg_index``): baseline sequential Huffman JPEG, 8-bit, 4:2:0, one
     scan, all frames of one size; anything else raises ``ValueError`` naming
     file, frame and field. AVI / MOV containers, progressive JPEG, 4:2:2, 4:4:4
-    and grayscale are not read, and there is no Huffman decoding on the GPU.
+    and grayscale are not read.
 
     ``decode`` entropy-decodes each clip's F frames (``librnb_jpeg.so``, on
     ``threads`` host threads with the GIL released) straight into a pinned
@@ -378,19 +379,48 @@ class MjpegDecoder(_StagedFileDecoder):
     its event discipline are ``Y4mDecoder``'s. On a CPU device the records go
     to the ops' CPU mirrors.
 
-    ``crop`` as for ``Y4mDecoder``; ``threads``: 1-16 entropy-decode threads."""
+    ``crop`` as for ``Y4mDecoder``; ``threads``: 1-16 entropy-decode threads.
+
+    ``entropy="gpu"`` (opt-in; ``"host"`` is the path above) moves the Huffman
+    decode to the GPU. ``decode`` then only *packs* each clip's scans on the
+    host (``mjpeg.pack_scans``: header parse and restart markers, no Huffman
+    work) into the pinned entry, which is sized from the frames' byte lengths,
+    and uploads a clip while the next one packs: the entropy-coded bytes cross
+    the bus, not the coefficients. One ``jpeg_huff`` launch (one workgroup per
+    frame, one lane per restart interval, the host decoder's loop) writes the
+    frame records into a device buffer the decoder owns, and ``jpeg_idct`` and
+    ``yuv420_to_clip`` follow as above. What the packer refuses still raises
+    from ``decode``. What only the Huffman decode can find (a bad code, a run
+    past 63, an interval that does not end at its marker, ...) is *deferred*:
+    the kernel's per-frame status words are copied back asynchronously into
+    the entry's pinned memory and checked when that entry is next acquired
+    (after its event) and in ``drain()``; either raises ``JpegError`` naming
+    the file, the frame and the field of the request that failed. Until then
+    the pixels of a corrupt frame (of its failing restart intervals) are grey:
+    zero coefficients. On a CPU device the same decode loop runs on the host
+    and such a frame raises from ``decode``.
+
+    ``stats``: ``requests`` served and ``uploaded_bytes`` staged for upload
+    (records, or scan records and their offset table)."""
 
     def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
                  width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full",
-                 threads: int = 4):
+                 threads: int = 4, entropy: str = "host"):
         if isinstance(threads, bool) or not isinstance(threads, int) or not 1 <= threads <= 16:
             raise ValueError("MjpegDecoder: threads must be an integer in 1..16, got %r"
                              % (threads,))
         if isinstance(depth, bool) or not isinstance(depth, int):
             raise ValueError("MjpegDecoder: ring depth must be an integer, got %r" % (depth,))
+        if entropy not in ("host", "gpu"):
+            raise ValueError("MjpegDecoder: entropy must be 'host' or 'gpu', got %r" % (entropy,))
         super().__init__(device, clip_length, height, width, dtype, depth, crop)
         self.threads = threads
+        self.entropy = entropy
+        self.stats = {"requests": 0, "uploaded_bytes": 0}
         self._surface = None       # device I420 planes of the request being decoded
+        self._records = None       # entropy="gpu": device frame records of that request
+        self._status = None        # ... and the kernel's per-frame status words
+        self._max_len = {}         # video id -> longest frame in bytes
 
     def probe(self, path):
         vid = self._ids.get(path)
@@ -453,7 +483,11 @@ class MjpegDecoder(_StagedFileDecoder):
             if s < 0 or s + self.F > idx.num_frames:
                 raise ValueError("%s: clip at frame %d (+%d) is outside the %d frames"
                                  % (path, s, self.F, idx.num_frames))
+        self.stats["requests"] += 1
+        if self.entropy == "gpu":
+            return self._decode_gpu_entropy(vid, path, idx, data, starts, out)
         span = self.F * idx.record_bytes
+        self.stats["uploaded_bytes"] += n * span
         cuda = self.device.type == "cuda"
         if cuda:
             entry = self._entry(max(n, 15) * span)
@@ -478,11 +512,105 @@ class MjpegDecoder(_StagedFileDecoder):
                 entry.in_flight = True
         return out
 
+    # -- entropy="gpu" ----------------------------------------------------------
+    def _check_entry(self, e: _UploadEntry) -> None:
+        """Look at the status words of the entry's last request (its event has
+        completed); raises for the first frame that failed."""
+        pending, e.pending = e.pending, None
+        if pending is not None:
+            path, frames, at = pending
+            status = e.host[at:at + 4 * len(frames)].view(np.int32)
+            mjpeg.raise_for_status(status, path, frames)
+
+    def _entry(self, nbytes: int) -> _UploadEntry:
+        if self._ring and nbytes > self._ring_bytes:
+            self.drain()                         # the ring is replaced: look at it first
+        e = super()._entry(nbytes)
+        self._check_entry(e)
+        return e
+
+    def drain(self) -> None:
+        """Wait for every request in flight and raise ``JpegError`` for the
+        oldest one whose Huffman decode failed on the GPU (``entropy="gpu"``),
+        naming its file, frame and field. All deferred errors are cleared."""
+        first = None
+        for k in range(len(self._ring)):
+            e = self._ring[(self._next + k) % len(self._ring)]      # oldest first
+            e.acquire()
+            try:
+                self._check_entry(e)
+            except mjpeg.JpegError as err:
+                first = first or err
+        if first is not None:
+            raise first
+
+    def _device_buffer(self, name: str, numel: int, dtype) -> torch.Tensor:
+        # reused like _surface: its uses are ordered on the stream
+        buf = getattr(self, name)
+        if buf is None or buf.numel() < numel:
+            buf = torch.empty(numel, dtype=dtype, device=self.device)
+            setattr(self, name, buf)
+        return buf
+
+    def _decode_gpu_entropy(self, vid, path, idx, data, starts, out):
+        n, F = len(starts), self.F
+        nfr = n * F
+        longest = self._max_len.get(vid)
+        if longest is None:
+            longest = self._max_len[vid] = int(idx.lengths.max())
+        per = mjpeg.scan_record_bound(idx.mw, idx.mh, longest)
+        cap = max(n, 15) * F                                  # frames the entry is sized for
+        head = (8 * (cap + 1) + 15) & ~15                     # the offset table, then the records
+        stat_at = head + cap * per                            # then the status words come back
+        frames = [s + f for s in starts for f in range(F)]
+        cuda = self.device.type == "cuda"
+        if cuda:
+            entry = self._entry(stat_at + 4 * cap)
+            host, buf = entry.host, entry.dev
+        else:
+            host = np.empty(stat_at, dtype=np.uint8)
+            buf = torch.from_numpy(host)
+        offs = host[:8 * (nfr + 1)].view(np.int64)
+        try:
+            pos = head
+            for i, s in enumerate(starts):
+                got, rel = mjpeg.pack_scans(data, idx.offsets[s:s + F], idx.lengths[s:s + F],
+                                            host[pos:stat_at], idx.width, idx.height,
+                                            name=path, frame0=s)
+                offs[i * F:(i + 1) * F] = rel[:F] + pos
+                if cuda:     # this clip uploads while the next one packs
+                    buf[pos:pos + got].copy_(entry.pinned[pos:pos + got], non_blocking=True)
+                pos += got
+            offs[nfr] = pos
+            self.stats["uploaded_bytes"] += pos - head + 8 * (nfr + 1)
+            rb = idx.record_bytes
+            if cuda:
+                buf[:8 * (nfr + 1)].copy_(entry.pinned[:8 * (nfr + 1)], non_blocking=True)
+                records, status = vops.jpeg_huff(
+                    buf[:pos], offs, nfr, idx.mw, idx.mh,
+                    out=self._device_buffer("_records", cap * rb, torch.uint8),
+                    status=self._device_buffer("_status", cap, torch.int32),
+                    offs_dev=buf[:8 * (nfr + 1)].view(torch.int64))
+                entry.pinned[stat_at:stat_at + 4 * nfr].view(torch.int32).copy_(
+                    status, non_blocking=True)
+                entry.pending = (path, frames, stat_at)
+            else:
+                records, status = vops.jpeg_huff(buf[:pos], offs, nfr, idx.mw, idx.mh)
+                mjpeg.raise_for_status(status.numpy(), path, frames)
+            out = self._out(n, out)
+            self._to_clips(records, n, idx.width, idx.height, idx.mw, idx.mh,
+                           self._crop_box(idx), out)
+        finally:
+            if cuda:     # also behind the uploads of a request that raised
+                entry.event.record(torch.cuda.current_stream(self.device))
+                entry.in_flight = True
+        return out
+
 
 def make_decoder(backend: str, device: torch.device, clip_length=8, height=112, width=112,
                  dtype=torch.bfloat16, decoder_args: Optional[dict] = None) -> Decoder:
     """``decoder_args``: backend-specific constructor arguments (``y4m``:
-    ``depth``, ``crop``; ``mjpeg``: ``depth``, ``crop``, ``threads``); the other
+    ``depth``, ``crop``; ``mjpeg``: ``depth``, ``crop``, ``threads``, ``entropy``); the other
     backends take none and ignore it."""
     if backend == "y4m":
         return Y4mDecoder(device, clip_length, height, width, dtype, **(decoder_args or {}))

@@ -222,6 +222,11 @@ class Kernels:
                                       ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
         lib.rnb_jpeg_idct.restype = ctypes.c_int
+        lib.rnb_jpeg_huff.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong,
+                                      ctypes.c_void_p, ctypes.c_void_p]
+        lib.rnb_jpeg_huff.restype = ctypes.c_int
         lib.rnb_preprocess.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
                                        ctypes.POINTER(ctypes.c_float),
                                        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
@@ -826,6 +831,20 @@ class Kernels:
         _check(self.lib.rnb_jpeg_idct(rec_ptr, rec_len, record_bytes, nframes, mw, mh,
                                       surf_ptr, surf_len, stream), "jpeg_idct")
 
+    def jpeg_huff(self, scans_ptr, scans_len, offs_host, offs_dev_ptr, nframes, mw, mh,
+                  rec_ptr, rec_len, record_bytes, status_ptr, stream):
+        """Scan records -> frame records + per-frame status. ``offs_host``:
+        contiguous int64 numpy array of ``nframes + 1`` offsets, which the
+        launcher checks against ``scans_len`` before it launches;
+        ``offs_dev_ptr``: the same table on the device."""
+        if offs_host.dtype.name != "int64" or not offs_host.flags.c_contiguous \
+                or offs_host.size < nframes + 1:
+            raise ValueError("jpeg_huff: scan_offs must be %d contiguous int64 offsets"
+                             % (nframes + 1))
+        _check(self.lib.rnb_jpeg_huff(scans_ptr, scans_len, offs_host.ctypes.data, offs_dev_ptr,
+                                      nframes, mw, mh, rec_ptr, rec_len, record_bytes,
+                                      status_ptr, stream), "jpeg_huff")
+
     def preprocess(self, in_ptr, out_ptr, npix, mean, std, stream):
         m = (ctypes.c_float * 3)(*mean)
         s = (ctypes.c_float * 3)(*std)
@@ -864,6 +883,49 @@ class Jpeg:
         lib.rnb_jpeg_decode_frames.argtypes = [vp, ll, vp, vp, ctypes.c_int, vp, ll,
                                                ctypes.c_int]
         lib.rnb_jpeg_decode_frames.restype = ctypes.c_int
+        lib.rnb_jpeg_pack_scans.argtypes = [vp, ll, vp, vp, ctypes.c_int, vp, ll, vp,
+                                            ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_int)]
+        lib.rnb_jpeg_pack_scans.restype = ll
+        lib.rnb_jpeg_decode_scans_host.argtypes = [vp, ll, vp, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_int, vp, ll, ll, vp]
+        lib.rnb_jpeg_decode_scans_host.restype = ctypes.c_int
+
+    def pack_scans(self, buf, offsets, lengths, out, width=0, height=0):
+        """Pack the scans of the frames at ``offsets`` / ``lengths`` of ``buf``
+        into scan records in the flat uint8 array ``out`` (16-byte aligned).
+        Returns (bytes written, int64 offsets [n + 1]) or, on a refusal,
+        (negative code, index of the frame it is in)."""
+        import numpy as np
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        lens = np.ascontiguousarray(lengths, dtype=np.int64)
+        n = int(offs.size)
+        if lens.size != n or not out.flags.c_contiguous or not buf.flags.c_contiguous \
+                or out.dtype != np.uint8:
+            raise ValueError("jpeg pack_scans: table / output arrays do not fit")
+        scan_offs = np.zeros(n + 1, dtype=np.int64)
+        info = (ctypes.c_int * 3)()
+        rc = int(self.lib.rnb_jpeg_pack_scans(buf.ctypes.data, buf.size, offs.ctypes.data,
+                                              lens.ctypes.data, n, out.ctypes.data, out.size,
+                                              scan_offs.ctypes.data, int(width), int(height),
+                                              info))
+        if rc < 0:
+            return rc, int(info[2])
+        return rc, scan_offs
+
+    def decode_scans_host(self, scans, scan_offs, nframes, mw, mh, out, record_bytes, status):
+        """The interval decoder on the CPU (what ``jpeg_huff_kernel`` computes):
+        returns 0 or the negative buffer-level refusal; ``status`` (int32
+        [nframes]) receives each frame's code."""
+        import numpy as np
+        offs = np.ascontiguousarray(scan_offs, dtype=np.int64)
+        if offs.size < nframes + 1 or status.dtype != np.int32 or status.size < nframes \
+                or not (scans.flags.c_contiguous and out.flags.c_contiguous
+                        and status.flags.c_contiguous):
+            raise ValueError("jpeg decode_scans_host: table / output arrays do not fit")
+        return int(self.lib.rnb_jpeg_decode_scans_host(
+            scans.ctypes.data, scans.size, offs.ctypes.data, int(nframes), int(mw), int(mh),
+            out.ctypes.data, out.size, int(record_bytes), status.ctypes.data))
 
     def error_name(self, code: int) -> str:
         return self.lib.rnb_jpeg_error_name(int(code)).decode()

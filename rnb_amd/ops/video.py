@@ -366,6 +366,71 @@ def jpeg_idct(records: torch.Tensor, nframes: int, mw: int, mh: int,
     return res
 
 
+def jpeg_huff(scans: torch.Tensor, scan_offs, nframes: int, mw: int, mh: int,
+              out: Optional[torch.Tensor] = None, record_bytes: Optional[int] = None,
+              status: Optional[torch.Tensor] = None,
+              offs_dev: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Huffman-decode ``nframes`` packed scan records (``utils/mjpeg.py:
+    pack_scans``; flat uint8 tensor ``scans``, record ``i`` at
+    ``scan_offs[i] : scan_offs[i + 1]``, ``scan_offs`` a host table of
+    ``nframes + 1`` int64 offsets) into frame records ``record_bytes`` apart
+    (default ``384 + 768 mw mh``). Returns ``(records, status)``: the leading
+    ``nframes`` records of ``out`` (a flat uint8 tensor, allocated if not
+    given) and an int32 tensor with 0 or the code of each frame's
+    lowest-numbered failing interval (``mjpeg.status_field``); a frame or an
+    interval that fails has zero blocks. Every block is written.
+
+    On the GPU one ``jpeg_huff_kernel`` launch, one workgroup per frame and one
+    lane per restart interval, asynchronous: ``status`` is read by whoever
+    synchronises. ``offs_dev``: the offset table on the device (int64, e.g. a
+    view of the upload); uploaded here when not given. The launcher refuses
+    (``RuntimeError``) without launching when a record would reach outside its
+    buffer or is misaligned. On the CPU ``rnb_jpeg_decode_scans_host``, the
+    same decode loop."""
+    import numpy as np
+    n = mw * mh
+    rb = 384 + 768 * n if record_bytes is None else int(record_bytes)
+    offs = np.ascontiguousarray(scan_offs.numpy() if isinstance(scan_offs, torch.Tensor)
+                                else scan_offs, dtype=np.int64)
+    if offs.ndim != 1 or offs.size != nframes + 1:
+        raise ValueError("jpeg_huff: scan_offs must hold nframes + 1 = %d offsets" % (nframes + 1))
+    if scans.dtype != torch.uint8 or scans.dim() != 1 or not scans.is_contiguous():
+        raise ValueError("jpeg_huff: scans must be a flat contiguous uint8 tensor")
+    if out is not None and (out.dtype != torch.uint8 or out.dim() != 1
+                            or not out.is_contiguous() or out.device != scans.device):
+        raise ValueError("jpeg_huff: out must be a flat contiguous uint8 tensor on %s"
+                         % (scans.device,))
+    if status is not None and (status.dtype != torch.int32 or status.dim() != 1
+                               or not status.is_contiguous() or status.device != scans.device
+                               or status.numel() < nframes):
+        raise ValueError("jpeg_huff: status must be a contiguous int32 tensor of >= %d on %s"
+                         % (nframes, scans.device))
+    if out is None:
+        out = torch.empty(nframes * rb, dtype=torch.uint8, device=scans.device)
+    if status is None:
+        status = torch.zeros(nframes, dtype=torch.int32, device=scans.device)
+    if scans.is_cuda:
+        from .native import kernels
+        if offs_dev is None:
+            offs_dev = torch.from_numpy(offs).to(scans.device)
+        elif offs_dev.dtype != torch.int64 or offs_dev.device != scans.device \
+                or not offs_dev.is_contiguous() or offs_dev.numel() < nframes + 1:
+            raise ValueError("jpeg_huff: offs_dev must be >= %d contiguous int64 on %s"
+                             % (nframes + 1, scans.device))
+        kernels().jpeg_huff(scans.data_ptr(), scans.numel(), offs, offs_dev.data_ptr(), nframes,
+                            mw, mh, out.data_ptr(), out.numel(), rb, status.data_ptr(),
+                            torch.cuda.current_stream(scans.device).cuda_stream)
+        return out[:nframes * rb], status[:nframes]
+    from ..utils import mjpeg
+    try:
+        mjpeg.decode_scans_host(scans.numpy(), offs, nframes, mw, mh, out.numpy(), rb,
+                                status.numpy())
+    except mjpeg.JpegError:
+        raise ValueError("jpeg_huff: a scan record or a frame record lies outside its buffer, "
+                         "or is misaligned")
+    return out[:nframes * rb], status[:nframes]
+
+
 def preprocess(frames_u8: torch.Tensor, mean=KINETICS_MEAN, std=KINETICS_STD,
                out: Optional[torch.Tensor] = None, packed: bool = False,
                dtype=torch.bfloat16) -> torch.Tensor:

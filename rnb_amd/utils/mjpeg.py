@@ -20,6 +20,12 @@ component, natural order), then ``int16`` quantised coefficients, 64 per block
 in natural order: the Y blocks row-major over the padded ``2 mh x 2 mw`` grid,
 then the ``mh x mw`` Cb blocks, then Cr (``mw = ceil(W / 16)``, ``mh =
 ceil(H / 16)``): ``384 + 768 mw mh`` bytes.
+
+``pack_scans`` / ``decode_scans_host`` serve ``MjpegDecoder(entropy="gpu")``:
+the first packs frames' entropy-coded scans into *scan records* (tables, the
+byte span of every restart interval, the scan verbatim; layout in
+``csrc/jpeg_huff.h``), the second is the host mirror of ``jpeg_huff_kernel``,
+which decodes them into frame records, one restart interval per lane.
 """
 from __future__ import annotations
 
@@ -90,6 +96,7 @@ _REASONS = {
     "record": "the record is too small for the frame",
     "dc_range": "DC value outside the 16-bit range",
     "dimensions": "zero width or height",
+    "scan record": "malformed scan record (header, span table or extent)",
 }
 
 
@@ -190,6 +197,80 @@ def entropy_decode(data, offsets, lengths, out: np.ndarray, record_bytes: int,
             raise ValueError("%s: a sampled frame is not read (field 'record': %s)"
                              % (name, _REASONS["record"]))
         out[i * record_bytes:i * record_bytes + rec.size] = rec
+
+
+# scan records (the upload format of ``MjpegDecoder(entropy="gpu")``; layout in
+# csrc/jpeg_huff.h): 2032 fixed bytes (tables and header), 8 per restart
+# interval, then the scan's bytes, padded to 16
+SCAN_RECORD_FIXED = 2032
+
+
+def scan_record_bound(mw: int, mh: int, frame_len: int) -> int:
+    """An upper bound of the scan record of a ``frame_len``-byte frame."""
+    return (SCAN_RECORD_FIXED + 8 * mw * mh + int(frame_len) + 15) & ~15
+
+
+def _need_native(what: str):
+    lib = _native()
+    if lib is None:
+        raise RuntimeError("%s needs librnb_jpeg.so (python -m rnb_amd.build)" % what)
+    return lib
+
+
+def pack_scans(data, offsets, lengths, out: np.ndarray, width: int = 0, height: int = 0,
+               name: str = "<mjpeg>", frame0: int = 0) -> Tuple[int, np.ndarray]:
+    """Pack the scans of the frames at ``offsets`` / ``lengths`` of ``data``
+    into scan records in the flat, 16-byte aligned uint8 array ``out``
+    (``rnb_jpeg_pack_scans``: header parse, restart markers located, counted and
+    checked, no Huffman work). ``width`` / ``height``: the size every frame must
+    have (0: the first frame's). Returns (bytes written, int64 offsets
+    [n + 1] of the records in ``out``). A refusal raises ``JpegError`` naming
+    ``name``, the frame (``frame0`` + its index) and the field."""
+    lib = _need_native("pack_scans")
+    got, extra = lib.pack_scans(_as_u8(data), offsets, lengths, out, width, height)
+    if got < 0:
+        field = lib.error_name(got)
+        raise JpegError(field, "%s: frame %d is not read (field '%s': %s)"
+                        % (name, frame0 + extra, field, _REASONS.get(field, field)))
+    return got, extra
+
+
+def decode_scans_host(scans: np.ndarray, scan_offs, nframes: int, mw: int, mh: int,
+                      out: Optional[np.ndarray] = None, record_bytes: Optional[int] = None,
+                      status: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The GPU interval decoder's host mirror (``rnb_jpeg_decode_scans_host``):
+    ``nframes`` scan records -> (frame records ``record_bytes`` apart in a flat
+    uint8 array, int32 status per frame: 0 or the code of the frame's
+    lowest-numbered failing interval; see ``status_field``). A buffer, offset
+    or alignment that is refused raises ``JpegError`` (field 'argument')."""
+    lib = _need_native("decode_scans_host")
+    rb = 384 + 768 * mw * mh if record_bytes is None else int(record_bytes)
+    if out is None:
+        out = np.empty(nframes * rb, dtype=np.uint8)
+    if status is None:
+        status = np.zeros(nframes, dtype=np.int32)
+    rc = lib.decode_scans_host(scans, scan_offs, nframes, mw, mh, out, rb, status)
+    if rc:
+        field = lib.error_name(rc)
+        raise JpegError(field, "decode_scans_host: %s (field '%s')"
+                        % (_REASONS.get(field, field), field))
+    return out, status
+
+
+def status_field(code: int) -> str:
+    """The field name of a per-frame status code of the interval decoders."""
+    return _need_native("status_field").error_name(int(code))
+
+
+def raise_for_status(status, name: str, frames) -> None:
+    """Raise ``JpegError`` for the first non-zero code in ``status``;
+    ``frames[i]`` is the frame number status ``i`` belongs to."""
+    bad = np.nonzero(np.asarray(status))[0]
+    if bad.size:
+        i = int(bad[0])
+        field = status_field(int(status[i]))
+        raise JpegError(field, "%s: frame %d is not read (field '%s': %s)"
+                        % (name, int(frames[i]), field, _REASONS.get(field, field)))
 
 
 def pack_record(coefs: np.ndarray, qt: np.ndarray) -> np.ndarray:

@@ -8,9 +8,19 @@
     stream written to a temporary directory (smooth synthetic frames with a
     little noise, quality 75; the entropy decode's cost grows with the bit
     rate) and read once before: time of the call itself, and of the call plus
-    a device synchronise; and the host entropy decode alone.
+    a device synchronise; and the host entropy decode alone; then the
+    sustained rate of ``--sustained`` requests back to back with one final
+    synchronise, which counts kernels that outlast the host call;
+  * ``--entropy gpu`` adds, in the same session: ``jpeg_huff_kernel`` on the
+    request's 120 packed scan records (back-to-back launches, device events),
+    the scan packer alone, and the same host and sustained figures for
+    ``MjpegDecoder(entropy="gpu")``, with the bytes each path uploads.
+    ``--restart-interval N`` writes the stream with a restart marker every N
+    MCUs (22: one MCU row at 340x256, 16 intervals, i.e. GPU lanes, per frame;
+    0: none, one lane per frame).
 
     python scripts/mjpeg_decode_bench.py --out profiles/mjpeg_decode.txt
+    python scripts/mjpeg_decode_bench.py --entropy gpu --restart-interval 22
 """
 import argparse
 import os
@@ -43,9 +53,60 @@ def event_ms(fn, reps):
     return a.elapsed_time(b) / reps
 
 
-def encode(quality):
+def encode(quality, restart=0):
     q = mjpeg.quality_tables(quality)
-    return [mjpeg.encode_frame(*f, q) for f in synthetic_frames(3, DISTINCT, W, H)]
+    return [mjpeg.encode_frame(*f, q, restart) for f in synthetic_frames(3, DISTINCT, W, H)]
+
+
+def huff_kernel(dev, encoded, reps, rounds, lines):
+    """jpeg_huff_kernel on one request's scan records, alternating with the
+    IDCT kernel it feeds."""
+    mw, mh, rb = mjpeg.geometry(W, H)
+    n = CLIPS * F
+    frames = [encoded[i % DISTINCT][0] for i in range(n)]
+    lens = np.array([len(f) for f in frames], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    data = np.frombuffer(b"".join(frames), dtype=np.uint8)
+    buf = np.zeros(sum(mjpeg.scan_record_bound(mw, mh, x) for x in lens), dtype=np.uint8)
+    size, scan_offs = mjpeg.pack_scans(data, offs, lens, buf)
+    scans = torch.from_numpy(buf[:size]).to(dev)
+    offs_dev = torch.from_numpy(scan_offs).to(dev)
+    rec = torch.empty(n * rb, dtype=torch.uint8, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    surf = torch.empty(n * 384 * mw * mh, dtype=torch.uint8, device=dev)
+
+    def huff():
+        vops.jpeg_huff(scans, scan_offs, n, mw, mh, out=rec, status=status, offs_dev=offs_dev)
+
+    def idct():
+        vops.jpeg_idct(rec, n, mw, mh, out=surf)
+    reps = max(10, reps // 10)                            # a millisecond-scale kernel
+    fns = (("jpeg_huff_kernel", huff), ("jpeg_idct_kernel", idct))
+    for _, fn in fns:
+        event_ms(fn, reps)
+    assert int(status.abs().sum()) == 0
+    want = np.empty(n * rb, dtype=np.uint8)
+    mjpeg.entropy_decode(data, offs, lens, want, rb, 4)
+    assert (rec.cpu().numpy() == want).all()              # what is timed is the right answer
+    times = {name: [] for name, _ in fns}
+    for _ in range(rounds):
+        for name, fn in fns:
+            times[name].append(event_ms(fn, reps))
+    intervals = int(buf[2016:2020].view(np.uint32)[0])
+    for name, _ in fns:
+        t = times[name]
+        lines.append("%-26s median %.1f us/launch (min %.1f, max %.1f over %d rounds of %d)"
+                     % (name, statistics.median(t) * 1e3, min(t) * 1e3, max(t) * 1e3, rounds, reps))
+    lines.append("jpeg_huff_kernel: %d workgroups of 64 lanes, %d intervals (busy lanes) per frame; "
+                 "%d bytes of scan records in, %d bytes of frame records out"
+                 % (n, intervals, size, n * rb))
+    t = []
+    for _ in range(20):
+        t0 = time.perf_counter()
+        mjpeg.pack_scans(data, offs, lens, buf)
+        t.append((time.perf_counter() - t0) * 1e3)
+    lines.append("scan packer alone: median %.3f ms per %d frames (min %.3f), one thread"
+                 % (statistics.median(t), n, min(t)))
 
 
 def kernels(dev, dtype, encoded, reps, rounds, lines):
@@ -95,7 +156,45 @@ def kernels(dev, dtype, encoded, reps, rounds, lines):
                  % (rec.numel(), n, rb, surf.numel(), n * W * H * 3 // 2))
 
 
-def host(dev, dtype, encoded, reqs, lines):
+def decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines, label, **kw):
+    """Host time of decode, and the sustained rate with one final synchronise."""
+    dec = MjpegDecoder(dev, dtype=dtype, **kw)
+    vid, _ = dec.probe(path)
+    for _ in range(5):
+        dec.decode(vid, starts, out=out)
+    torch.cuda.synchronize()
+    call, total = [], []
+    for _ in range(reqs):
+        t0 = time.perf_counter()
+        dec.decode(vid, starts, out=out)
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        call.append((t1 - t0) * 1e3)
+        total.append((t2 - t0) * 1e3)
+    med = statistics.median(call)
+    lines.append("MjpegDecoder.decode %-16s %s: host call median %.3f ms (min %.3f, "
+                 "max %.3f), call + sync median %.3f ms, %d requests of %d clips: "
+                 "%.0f videos/s from one loader process"
+                 % (label, str(dtype).split(".")[1], med, min(call), max(call),
+                    statistics.median(total), reqs, CLIPS, 1e3 / med))
+    rates = []
+    for _ in range(3):
+        before = dict(dec.stats)
+        t0 = time.perf_counter()
+        for _ in range(sustained):
+            dec.decode(vid, starts, out=out)
+        torch.cuda.synchronize()
+        rates.append(sustained / (time.perf_counter() - t0))
+    dec.drain()
+    up = (dec.stats["uploaded_bytes"] - before["uploaded_bytes"]) // sustained
+    lines.append("MjpegDecoder.decode %-16s sustained: %.0f requests/s (min %.0f, max %.0f over 3 "
+                 "runs of %d back-to-back requests, one final synchronise); %d bytes uploaded "
+                 "per request" % (label, statistics.median(rates), min(rates), max(rates),
+                                  sustained, up))
+
+
+def host(dev, dtype, encoded, reqs, lines, sustained=60, entropy="host", restart=0):
     frames = 300
     starts = [20 * c for c in range(CLIPS)]
     with tempfile.TemporaryDirectory() as d:
@@ -104,8 +203,9 @@ def host(dev, dtype, encoded, reqs, lines):
             for i in range(frames):
                 fp.write(encoded[i % DISTINCT][0])
         size = os.path.getsize(path)
-        lines.append("stream: %d frames, %.1f KB per frame (raw 4:2:0: %.1f KB), quality 75"
-                     % (frames, size / frames / 1e3, W * H * 1.5 / 1e3))
+        lines.append("stream: %d frames, %.1f KB per frame (raw 4:2:0: %.1f KB), quality 75, "
+                     "restart interval %d"
+                     % (frames, size / frames / 1e3, W * H * 1.5 / 1e3, restart))
         data = np.fromfile(path, dtype=np.uint8)
         idx = mjpeg.read_index(path, data=data)
         sel = np.concatenate([np.arange(s, s + F) for s in starts])
@@ -121,26 +221,11 @@ def host(dev, dtype, encoded, reqs, lines):
                 t.append((time.perf_counter() - t0) * 1e3)
             lines.append("entropy decode alone, %2d threads: median %.2f ms per %d frames "
                          "(min %.2f)" % (threads, statistics.median(t), len(sel), min(t)))
-            dec = MjpegDecoder(dev, dtype=dtype, threads=threads)
-            vid, _ = dec.probe(path)
-            for _ in range(5):
-                dec.decode(vid, starts, out=out)
-            torch.cuda.synchronize()
-            call, total = [], []
-            for _ in range(reqs):
-                t0 = time.perf_counter()
-                dec.decode(vid, starts, out=out)
-                t1 = time.perf_counter()
-                torch.cuda.synchronize()
-                t2 = time.perf_counter()
-                call.append((t1 - t0) * 1e3)
-                total.append((t2 - t0) * 1e3)
-            med = statistics.median(call)
-            lines.append("MjpegDecoder.decode threads=%-2d %s: host call median %.3f ms (min %.3f, "
-                         "max %.3f), call + sync median %.3f ms, %d requests of %d clips: "
-                         "%.0f videos/s from one loader process"
-                         % (threads, str(dtype).split(".")[1], med, min(call), max(call),
-                            statistics.median(total), reqs, CLIPS, 1e3 / med))
+            decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines,
+                         "threads=%d" % threads, threads=threads)
+        if entropy == "gpu":
+            decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines, "entropy=gpu",
+                         entropy="gpu")
 
 
 def main():
@@ -148,6 +233,11 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--requests", type=int, default=40)
+    ap.add_argument("--sustained", type=int, default=60,
+                    help="back-to-back requests per sustained-rate run")
+    ap.add_argument("--entropy", choices=("host", "gpu"), default="host",
+                    help="gpu: also measure jpeg_huff_kernel and MjpegDecoder(entropy='gpu')")
+    ap.add_argument("--restart-interval", type=int, default=0, help="in MCUs; 0: none")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -155,10 +245,13 @@ def main():
     dev = torch.device("cuda:0")
     lines = ["mjpeg decode path, per 15-clip request at %dx%d -> 112x112 (%s)"
              % (W, H, torch.cuda.get_device_name(0))]
-    encoded = encode(75)
+    encoded = encode(75, args.restart_interval)
     for dtype in (torch.float32, torch.bfloat16):
         kernels(dev, dtype, encoded, args.reps, args.rounds, lines)
-    host(dev, torch.float32, encoded, args.requests, lines)
+    if args.entropy == "gpu":
+        huff_kernel(dev, encoded, args.reps, args.rounds, lines)
+    host(dev, torch.float32, encoded, args.requests, lines, args.sustained, args.entropy,
+         args.restart_interval)
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if args.out:
