@@ -473,4 +473,146 @@ int rnb_jpeg_decode_scans_host(const uint8_t* scans, long long scans_len,
   return E_OK;
 }
 
+// The host emulation of jpeg_huff_subseq_kernel: as rnb_jpeg_decode_scans_host,
+// but a frame whose scan is one interval of more than one subsequence of
+// subseq_bytes (a multiple of 16 in 16..4096; see subseq_plan) is decoded by
+// synchronised subsequences, with the header functions the kernel runs, pass
+// by pass, as loops over the subsequences. Records and status equal
+// rnb_jpeg_decode_scans_host's byte for byte; rounds[i] receives the number of
+// synchronisation rounds frame i took (0 for every other frame).
+int rnb_jpeg_decode_scans_subseq_host(const uint8_t* scans, long long scans_len,
+                                      const long long* scan_offs, int nframes, int mw, int mh,
+                                      uint8_t* out, long long out_len, long long record_bytes,
+                                      int* status, int subseq_bytes, int* rounds) {
+  if (!rounds || !subseq_bytes_ok(subseq_bytes)) return E_ARG;
+  if (nframes == 0) return E_OK;
+  if (!scans || !scan_offs || !out || !status || nframes < 0 || mw < 1 || mh < 1 || mw > 4096 ||
+      mh > 4096 || scans_len < 0 || out_len < 0)
+    return E_ARG;
+  const long long nmcu = (long long)mw * mh;
+  if (((uintptr_t)out & 15u) != 0 || record_bytes % 16 != 0 || record_bytes < 384 + 768 * nmcu ||
+      record_bytes > out_len / nframes)
+    return E_ARG;
+  if (scan_offs[0] < 0 || scan_offs[nframes] > scans_len) return E_ARG;
+  for (int i = 0; i < nframes; ++i)
+    if (scan_offs[i] % 16 != 0 || scan_offs[i + 1] - scan_offs[i] < SR_SPANS + 8) return E_ARG;
+  std::vector<Huff> tabs(6);
+  std::vector<uint32_t> bits, entry, blocks;
+  std::vector<SubseqExit> exits;
+  std::vector<int> pred;
+  std::vector<char> dirty;
+  for (int i = 0; i < nframes; ++i) {
+    const uint8_t* rec = scans + scan_offs[i];
+    uint8_t* dst = out + (long long)i * record_bytes;
+    int16_t* coef = (int16_t*)(dst + 384);
+    ScanHeader h;
+    int rc = scan_record_check(rec, scan_offs[i + 1] - scan_offs[i], nmcu, h);
+    memcpy(dst, rec, 384);
+    rounds[i] = 0;
+    for (int k = 0; k < 6 && !rc; ++k) {
+      const uint8_t* tb = rec + SR_HUFF + SR_TABLE * k;
+      int total = 0;
+      for (int l = 0; l < 16; ++l) total += tb[l];
+      tabs[(size_t)k].set = 0;
+      rc = build_huff(tb, tb + 16, total, tabs[(size_t)k]);
+    }
+    if (rc) {
+      memset(coef, 0, (size_t)(768 * nmcu));
+      status[i] = rc;
+      continue;
+    }
+    status[i] = E_OK;
+    SubseqPlan pl;
+    if (!subseq_plan(rec, h, subseq_bytes, pl)) {
+      Tables t;
+      for (int c = 0; c < 3; ++c) {
+        t.dc[c] = &tabs[(size_t)(2 * c)];
+        t.ac[c] = &tabs[(size_t)(2 * c + 1)];
+      }
+      for (long long v = 0; v < (long long)h.n_intervals; ++v) {
+        rc = decode_record_interval(rec, h, v, t, mw, nmcu, coef);
+        if (rc && !status[i]) status[i] = rc;
+      }
+      continue;
+    }
+    const uint8_t* scan = rec + SR_SPANS + 8;
+    memset(coef, 0, (size_t)(768 * nmcu));
+    // pre-pass: data bytes per subsequence; the first marker ends the span
+    bits.assign((size_t)pl.n_sub + 1, 0u);
+    long long end = pl.end;
+    for (int s = 0; s < pl.n_sub; ++s) {
+      const long long b0 = pl.begin + s * pl.S;
+      const long long at = subseq_count(scan, pl.begin, pl.end, b0,
+                                        b0 + pl.S < pl.end ? b0 + pl.S : pl.end, bits[(size_t)s]);
+      if (at < end) end = at;
+    }
+    const int n_sub = end > pl.begin ? (int)((end - pl.begin + pl.S - 1) / pl.S) : 1;
+    auto start = [&](int s) { return subseq_start(scan, pl.begin, pl.begin + s * pl.S); };
+    // guess pass
+    entry.assign((size_t)n_sub, 0u);
+    exits.resize((size_t)n_sub);
+    for (int s = 0; s < n_sub; ++s)
+      subseq_scan(scan, start(s), end, (int)(8 * bits[(size_t)s]), tabs.data(), 0u,
+                  exits[(size_t)s]);
+    // synchronisation rounds
+    dirty.assign((size_t)n_sub, 0);
+    for (int r = 0; r < n_sub - 1; ++r) {
+      bool changed = false;
+      for (int s = 1; s < n_sub; ++s) {
+        dirty[(size_t)s] = exits[(size_t)s - 1].state != entry[(size_t)s];
+        if (dirty[(size_t)s]) {
+          entry[(size_t)s] = exits[(size_t)s - 1].state;
+          changed = true;
+        }
+      }
+      if (!changed) break;
+      ++rounds[i];
+      for (int s = 1; s < n_sub; ++s)
+        if (dirty[(size_t)s])
+          subseq_scan(scan, start(s), end, (int)(8 * bits[(size_t)s]), tabs.data(),
+                      entry[(size_t)s], exits[(size_t)s]);
+    }
+    // prefix sums: boundary bit positions, block indices, predictors
+    blocks.assign((size_t)n_sub, 0u);
+    pred.assign(3 * (size_t)n_sub, 0);
+    {
+      uint32_t at = 0;
+      unsigned long long g = 0;
+      long long d0 = 0, d1 = 0, d2 = 0;
+      for (int s = 0; s < n_sub; ++s) {
+        const uint32_t nb = 8 * bits[(size_t)s];
+        bits[(size_t)s] = at;
+        at += nb;
+        blocks[(size_t)s] = (uint32_t)g;
+        g += exits[(size_t)s].blocks;
+        pred[3 * (size_t)s] = subseq_clamp_pred(d0);
+        pred[3 * (size_t)s + 1] = subseq_clamp_pred(d1);
+        pred[3 * (size_t)s + 2] = subseq_clamp_pred(d2);
+        d0 += exits[(size_t)s].dc0;
+        d1 += exits[(size_t)s].dc1;
+        d2 += exits[(size_t)s].dc2;
+        if (s + 1 < n_sub && ((entry[(size_t)s + 1] >> 6) & 7) != g % 6) return E_ARG;
+      }
+      bits[(size_t)n_sub] = at;
+    }
+    // write pass; the lowest subsequence that fails holds the first error
+    long long bad_block = 6 * nmcu;
+    for (int s = 0; s < n_sub; ++s) {
+      if ((long long)blocks[(size_t)s] >= 6 * nmcu) break;
+      rc = subseq_write(scan, start(s), end, (int)(bits[(size_t)s + 1] - bits[(size_t)s]),
+                        s == n_sub - 1, (long long)bits[(size_t)n_sub] - bits[(size_t)s],
+                        tabs.data(), entry[(size_t)s], blocks[(size_t)s], pred[3 * (size_t)s],
+                        pred[3 * (size_t)s + 1], pred[3 * (size_t)s + 2], mw, nmcu, coef,
+                        bad_block);
+      if (rc) {
+        status[i] = rc;
+        break;
+      }
+    }
+    for (long long g = bad_block; g < 6 * nmcu; ++g)
+      zero_block(mcu_block(coef, g / 6, (int)(g % 6), mw, nmcu));
+  }
+  return E_OK;
+}
+
 }  // extern "C"

@@ -352,4 +352,308 @@ RNB_HD inline int decode_record_interval(const uint8_t* rec, const ScanHeader& h
   return E_OK;
 }
 
+// ---------------------------------------------------------------------------
+// One interval decoded by synchronised subsequences (jpeg_huff_subseq_kernel
+// and its host emulation rnb_jpeg_decode_scans_subseq_host run these
+// functions pass by pass; the result equals decode_record_interval's byte for
+// byte).
+//
+// The span [begin, end) is cut into subsequences of S raw bytes; a symbol
+// belongs to the subsequence its first bit lies in. Positions are counted in
+// DE-STUFFED bits: the raw bytes parse without context into data bytes (any
+// byte but FF; FF 00, which starts at its FF), fill bytes (FF in front of FF)
+// and a marker (FF in front of anything else, or as the span's last byte),
+// because a 00 behind an FF is always the second byte of a pair. subseq_count
+// counts the data bytes that start in a subsequence, so a prefix sum gives
+// every boundary's bit position, and the first marker found anywhere ends the
+// span for every reader, as it does for the serial one. The decoder's state
+// between two symbols is (bit position, block in MCU j, coefficient index k;
+// k = 0: DC next), kept relative to the subsequence's boundary: a symbol is at
+// most 31 bits, so a state packs into 15 bits whatever the span's length.
+//
+// Passes: every subsequence is scanned (no coefficient written) from the
+// guess (boundary, 0, 0); then each takes its left neighbour's exit state as
+// its entry and is scanned again while any entry changes. Subsequence 0 starts
+// at the truth, so after round r the first r + 1 are true and at most
+// n_sub - 1 rounds run. Prefix sums of the blocks completed and of the DC
+// differences per component give each entry's block index and predictors, and
+// the write pass decodes every subsequence from its true entry into a frame
+// whose coefficients were zeroed before: a block may begin in one subsequence
+// and end in the next, so only non-zero coefficients are stored.
+//
+// A scan from a wrong guess meets invalid data at once. It must not stop
+// there, or the error state is handed down the chain and nothing ever
+// synchronises; subseq_scan recovers by one fixed rule: a code that matches
+// no entry skips one bit, a DC category above 11 reads no bits, a run or ZRL
+// past coefficient 63 ends the block. On the true chain no recovery happens in
+// front of the first real error, which the write pass reports, and everything
+// from the failing block on is zeroed, so the result does not depend on the
+// rule.
+// ---------------------------------------------------------------------------
+constexpr int SUBSEQ_CAP = 1024;                     // subsequences per span at most
+constexpr long long SUBSEQ_MAX_SPAN = 1LL << 28;     // bit positions and block counts fit 32 bits
+
+RNB_HD inline bool subseq_bytes_ok(long long s) { return s >= 16 && s <= 4096 && s % 16 == 0; }
+
+// the subsequence size used for a span of len bytes: S, raised so that at most
+// SUBSEQ_CAP subsequences cover it
+RNB_HD inline long long subseq_effective(long long S, long long len) {
+  if ((len + S - 1) / S <= SUBSEQ_CAP) return S;
+  return ((len + SUBSEQ_CAP - 1) / SUBSEQ_CAP + 15) & ~15LL;
+}
+
+struct SubseqPlan {
+  long long begin, end, S;
+  int n_sub;
+};
+
+// Whether the checked record's frame takes the subsequence path, and how: one
+// interval whose span decode_record_interval would accept, short enough for
+// 32-bit bit positions, and longer than one subsequence. Everything else is
+// decoded as before, one interval per lane.
+RNB_HD inline bool subseq_plan(const uint8_t* rec, const ScanHeader& h, int subseq_bytes,
+                               SubseqPlan& pl) {
+  pl.begin = pl.end = 0;
+  pl.S = subseq_bytes;
+  pl.n_sub = 1;
+  if (h.n_intervals != 1 || !subseq_bytes_ok(subseq_bytes)) return false;
+  pl.begin = load_u32(rec + SR_SPANS);
+  pl.end = load_u32(rec + SR_SPANS + 4);
+  if (pl.begin > pl.end || pl.end > (long long)h.scan_len) return false;
+  const long long len = pl.end - pl.begin;
+  if (len > SUBSEQ_MAX_SPAN) return false;
+  pl.S = subseq_effective(subseq_bytes, len);
+  const long long n = (len + pl.S - 1) / pl.S;
+  if (n < 2) return false;
+  pl.n_sub = (int)n;
+  return true;
+}
+
+// The data bytes that start in p[b0 .. b1) of the span [begin, end), up to the
+// first marker there. Returns the marker's position, or `end` without one.
+// Reads p[b0 - 1] (when b0 > begin) and p[r + 1] behind an FF at r (when
+// r + 1 < end): nothing outside the span.
+RNB_HD inline long long subseq_count(const uint8_t* p, long long begin, long long end,
+                                     long long b0, long long b1, uint32_t& count) {
+  unsigned prev = b0 > begin ? p[b0 - 1] : 0u;
+  uint32_t n = 0;
+  long long at = end;
+  for (long long r = b0; r < b1; ++r) {
+    const unsigned c = p[r];
+    if (c == 0xFF) {
+      const unsigned nx = r + 1 < end ? p[r + 1] : 0xD9u;
+      if (nx == 0x00) {
+        ++n;
+      } else if (nx != 0xFF) {
+        at = r;
+        break;
+      }
+    } else if (!(c == 0x00 && prev == 0xFF)) {
+      ++n;
+    }
+    prev = c;
+  }
+  count = n;
+  return at;
+}
+
+// where the reader of the subsequence at b0 starts: behind the 00 of a
+// stuffing pair that the boundary cuts (fill bytes the reader skips itself)
+RNB_HD inline long long subseq_start(const uint8_t* p, long long begin, long long b0) {
+  return b0 + ((b0 > begin && p[b0] == 0x00 && p[b0 - 1] == 0xFF) ? 1 : 0);
+}
+
+// state: (bits behind the boundary << 9) | (j << 6) | k
+RNB_HD inline uint32_t subseq_state(int off, int j, int k) {
+  return ((uint32_t)(off > 63 ? 63 : off) << 9) | ((uint32_t)j << 6) | (uint32_t)k;
+}
+
+// a reader at raw position `at`, `off` bits further
+RNB_HD inline void subseq_open(Bits& b, const uint8_t* p, long long at, long long end, int off) {
+  b.p = p;
+  b.pos = at;
+  b.end = end;
+  b.acc = 0; b.n = 0; b.fake = 0; b.marker = false;
+  while (off > 0) {
+    b.fill();
+    const int s = off < 32 ? off : 32;
+    b.skip(s);
+    off -= s;
+  }
+}
+
+struct SubseqExit {
+  uint32_t state;      // relative to the NEXT boundary
+  uint32_t blocks;     // blocks completed
+  int dc0, dc1, dc2;   // sum of the DC differences per component
+};
+
+// Scan the subsequence whose reader starts at `at` and which holds `limit`
+// de-stuffed bits, from `entry`: every symbol that starts in front of `limit`,
+// with the recovery rule above and without writing. Every iteration consumes
+// at least one bit and at most 31, so the loop runs at most `limit` times and
+// the exit state lies fewer than 31 bits behind the next boundary. tabs: the
+// six tables of the scan record (2c: DC, 2c + 1: AC of component c).
+RNB_HD inline void subseq_scan(const uint8_t* p, long long at, long long end, int limit,
+                               const Huff* tabs, uint32_t entry, SubseqExit& x) {
+  int j = (int)(entry >> 6) & 7, k = (int)(entry & 63);
+  int pos = (int)(entry >> 9);
+  Bits b;
+  subseq_open(b, p, at, end, pos);
+  uint32_t nb = 0;
+  int d0 = 0, d1 = 0, d2 = 0;
+  while (pos < limit) {
+    if (b.n < 32) b.fill();
+    const int n0 = b.n;
+    const int c = j < 4 ? 0 : j - 3;
+    bool done = false;
+    if (k == 0) {
+      const int s = decode_symbol(b, tabs[2 * c]);
+      if (s < 0) {
+        if (b.n == n0) b.skip(1);
+      } else {
+        if (s >= 1 && s <= 11) {
+          const int d = receive_extend(b, s);
+          if (c == 0) d0 += d; else if (c == 1) d1 += d; else d2 += d;
+        }
+        k = 1;
+      }
+    } else {
+      const int rs = decode_symbol(b, tabs[2 * c + 1]);
+      if (rs < 0) {
+        if (b.n == n0) b.skip(1);
+      } else {
+        const int r = rs >> 4, s = rs & 15;
+        if (s == 0) {
+          if (r != 15 || k + 15 > 63) {
+            done = true;
+          } else {
+            k += 16;
+            done = k > 63;
+          }
+        } else {
+          k += r;
+          if (k > 63) {
+            done = true;
+          } else {
+            b.skip(s);
+            ++k;
+            done = k > 63;
+          }
+        }
+      }
+    }
+    pos += n0 - b.n;
+    if (done) {
+      k = 0;
+      j = j == 5 ? 0 : j + 1;
+      ++nb;
+    }
+  }
+  x.state = subseq_state(pos - limit, j, k);
+  x.blocks = nb;
+  x.dc0 = d0; x.dc1 = d1; x.dc2 = d2;
+}
+
+// what a 64-bit prefix sum of DC differences is stored as: in front of the
+// first error every true predictor is inside int16, so the clamp changes no
+// value that counts, and a clamped one is out of range for whoever starts
+// from it
+RNB_HD inline int subseq_clamp_pred(long long v) {
+  return v < -(1 << 20) ? -(1 << 20) : v > (1 << 20) ? (1 << 20) : (int)v;
+}
+
+// The write pass of one subsequence: from its true entry state, global block
+// index g and predictors, decode every symbol that starts in front of `limit`
+// (`last`: no limit, the span's last subsequence goes on over the reader's zero
+// bits until its block ends, as the serial loop does) and store the non-zero
+// coefficients of blocks g < 6 nmcu; `rem` is the number of real bits from the
+// subsequence's boundary to the end of the span, for E_TRUNCATED. Stops at the
+// first error and returns its code, the block in bad_block: with decode_block's
+// checks in decode_block's order, so the lowest subsequence that reports one
+// reports the serial decoder's first error.
+RNB_HD inline int subseq_write(const uint8_t* p, long long at, long long end, int limit, bool last,
+                               long long rem, const Huff* tabs, uint32_t entry, long long g,
+                               int p0, int p1, int p2, long long mw, long long nmcu, int16_t* coef,
+                               long long& bad_block) {
+  const long long total = 6 * nmcu;
+  int k = (int)(entry & 63);
+  long long pos = (long long)(entry >> 9);
+  long long m = g / 6;
+  int j = (int)(g - 6 * m);
+  Bits b;
+  subseq_open(b, p, at, end, (int)pos);
+  while (g < total && (last || pos < limit)) {
+    int16_t* blk = mcu_block(coef, m, j, mw, nmcu);
+    const int c = j < 4 ? 0 : j - 3;
+    bool done = false;
+    while (!done && (last || pos < limit)) {
+      if (b.n < 32) b.fill();
+      const int n0 = b.n;
+      int rc = E_OK;
+      if (k == 0) {
+        const int s = decode_symbol(b, tabs[2 * c]);
+        if (s < 0) {
+          rc = s;
+        } else if (s > 11) {
+          rc = E_DC_RANGE;
+        } else {
+          int pred = c == 0 ? p0 : c == 1 ? p1 : p2;
+          if (s) pred += receive_extend(b, s);
+          if (pred < -32768 || pred > 32767) {
+            rc = E_DC_RANGE;
+          } else {
+            if (c == 0) p0 = pred; else if (c == 1) p1 = pred; else p2 = pred;
+            if (pred) blk[0] = (int16_t)pred;
+            k = 1;
+          }
+        }
+      } else {
+        const int rs = decode_symbol(b, tabs[2 * c + 1]);
+        if (rs < 0) {
+          rc = rs;
+        } else {
+          const int r = rs >> 4, s = rs & 15;
+          if (s == 0) {
+            if (r != 15) {
+              done = true;                       // EOB
+            } else if (k + 15 > 63) {
+              rc = E_RUN;
+            } else {
+              k += 16;
+              done = k > 63;
+            }
+          } else {
+            k += r;
+            if (k > 63) {
+              rc = E_RUN;
+            } else {
+              blk[zigzag(k)] = (int16_t)receive_extend(b, s);
+              ++k;
+              done = k > 63;
+            }
+          }
+        }
+      }
+      pos += n0 - b.n;
+      if (rc) {
+        bad_block = g;
+        return rc;
+      }
+    }
+    if (!done) break;                            // the boundary lies inside this block
+    if (pos > rem) {
+      bad_block = g;
+      return E_TRUNCATED;
+    }
+    k = 0;
+    ++g;
+    if (++j == 6) {
+      j = 0;
+      ++m;
+    }
+  }
+  return E_OK;
+}
+
 }  // namespace jpeg_huff

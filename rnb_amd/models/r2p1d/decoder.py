@@ -400,12 +400,22 @@ class MjpegDecoder(_StagedFileDecoder):
     zero coefficients. On a CPU device the same decode loop runs on the host
     and such a frame raises from ``decode``.
 
+    ``subseq_bytes`` (only with ``entropy="gpu"``; default ``SUBSEQ_BYTES``):
+    above 0, a multiple of 16 in 16..4096, the launch is
+    ``jpeg_huff_subseq_kernel``, which cuts the scan of a frame WITHOUT restart
+    markers into subsequences of that many bytes and decodes them on the lanes
+    of the frame's workgroup, synchronising their entry states
+    (``csrc/jpeg_huff.h``); records, status words and deferred errors are the
+    same. 0: one lane per restart interval, i.e. per frame of such a stream.
+
     ``stats``: ``requests`` served and ``uploaded_bytes`` staged for upload
     (records, or scan records and their offset table)."""
 
+    SUBSEQ_BYTES = 48          # entropy="gpu" without subseq_bytes: the measured best (profiles/NOTES.md)
+
     def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
                  width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full",
-                 threads: int = 4, entropy: str = "host"):
+                 threads: int = 4, entropy: str = "host", subseq_bytes: Optional[int] = None):
         if isinstance(threads, bool) or not isinstance(threads, int) or not 1 <= threads <= 16:
             raise ValueError("MjpegDecoder: threads must be an integer in 1..16, got %r"
                              % (threads,))
@@ -413,13 +423,21 @@ class MjpegDecoder(_StagedFileDecoder):
             raise ValueError("MjpegDecoder: ring depth must be an integer, got %r" % (depth,))
         if entropy not in ("host", "gpu"):
             raise ValueError("MjpegDecoder: entropy must be 'host' or 'gpu', got %r" % (entropy,))
+        if subseq_bytes is not None and entropy != "gpu":
+            raise ValueError("MjpegDecoder: subseq_bytes goes with entropy='gpu', not %r"
+                             % (entropy,))
+        if subseq_bytes is None:
+            subseq_bytes = self.SUBSEQ_BYTES if entropy == "gpu" else 0
+        subseq_bytes = mjpeg.check_subseq_bytes(subseq_bytes, "MjpegDecoder")
         super().__init__(device, clip_length, height, width, dtype, depth, crop)
         self.threads = threads
         self.entropy = entropy
+        self.subseq_bytes = subseq_bytes
         self.stats = {"requests": 0, "uploaded_bytes": 0}
         self._surface = None       # device I420 planes of the request being decoded
         self._records = None       # entropy="gpu": device frame records of that request
         self._status = None        # ... and the kernel's per-frame status words
+        self._rounds = None        # ... and, with subseq_bytes, its rounds per frame
         self._max_len = {}         # video id -> longest frame in bytes
 
     def probe(self, path):
@@ -590,12 +608,16 @@ class MjpegDecoder(_StagedFileDecoder):
                     buf[:pos], offs, nfr, idx.mw, idx.mh,
                     out=self._device_buffer("_records", cap * rb, torch.uint8),
                     status=self._device_buffer("_status", cap, torch.int32),
-                    offs_dev=buf[:8 * (nfr + 1)].view(torch.int64))
+                    offs_dev=buf[:8 * (nfr + 1)].view(torch.int64),
+                    subseq_bytes=self.subseq_bytes,
+                    rounds=self._device_buffer("_rounds", cap, torch.int32)
+                    if self.subseq_bytes else None)
                 entry.pinned[stat_at:stat_at + 4 * nfr].view(torch.int32).copy_(
                     status, non_blocking=True)
                 entry.pending = (path, frames, stat_at)
             else:
-                records, status = vops.jpeg_huff(buf[:pos], offs, nfr, idx.mw, idx.mh)
+                records, status = vops.jpeg_huff(buf[:pos], offs, nfr, idx.mw, idx.mh,
+                                                 subseq_bytes=self.subseq_bytes)
                 mjpeg.raise_for_status(status.numpy(), path, frames)
             out = self._out(n, out)
             self._to_clips(records, n, idx.width, idx.height, idx.mw, idx.mh,
@@ -610,7 +632,8 @@ class MjpegDecoder(_StagedFileDecoder):
 def make_decoder(backend: str, device: torch.device, clip_length=8, height=112, width=112,
                  dtype=torch.bfloat16, decoder_args: Optional[dict] = None) -> Decoder:
     """``decoder_args``: backend-specific constructor arguments (``y4m``:
-    ``depth``, ``crop``; ``mjpeg``: ``depth``, ``crop``, ``threads``, ``entropy``); the other
+    ``depth``, ``crop``; ``mjpeg``: ``depth``, ``crop``, ``threads``, ``entropy``,
+    ``subseq_bytes``); the other
     backends take none and ignore it."""
     if backend == "y4m":
         return Y4mDecoder(device, clip_length, height, width, dtype, **(decoder_args or {}))

@@ -227,6 +227,12 @@ class Kernels:
                                       ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong,
                                       ctypes.c_void_p, ctypes.c_void_p]
         lib.rnb_jpeg_huff.restype = ctypes.c_int
+        lib.rnb_jpeg_huff_subseq.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
+                                             ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_void_p]
+        lib.rnb_jpeg_huff_subseq.restype = ctypes.c_int
         lib.rnb_preprocess.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
                                        ctypes.POINTER(ctypes.c_float),
                                        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
@@ -845,6 +851,22 @@ class Kernels:
                                       nframes, mw, mh, rec_ptr, rec_len, record_bytes,
                                       status_ptr, stream), "jpeg_huff")
 
+    def jpeg_huff_subseq(self, scans_ptr, scans_len, offs_host, offs_dev_ptr, nframes, mw, mh,
+                         rec_ptr, rec_len, record_bytes, status_ptr, subseq_bytes, rounds_ptr,
+                         stream):
+        """As ``jpeg_huff`` through ``jpeg_huff_subseq_kernel``: one-interval
+        frames by synchronised subsequences of ``subseq_bytes`` scan bytes;
+        ``rounds_ptr``: ``nframes`` int32 on the device. The launcher also
+        refuses a ``subseq_bytes`` that is not a multiple of 16 in 16..4096."""
+        if offs_host.dtype.name != "int64" or not offs_host.flags.c_contiguous \
+                or offs_host.size < nframes + 1:
+            raise ValueError("jpeg_huff: scan_offs must be %d contiguous int64 offsets"
+                             % (nframes + 1))
+        _check(self.lib.rnb_jpeg_huff_subseq(scans_ptr, scans_len, offs_host.ctypes.data,
+                                             offs_dev_ptr, nframes, mw, mh, rec_ptr, rec_len,
+                                             record_bytes, status_ptr, int(subseq_bytes),
+                                             rounds_ptr, stream), "jpeg_huff_subseq")
+
     def preprocess(self, in_ptr, out_ptr, npix, mean, std, stream):
         m = (ctypes.c_float * 3)(*mean)
         s = (ctypes.c_float * 3)(*std)
@@ -890,6 +912,10 @@ class Jpeg:
         lib.rnb_jpeg_decode_scans_host.argtypes = [vp, ll, vp, ctypes.c_int, ctypes.c_int,
                                                    ctypes.c_int, vp, ll, ll, vp]
         lib.rnb_jpeg_decode_scans_host.restype = ctypes.c_int
+        lib.rnb_jpeg_decode_scans_subseq_host.argtypes = [vp, ll, vp, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.c_int, vp, ll, ll, vp,
+                                                          ctypes.c_int, vp]
+        lib.rnb_jpeg_decode_scans_subseq_host.restype = ctypes.c_int
 
     def pack_scans(self, buf, offsets, lengths, out, width=0, height=0):
         """Pack the scans of the frames at ``offsets`` / ``lengths`` of ``buf``
@@ -913,16 +939,27 @@ class Jpeg:
             return rc, int(info[2])
         return rc, scan_offs
 
-    def decode_scans_host(self, scans, scan_offs, nframes, mw, mh, out, record_bytes, status):
+    def decode_scans_host(self, scans, scan_offs, nframes, mw, mh, out, record_bytes, status,
+                          subseq_bytes=0, rounds=None):
         """The interval decoder on the CPU (what ``jpeg_huff_kernel`` computes):
         returns 0 or the negative buffer-level refusal; ``status`` (int32
-        [nframes]) receives each frame's code."""
+        [nframes]) receives each frame's code. ``subseq_bytes`` > 0: the
+        emulation of ``jpeg_huff_subseq_kernel``; ``rounds`` (int32 [nframes])
+        then receives each frame's synchronisation rounds."""
         import numpy as np
         offs = np.ascontiguousarray(scan_offs, dtype=np.int64)
         if offs.size < nframes + 1 or status.dtype != np.int32 or status.size < nframes \
                 or not (scans.flags.c_contiguous and out.flags.c_contiguous
                         and status.flags.c_contiguous):
             raise ValueError("jpeg decode_scans_host: table / output arrays do not fit")
+        if subseq_bytes:
+            if rounds is None or rounds.dtype != np.int32 or rounds.size < nframes \
+                    or not rounds.flags.c_contiguous:
+                raise ValueError("jpeg decode_scans_host: rounds must be int32 [nframes]")
+            return int(self.lib.rnb_jpeg_decode_scans_subseq_host(
+                scans.ctypes.data, scans.size, offs.ctypes.data, int(nframes), int(mw), int(mh),
+                out.ctypes.data, out.size, int(record_bytes), status.ctypes.data,
+                int(subseq_bytes), rounds.ctypes.data))
         return int(self.lib.rnb_jpeg_decode_scans_host(
             scans.ctypes.data, scans.size, offs.ctypes.data, int(nframes), int(mw), int(mh),
             out.ctypes.data, out.size, int(record_bytes), status.ctypes.data))

@@ -369,7 +369,8 @@ def jpeg_idct(records: torch.Tensor, nframes: int, mw: int, mh: int,
 def jpeg_huff(scans: torch.Tensor, scan_offs, nframes: int, mw: int, mh: int,
               out: Optional[torch.Tensor] = None, record_bytes: Optional[int] = None,
               status: Optional[torch.Tensor] = None,
-              offs_dev: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+              offs_dev: Optional[torch.Tensor] = None, subseq_bytes: int = 0,
+              rounds: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Huffman-decode ``nframes`` packed scan records (``utils/mjpeg.py:
     pack_scans``; flat uint8 tensor ``scans``, record ``i`` at
     ``scan_offs[i] : scan_offs[i + 1]``, ``scan_offs`` a host table of
@@ -386,8 +387,21 @@ def jpeg_huff(scans: torch.Tensor, scan_offs, nframes: int, mw: int, mh: int,
     view of the upload); uploaded here when not given. The launcher refuses
     (``RuntimeError``) without launching when a record would reach outside its
     buffer or is misaligned. On the CPU ``rnb_jpeg_decode_scans_host``, the
-    same decode loop."""
+    same decode loop.
+
+    ``subseq_bytes`` > 0 (a multiple of 16 in 16..4096, else ``ValueError``
+    before anything is launched) selects ``jpeg_huff_subseq_kernel``: a frame
+    whose scan is one interval (no restart markers) is cut into subsequences
+    of that many scan bytes, which the lanes of its workgroup decode in
+    parallel and synchronise (``csrc/jpeg_huff.h``); frames with restart
+    markers go lane per interval as above. Records and status are the same
+    byte for byte. ``rounds``: an int32 tensor of >= ``nframes`` on the
+    device of ``scans`` that receives each frame's synchronisation rounds
+    (allocated and dropped when not given). On the CPU the kernel's host
+    emulation, ``rnb_jpeg_decode_scans_subseq_host``."""
     import numpy as np
+    from ..utils import mjpeg
+    subseq_bytes = mjpeg.check_subseq_bytes(subseq_bytes, "jpeg_huff")
     n = mw * mh
     rb = 384 + 768 * n if record_bytes is None else int(record_bytes)
     offs = np.ascontiguousarray(scan_offs.numpy() if isinstance(scan_offs, torch.Tensor)
@@ -405,6 +419,13 @@ def jpeg_huff(scans: torch.Tensor, scan_offs, nframes: int, mw: int, mh: int,
                                or status.numel() < nframes):
         raise ValueError("jpeg_huff: status must be a contiguous int32 tensor of >= %d on %s"
                          % (nframes, scans.device))
+    if rounds is not None and (rounds.dtype != torch.int32 or rounds.dim() != 1
+                               or not rounds.is_contiguous() or rounds.device != scans.device
+                               or rounds.numel() < nframes):
+        raise ValueError("jpeg_huff: rounds must be a contiguous int32 tensor of >= %d on %s"
+                         % (nframes, scans.device))
+    if rounds is None and subseq_bytes:
+        rounds = torch.zeros(nframes, dtype=torch.int32, device=scans.device)
     if out is None:
         out = torch.empty(nframes * rb, dtype=torch.uint8, device=scans.device)
     if status is None:
@@ -417,17 +438,25 @@ def jpeg_huff(scans: torch.Tensor, scan_offs, nframes: int, mw: int, mh: int,
                 or not offs_dev.is_contiguous() or offs_dev.numel() < nframes + 1:
             raise ValueError("jpeg_huff: offs_dev must be >= %d contiguous int64 on %s"
                              % (nframes + 1, scans.device))
-        kernels().jpeg_huff(scans.data_ptr(), scans.numel(), offs, offs_dev.data_ptr(), nframes,
-                            mw, mh, out.data_ptr(), out.numel(), rb, status.data_ptr(),
-                            torch.cuda.current_stream(scans.device).cuda_stream)
+        stream = torch.cuda.current_stream(scans.device).cuda_stream
+        if subseq_bytes:
+            kernels().jpeg_huff_subseq(scans.data_ptr(), scans.numel(), offs, offs_dev.data_ptr(),
+                                       nframes, mw, mh, out.data_ptr(), out.numel(), rb,
+                                       status.data_ptr(), subseq_bytes, rounds.data_ptr(), stream)
+        else:
+            kernels().jpeg_huff(scans.data_ptr(), scans.numel(), offs, offs_dev.data_ptr(),
+                                nframes, mw, mh, out.data_ptr(), out.numel(), rb,
+                                status.data_ptr(), stream)
         return out[:nframes * rb], status[:nframes]
-    from ..utils import mjpeg
     try:
-        mjpeg.decode_scans_host(scans.numpy(), offs, nframes, mw, mh, out.numpy(), rb,
-                                status.numpy())
+        got = mjpeg.decode_scans_host(scans.numpy(), offs, nframes, mw, mh, out.numpy(), rb,
+                                      status.numpy(), subseq_bytes=subseq_bytes,
+                                      return_rounds=True)
     except mjpeg.JpegError:
         raise ValueError("jpeg_huff: a scan record or a frame record lies outside its buffer, "
                          "or is misaligned")
+    if rounds is not None:
+        rounds[:nframes].copy_(torch.from_numpy(got[2]))
     return out[:nframes * rb], status[:nframes]
 
 

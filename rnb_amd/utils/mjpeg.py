@@ -25,7 +25,9 @@ ceil(H / 16)``): ``384 + 768 mw mh`` bytes.
 the first packs frames' entropy-coded scans into *scan records* (tables, the
 byte span of every restart interval, the scan verbatim; layout in
 ``csrc/jpeg_huff.h``), the second is the host mirror of ``jpeg_huff_kernel``,
-which decodes them into frame records, one restart interval per lane.
+which decodes them into frame records, one restart interval per lane, and
+with ``subseq_bytes`` the emulation of ``jpeg_huff_subseq_kernel``, which
+decodes a scan without restart markers by synchronised subsequences.
 """
 from __future__ import annotations
 
@@ -235,26 +237,47 @@ def pack_scans(data, offsets, lengths, out: np.ndarray, width: int = 0, height: 
     return got, extra
 
 
+def check_subseq_bytes(subseq_bytes, what: str) -> int:
+    """``subseq_bytes`` as the subsequence decoders take it: 0 (off) or a
+    multiple of 16 in 16..4096; anything else raises ``ValueError``."""
+    if isinstance(subseq_bytes, bool) or not isinstance(subseq_bytes, (int, np.integer)) \
+            or (subseq_bytes != 0 and not (16 <= subseq_bytes <= 4096 and subseq_bytes % 16 == 0)):
+        raise ValueError("%s: subseq_bytes must be 0 or a multiple of 16 in 16..4096, got %r"
+                         % (what, subseq_bytes))
+    return int(subseq_bytes)
+
+
 def decode_scans_host(scans: np.ndarray, scan_offs, nframes: int, mw: int, mh: int,
                       out: Optional[np.ndarray] = None, record_bytes: Optional[int] = None,
-                      status: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+                      status: Optional[np.ndarray] = None, subseq_bytes: int = 0,
+                      return_rounds: bool = False):
     """The GPU interval decoder's host mirror (``rnb_jpeg_decode_scans_host``):
     ``nframes`` scan records -> (frame records ``record_bytes`` apart in a flat
     uint8 array, int32 status per frame: 0 or the code of the frame's
     lowest-numbered failing interval; see ``status_field``). A buffer, offset
-    or alignment that is refused raises ``JpegError`` (field 'argument')."""
+    or alignment that is refused raises ``JpegError`` (field 'argument').
+
+    ``subseq_bytes`` > 0 (a multiple of 16 in 16..4096, else ``ValueError``)
+    runs the emulation of ``jpeg_huff_subseq_kernel`` instead
+    (``rnb_jpeg_decode_scans_subseq_host``): frames without restart markers are
+    decoded by synchronised subsequences of that many scan bytes, to the same
+    records and status. ``return_rounds`` appends the int32 synchronisation
+    rounds per frame (zeros at ``subseq_bytes=0``) to the result."""
+    check_subseq_bytes(subseq_bytes, "decode_scans_host")
     lib = _need_native("decode_scans_host")
     rb = 384 + 768 * mw * mh if record_bytes is None else int(record_bytes)
     if out is None:
         out = np.empty(nframes * rb, dtype=np.uint8)
     if status is None:
         status = np.zeros(nframes, dtype=np.int32)
-    rc = lib.decode_scans_host(scans, scan_offs, nframes, mw, mh, out, rb, status)
+    rounds = np.zeros(nframes, dtype=np.int32)
+    rc = lib.decode_scans_host(scans, scan_offs, nframes, mw, mh, out, rb, status,
+                               subseq_bytes, rounds)
     if rc:
         field = lib.error_name(rc)
         raise JpegError(field, "decode_scans_host: %s (field '%s')"
                         % (_REASONS.get(field, field), field))
-    return out, status
+    return (out, status, rounds) if return_rounds else (out, status)
 
 
 def status_field(code: int) -> str:

@@ -17,10 +17,15 @@
     ``MjpegDecoder(entropy="gpu")``, with the bytes each path uploads.
     ``--restart-interval N`` writes the stream with a restart marker every N
     MCUs (22: one MCU row at 340x256, 16 intervals, i.e. GPU lanes, per frame;
-    0: none, one lane per frame).
+    0: none, one lane per frame). ``--subseq-bytes 0,64,256`` times
+    ``jpeg_huff_subseq_kernel`` at each size above 0 in the same rounds as
+    ``jpeg_huff_kernel`` (0, the baseline), after comparing its records with
+    the host decoder's, prints the synchronisation rounds and subsequences
+    per frame, and repeats the ``MjpegDecoder(entropy="gpu")`` rows per size.
 
     python scripts/mjpeg_decode_bench.py --out profiles/mjpeg_decode.txt
     python scripts/mjpeg_decode_bench.py --entropy gpu --restart-interval 22
+    python scripts/mjpeg_decode_bench.py --entropy gpu --subseq-bytes 0,64,128,256,512
 """
 import argparse
 import os
@@ -58,9 +63,10 @@ def encode(quality, restart=0):
     return [mjpeg.encode_frame(*f, q, restart) for f in synthetic_frames(3, DISTINCT, W, H)]
 
 
-def huff_kernel(dev, encoded, reps, rounds, lines):
+def huff_kernel(dev, encoded, reps, rounds, lines, subseq=()):
     """jpeg_huff_kernel on one request's scan records, alternating with the
-    IDCT kernel it feeds."""
+    IDCT kernel it feeds and with jpeg_huff_subseq_kernel at every size in
+    ``subseq``."""
     mw, mh, rb = mjpeg.geometry(W, H)
     n = CLIPS * F
     frames = [encoded[i % DISTINCT][0] for i in range(n)]
@@ -80,14 +86,31 @@ def huff_kernel(dev, encoded, reps, rounds, lines):
 
     def idct():
         vops.jpeg_idct(rec, n, mw, mh, out=surf)
+    sync_rounds = torch.zeros(n, dtype=torch.int32, device=dev)
+
+    def huff_subseq(size):
+        def run():
+            vops.jpeg_huff(scans, scan_offs, n, mw, mh, out=rec, status=status, offs_dev=offs_dev,
+                           subseq_bytes=size, rounds=sync_rounds)
+        return run
     reps = max(10, reps // 10)                            # a millisecond-scale kernel
-    fns = (("jpeg_huff_kernel", huff), ("jpeg_idct_kernel", idct))
-    for _, fn in fns:
-        event_ms(fn, reps)
-    assert int(status.abs().sum()) == 0
+    fns = (("jpeg_huff_kernel", huff), ("jpeg_idct_kernel", idct)) + tuple(
+        ("jpeg_huff_subseq S=%d" % sub, huff_subseq(sub)) for sub in subseq if sub)
     want = np.empty(n * rb, dtype=np.uint8)
     mjpeg.entropy_decode(data, offs, lens, want, rb, 4)
-    assert (rec.cpu().numpy() == want).all()              # what is timed is the right answer
+    shape = {}
+    for name, fn in fns:
+        if fn is not idct:
+            rec.fill_(0x5A)
+        event_ms(fn, reps)
+        assert int(status.abs().sum()) == 0, name
+        assert (rec.cpu().numpy() == want).all(), name    # what is timed is the right answer
+        if "subseq" in name:
+            sub = int(name.split("=")[1])
+            spans = [int(buf[o + 2036:o + 2040].view(np.uint32)[0])
+                     - int(buf[o + 2032:o + 2036].view(np.uint32)[0]) for o in scan_offs[:-1]]
+            shape[name] = (sync_rounds.float().mean().item(), int(sync_rounds.max()),
+                           float(np.mean([-(-x // sub) for x in spans])))
     times = {name: [] for name, _ in fns}
     for _ in range(rounds):
         for name, fn in fns:
@@ -100,6 +123,12 @@ def huff_kernel(dev, encoded, reps, rounds, lines):
     lines.append("jpeg_huff_kernel: %d workgroups of 64 lanes, %d intervals (busy lanes) per frame; "
                  "%d bytes of scan records in, %d bytes of frame records out"
                  % (n, intervals, size, n * rb))
+    for name in shape:
+        lines.append("%s: %d workgroups of 256 lanes; synchronisation rounds per frame mean %.1f, "
+                     "max %d; %.0f subsequences per frame%s"
+                     % ((name, n) + shape[name]
+                        + ("" if intervals == 1 else " if it had one interval: it has %d, one "
+                           "lane each, no rounds" % intervals,)))
     t = []
     for _ in range(20):
         t0 = time.perf_counter()
@@ -194,7 +223,8 @@ def decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines, label, *
                                   sustained, up))
 
 
-def host(dev, dtype, encoded, reqs, lines, sustained=60, entropy="host", restart=0):
+def host(dev, dtype, encoded, reqs, lines, sustained=60, entropy="host", restart=0,
+         subseq=()):
     frames = 300
     starts = [20 * c for c in range(CLIPS)]
     with tempfile.TemporaryDirectory() as d:
@@ -224,8 +254,10 @@ def host(dev, dtype, encoded, reqs, lines, sustained=60, entropy="host", restart
             decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines,
                          "threads=%d" % threads, threads=threads)
         if entropy == "gpu":
-            decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines, "entropy=gpu",
-                         entropy="gpu")
+            for sub in subseq or (None,):
+                decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines,
+                             "entropy=gpu" if sub is None else "gpu S=%d" % sub,
+                             entropy="gpu", subseq_bytes=sub)
 
 
 def main():
@@ -238,6 +270,9 @@ def main():
     ap.add_argument("--entropy", choices=("host", "gpu"), default="host",
                     help="gpu: also measure jpeg_huff_kernel and MjpegDecoder(entropy='gpu')")
     ap.add_argument("--restart-interval", type=int, default=0, help="in MCUs; 0: none")
+    ap.add_argument("--subseq-bytes", default="",
+                    help="with --entropy gpu: comma-separated subsequence sizes for "
+                         "jpeg_huff_subseq_kernel (0: jpeg_huff_kernel, always the baseline)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -245,13 +280,15 @@ def main():
     dev = torch.device("cuda:0")
     lines = ["mjpeg decode path, per 15-clip request at %dx%d -> 112x112 (%s)"
              % (W, H, torch.cuda.get_device_name(0))]
+    subseq = tuple(mjpeg.check_subseq_bytes(int(x), "--subseq-bytes")
+                   for x in args.subseq_bytes.split(",") if x.strip())
     encoded = encode(75, args.restart_interval)
     for dtype in (torch.float32, torch.bfloat16):
         kernels(dev, dtype, encoded, args.reps, args.rounds, lines)
     if args.entropy == "gpu":
-        huff_kernel(dev, encoded, args.reps, args.rounds, lines)
+        huff_kernel(dev, encoded, args.reps, args.rounds, lines, subseq)
     host(dev, torch.float32, encoded, args.requests, lines, args.sustained, args.entropy,
-         args.restart_interval)
+         args.restart_interval, subseq)
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if args.out:
