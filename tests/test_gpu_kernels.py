@@ -262,6 +262,76 @@ def test_head_many_clips(n):
     assert torch.allclose(y, head.forward_torch(x), atol=1e-4, rtol=1e-4)
 
 
+def _head_case(dtype, thw, integer, seed):
+    """N = 17 (a full 16-clip block + 1), C = 80 of Cs = 88 channels (20 per
+    wave: one full 16-channel group and a partial one), 70 classes (a full
+    64-class block + 6 lanes); the padding channels hold 1e4."""
+    N, C, Cs, ncls = 17, 80, 88, 70
+    S = thw[0] * thw[1] * thw[2]
+    g = torch.Generator().manual_seed(seed)
+    lin = torch.nn.Linear(C, ncls)
+    if integer:
+        # multiples of S, so that sum * (1.0f / S) rounds back to the exact integer mean
+        x = (S * torch.randint(-3, 4, (N,) + thw + (Cs,), generator=g)).float()
+        with torch.no_grad():
+            lin.weight.copy_(torch.randint(-2, 3, (ncls, C), generator=g).float())
+            lin.bias.copy_(torch.randint(-9, 10, (ncls,), generator=g).float())
+    else:
+        x = torch.randn((N,) + thw + (Cs,), generator=g)
+    x[..., C:] = 1e4
+    x = x.to(dtype)
+    ref = x[..., :C].double().mean(dim=(1, 2, 3)) @ lin.weight.double().t() + lin.bias.double()
+    return vops.Head(lin, DEV), x.to(DEV), ref
+
+
+@pytest.mark.parametrize("integer", [False, True], ids=["random", "integers"])
+@pytest.mark.parametrize("thw", [(1, 2, 5), (1, 1, 5)], ids=["S10", "S5"])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+def test_head_tails_against_fp64(dtype, thw, integer):
+    """The S-tail loops of both pool kernels (S = 10: a group of 7 + 3; S = 5:
+    the tail alone), Cs > C, the partial 16-channel group and the partial class
+    block of head_linear_kernel, against fp64; integer inputs with equality."""
+    head, x, ref = _head_case(dtype, thw, integer, seed=thw[2] * thw[1] + integer)
+    out = torch.full((20, 70), -77.0, device=DEV)
+    y = head.forward(x, out=out[:17])
+    torch.cuda.synchronize()
+    assert y.data_ptr() == out.data_ptr() and tuple(y.shape) == (17, 70)
+    assert torch.all(out[17:] == -77.0)                    # the canary rows
+    err = (y.double().cpu() - ref).abs().max().item()
+    print("head %s S=%d %s: max |kernel - fp64| = %.3g, max |ref| = %.3g"
+          % (dtype, x.shape[1] * x.shape[2] * x.shape[3], "integers" if integer else "random",
+             err, ref.abs().max().item()))
+    if integer:
+        assert torch.equal(y.double().cpu(), ref)
+    else:
+        assert err < 1e-5 * ref.abs().max().item()         # test_f32_preprocess_and_head_match_mirrors'
+
+
+@pytest.mark.parametrize("ncls,dup", [(300, (4, 7, 260)), (5, (1, 3))])
+def test_video_reduce_ties_and_small_class_counts(ncls, dup):
+    """Integer logits, so the sums are exact: an all-equal row -> 0, an empty
+    video -> -1 with a zero sums row, and maxima duplicated within one thread's
+    strides (4 and 260 = 4 + 256) and across threads -> the lowest index."""
+    g = torch.Generator().manual_seed(ncls)
+    logits = torch.randint(-5, 6, (11, ncls), generator=g).float()
+    logits[0] = 3.0                                         # video 0: all classes equal
+    offs = [0, 1, 1, 6, 11]
+    for v in (2, 3):
+        a, b = offs[v], offs[v + 1]
+        s = logits[a:b].sum(0)
+        for i in dup:
+            logits[a, i] += s.max() + 3.0 - s[i]
+    want = torch.stack([logits[offs[v]:offs[v + 1]].double().sum(0) for v in range(4)])
+    assert all((want[v] == want[v].max()).nonzero().view(-1).tolist() == list(dup) for v in (2, 3))
+    sums = torch.full((4, ncls), 7.0, device=DEV)
+    got, arg = vops.video_reduce(logits.to(DEV), torch.tensor(offs, dtype=torch.int32, device=DEV),
+                                 sums=sums)
+    torch.cuda.synchronize()
+    assert got.data_ptr() == sums.data_ptr()
+    assert torch.equal(got.double().cpu(), want) and torch.all(got[1] == 0)
+    assert arg.cpu().tolist() == [0, -1, dup[0], dup[0]]
+
+
 def test_clipgen_partial_and_many_clips():
     vids = torch.arange(5, dtype=torch.int32) * 7
     starts = torch.arange(5, dtype=torch.int32) * 3

@@ -528,8 +528,13 @@ def test_bt601_is_what_it_was(crop):
 
 @pytest.mark.parametrize("W,H", [(46, 34), (45, 33)])
 def test_jfif_mirror_against_the_formula_in_fp64(W, H):
-    """Random planes (odd sizes too: chroma planes round up); the reference
-    samples in fp64 and applies the JFIF formula."""
+    """Random planes (odd sizes too: chroma planes round up) through the
+    mirror in fp32 against the mirror's own sampler (``_bilinear_torch``) and
+    coordinate expressions evaluated in fp64, followed by the JFIF formula:
+    a check of the mirror's fp32 arithmetic, of the matrix as written here and
+    of the clamp, NOT of the mapping, the chroma siting or the tap selection,
+    which both sides share. Those are checked against an independent
+    reference in test_decode_oracle_cpu.py."""
     rng = np.random.default_rng(W)
     cw, ch = (W + 1) // 2, (H + 1) // 2
     F = 2
@@ -633,13 +638,34 @@ def test_make_decoder_mjpeg():
     dec.warmup(2)                                         # needs no file
 
 
+def pil_rgb(path):
+    """PIL's own RGB of every frame of a stream: uint8 [frames, H, W, 3]
+    (libjpeg's IDCT, its "fancy" chroma upsampling and its colour conversion)."""
+    import io
+    from PIL import Image
+    data = np.fromfile(path, dtype=np.uint8)
+    idx = mjpeg.read_index(path)
+    return np.stack([np.asarray(Image.open(io.BytesIO(frame_bytes(data, idx, i))).convert("RGB"))
+                     for i in range(idx.num_frames)])
+
+
 def write_golden():
+    """Streams and PIL's luma as PIL writes and reads them here; a stream that
+    is already there and that this PIL version would encode differently is
+    kept (with its luma), and only PIL's RGB of it is written."""
     os.makedirs(GOLDEN, exist_ok=True)
     for name, (W, H, options) in GOLDEN_STREAMS.items():
         kind = "ramp" if name.startswith("ramp") else "noise"
         data, lumas = pil_stream(W, H, dict(options, _kind=kind), seed=len(name))
-        open(os.path.join(GOLDEN, name + ".mjpeg"), "wb").write(data)
-        np.save(os.path.join(GOLDEN, name + "_luma.npy"), np.stack(lumas))
+        path = os.path.join(GOLDEN, name + ".mjpeg")
+        if os.path.exists(path) and open(path, "rb").read() != data:
+            print(name, "kept: this PIL version encodes it differently")
+        else:
+            open(path, "wb").write(data)
+            np.save(os.path.join(GOLDEN, name + "_luma.npy"), np.stack(lumas))
+        rgb = pil_rgb(path)
+        assert rgb.shape == (2, H, W, 3) and rgb.dtype == np.uint8
+        np.save(os.path.join(GOLDEN, name + "_rgb.npy"), rgb)
         print(name, len(data), "bytes")
 
 
