@@ -10,6 +10,9 @@
 //  * rnb_nv12_to_clip /  decoder surfaces (NV12) or uploaded file spans (planar
 //    rnb_yuv420_to_clip  I420 of .y4m files, raw NV12) -> scaled, colour-
 //                        converted, normalised clips in the slot layout.
+//  * rnb_yuv420_to_clip_aa
+//                        the same with the antialiased triangle filter
+//                        (separable through LDS) for downscaled real frames.
 //  * rnb_stem_pack       NDHWC8 -> zero-bordered pixel-pair-packed layout of
 //                        the stem conv (ops/conv.StemConv).
 //  * rnb_preprocess_packed  rnb_preprocess + rnb_stem_pack in one pass: uint8
@@ -291,6 +294,169 @@ __global__ __launch_bounds__(256) void yuv420_clip_kernel(const uint8_t* __restr
     *(uint4*)o = make_uint4(nv12_bf_bits(r) | (nv12_bf_bits(g) << 16), nv12_bf_bits(b), 0u, 0u);
   } else {
     *(float4*)((float*)out + i * 4) = make_float4(r, g, b, 0.f);
+  }
+}
+
+// The antialiased form of yuv420_clip_kernel: the same inputs, mapping, colour
+// and stores, but the triangle filter is widened by the downscale factor
+// (PIL's BILINEAR resize, torch's antialias=True). Along one axis of one plane
+// of n samples, output o of n_out from the box (start, size):
+//   scale = size / n_out, fs = max(scale, 1), s = start + (o + 0.5) scale - 0.5
+//   w_j = max(0, 1 - |j - s| / fs) for j = 0 .. n - 1, out = sum w_j p_j / sum w_j
+// The support is cut at the plane's true samples (never the row stride or a
+// JPEG surface's MCU padding) and the weights are renormalised; the launcher
+// has checked that the box lies inside the frame, so no row of weights is empty.
+//
+// Separable inside the workgroup: a block owns AA_TH output rows x up to AA_TW
+// output columns of one frame. Per plane it filters the source rows its band
+// needs horizontally into LDS as fp32, AA_CH rows at a time (so LDS use does not
+// depend on the scale), and every thread accumulates the vertical sums of its
+// AA_PX output pixels in registers from LDS. Source reads are byte loads (Y4M
+// frames are unaligned); a wave's loads of one tap walk one row segment.
+// Weights are computed in fp32 here: no table, no upload. Every address is a
+// function of geometry only, clamped to the plane.
+#define AA_TW 128
+#define AA_TH 8
+#define AA_CH 32
+#define AA_PX (AA_TW * AA_TH / 256)
+
+static __device__ __forceinline__ float aa_coord(float start, float scale, int o) {
+  return start + ((float)o + 0.5f) * scale - 0.5f;
+}
+
+// the samples inside the open support (s - fs, s + fs), cut to the plane; the
+// weight's own max(0, .) still decides at an end that rounding moved
+static __device__ __forceinline__ void aa_span(float s, float fs, int n, int& lo, int& hi) {
+  lo = max((int)floorf(s - fs) + 1, 0);
+  hi = min((int)ceilf(s + fs) - 1, n - 1);
+}
+
+// One plane of pw x ph samples (row stride `stride`, samples `step` bytes apart)
+// resampled from the box (bx, by, bw, bh) at this thread's pixels: tile columns
+// cx[k] (output column x0 + cx[k]) and output rows oy[k], k < AA_PX, oy < 0 for
+// none. rows: the tile's output rows oy0 .. oy0 + th - 1. All threads of the
+// block call this together (it synchronises).
+static __device__ __forceinline__ void aa_plane(const uint8_t* __restrict__ plane, int pw, int ph,
+                                                int stride, int step, float bx, float by,
+                                                float bw, float bh, int out_w, int out_h,
+                                                int x0, int tw, int oy0, int th,
+                                                const int* cx, const int* oy,
+                                                float* __restrict__ rows_lds, float* res) {
+  const float scx = bw / (float)out_w, scy = bh / (float)out_h;
+  const float fsx = fmaxf(scx, 1.f), fsy = fmaxf(scy, 1.f);
+  const float ifx = 1.f / fsx, ify = 1.f / fsy;
+  int band_lo, band_hi, unused;
+  aa_span(aa_coord(by, scy, oy0), fsy, ph, band_lo, unused);
+  aa_span(aa_coord(by, scy, oy0 + th - 1), fsy, ph, unused, band_hi);
+  float acc[AA_PX], wsum[AA_PX], sy[AA_PX];
+  int ylo[AA_PX], yhi[AA_PX];
+#pragma unroll
+  for (int k = 0; k < AA_PX; ++k) {
+    acc[k] = 0.f;
+    wsum[k] = 0.f;
+    sy[k] = aa_coord(by, scy, max(oy[k], 0));
+    aa_span(sy[k], fsy, ph, ylo[k], yhi[k]);
+    if (oy[k] < 0) yhi[k] = -1;                      // no pixel: an empty span
+  }
+  for (int r0 = band_lo; r0 <= band_hi; r0 += AA_CH) {
+    const int nrows = min(AA_CH, band_hi - r0 + 1);
+    __syncthreads();                                 // the last readers of rows_lds are done
+    for (int i = (int)threadIdx.x; i < nrows * tw; i += 256) {
+      const int r = i / tw, c = i - r * tw;
+      const float sx = aa_coord(bx, scx, x0 + c);
+      int xlo, xhi;
+      aa_span(sx, fsx, pw, xlo, xhi);
+      const uint8_t* row = plane + (long long)(r0 + r) * stride;
+      float a = 0.f, ws = 0.f;
+      // four taps per trip so that four byte loads are in flight; a tap past xhi
+      // reads sample xhi again with weight 0
+      for (int j = xlo; j <= xhi; j += 4) {
+        float p[4], w[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) p[t] = (float)row[(long long)min(j + t, xhi) * step];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          w[t] = j + t <= xhi ? fmaxf(0.f, 1.f - fabsf((float)(j + t) - sx) * ifx) : 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          a += w[t] * p[t];
+          ws += w[t];
+        }
+      }
+      // ws > 0 for every box the launcher lets through; the guard only keeps 0 / 0
+      // out of LDS should that ever not hold. It is no edge handling.
+      rows_lds[r * AA_TW + c] = ws > 0.f ? a / ws : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < AA_PX; ++k) {
+      const int j1 = min(yhi[k], r0 + nrows - 1);
+      for (int j = max(ylo[k], r0); j <= j1; ++j) {
+        const float w = fmaxf(0.f, 1.f - fabsf((float)j - sy[k]) * ify);
+        acc[k] += w * rows_lds[(j - r0) * AA_TW + cx[k]];
+        wsum[k] += w;
+      }
+    }
+  }
+  // wsum is 0 only on idle lanes (oy < 0: no pixel, nothing stored): no 0 / 0 there
+#pragma unroll
+  for (int k = 0; k < AA_PX; ++k) res[k] = wsum[k] > 0.f ? acc[k] / wsum[k] : 0.f;
+}
+
+template <bool FROM_ARRAY, bool JFIF>
+__global__ __launch_bounds__(256) void yuv420_clip_aa_kernel(const uint8_t* __restrict__ buf,
+                                                             const long long* __restrict__ offs,
+                                                             void* __restrict__ out,
+                                                             Yuv420ClipArgs a) {
+  // grid = (column tiles x row bands of one frame, F, nclips): frame and clip are
+  // uniform per block, as in yuv420_clip_kernel
+  __shared__ float rows_lds[AA_CH * AA_TW];
+  const int col_tiles = (a.g.out_w + AA_TW - 1) / AA_TW;
+  const int band = (int)blockIdx.x / col_tiles;
+  const int x0 = ((int)blockIdx.x - band * col_tiles) * AA_TW;
+  const int oy0 = band * AA_TH;
+  const int tw = min(AA_TW, a.g.out_w - x0), th = min(AA_TH, a.g.out_h - oy0);
+  const int f = (int)blockIdx.y, clip = (int)blockIdx.z;
+  const uint8_t* fr = buf + (FROM_ARRAY ? offs[clip] : a.offs[clip]) + f * a.frame_stride;
+  int cx[AA_PX], oy[AA_PX];
+#pragma unroll
+  for (int k = 0; k < AA_PX; ++k) {
+    const int p = (int)threadIdx.x + 256 * k;       // pixel of the tile, row-major
+    const int r = p / tw;
+    cx[k] = p - r * tw;
+    oy[k] = r < th ? oy0 + r : -1;
+  }
+  const int cw = JFIF ? (a.g.src_w + 1) / 2 : a.g.src_w / 2;
+  const int ch = JFIF ? (a.g.src_h + 1) / 2 : a.g.src_h / 2;
+  float yv[AA_PX], u[AA_PX], v[AA_PX];
+  aa_plane(fr + a.y_off, a.g.src_w, a.g.src_h, a.y_stride, 1, a.g.crop_x, a.g.crop_y,
+           a.g.crop_w, a.g.crop_h, a.g.out_w, a.g.out_h, x0, tw, oy0, th, cx, oy, rows_lds, yv);
+  // chroma sample j sits at luma 2 j + 0.5: the chroma box is the luma box / 2
+  const float hx = a.g.crop_x * 0.5f, hy = a.g.crop_y * 0.5f;
+  const float hw = a.g.crop_w * 0.5f, hh = a.g.crop_h * 0.5f;
+  aa_plane(fr + a.u_off, cw, ch, a.u_stride, a.c_step, hx, hy, hw, hh, a.g.out_w, a.g.out_h,
+           x0, tw, oy0, th, cx, oy, rows_lds, u);
+  aa_plane(fr + a.v_off, cw, ch, a.v_stride, a.c_step, hx, hy, hw, hh, a.g.out_w, a.g.out_h,
+           x0, tw, oy0, th, cx, oy, rows_lds, v);
+  const long long frame_px = ((long long)clip * a.F + f) * ((long long)a.g.out_w * a.g.out_h);
+#pragma unroll
+  for (int k = 0; k < AA_PX; ++k) {
+    if (oy[k] < 0) continue;
+    const long long i = frame_px + (long long)oy[k] * a.g.out_w + x0 + cx[k];
+    const float uu = u[k] - 128.f, vv = v[k] - 128.f;
+    const float yy = JFIF ? yv[k] : 1.164f * (yv[k] - 16.f);
+    float r = yy + (JFIF ? 1.402f : 1.596f) * vv;
+    float g = yy - (JFIF ? 0.344136f : 0.392f) * uu - (JFIF ? 0.714136f : 0.813f) * vv;
+    float b = yy + (JFIF ? 1.772f : 2.017f) * uu;
+    r = fminf(fmaxf(r, 0.f), 255.f) * a.g.scale[0] + a.g.shift[0];
+    g = fminf(fmaxf(g, 0.f), 255.f) * a.g.scale[1] + a.g.shift[1];
+    b = fminf(fmaxf(b, 0.f), 255.f) * a.g.scale[2] + a.g.shift[2];
+    if (a.g.bf16) {
+      uint16_t* o = (uint16_t*)out + i * 8;
+      *(uint4*)o = make_uint4(nv12_bf_bits(r) | (nv12_bf_bits(g) << 16), nv12_bf_bits(b), 0u, 0u);
+    } else {
+      *(float4*)((float*)out + i * 4) = make_float4(r, g, b, 0.f);
+    }
   }
 }
 
@@ -672,12 +838,15 @@ int rnb_nv12_to_clip(const void* nv12, void* out, long long frames, int src_w, i
 // would reach outside its frame stride / the buffer (nothing is launched).
 // matrix: 0 BT.601 video range (even frame sizes), 1 full-range JFIF (any size;
 // chroma planes of ceil(w / 2) x ceil(h / 2)).
-int rnb_yuv420_to_clip(const void* buf, long long buf_len, const long long* offs,
-                       const void* offs_dev, int nclips, int F, int src_w, int src_h,
-                       long long frame_stride, const long long* plane_off,
-                       const int* plane_stride, int c_step, void* out, int out_w, int out_h,
-                       const float* crop, const float* mean, const float* stdv, int bf16,
-                       int matrix, hipStream_t stream) {
+// filter: 0 the two-tap bilinear kernel, 1 the antialiased triangle filter
+// (yuv420_clip_aa_kernel), which also needs the crop box inside the frame: -5.
+static int yuv420_to_clip_launch(const void* buf, long long buf_len, const long long* offs,
+                                 const void* offs_dev, int nclips, int F, int src_w, int src_h,
+                                 long long frame_stride, const long long* plane_off,
+                                 const int* plane_stride, int c_step, void* out, int out_w,
+                                 int out_h, const float* crop, const float* mean,
+                                 const float* stdv, int bf16, int matrix, int filter,
+                                 hipStream_t stream) {
   if (nclips <= 0) return 0;
   if (matrix != 0 && matrix != 1) return -2;
   if (F <= 0 || src_w < 1 || src_h < 1 || out_w <= 0 || out_h <= 0) return -2;
@@ -697,6 +866,9 @@ int rnb_yuv420_to_clip(const void* buf, long long buf_len, const long long* offs
     if (offs[c] < 0 || offs[c] + (long long)F * frame_stride > buf_len) return -4;
   const long long ohw = (long long)out_w * out_h;
   if (ohw > 0x7FFFFF00LL || F > 65535 || nclips > 65535) return -2;    // grid limits
+  if (filter && !(crop[0] >= 0.f && crop[1] >= 0.f && crop[2] > 0.f && crop[3] > 0.f &&
+                   (double)crop[0] + crop[2] <= src_w && (double)crop[1] + crop[3] <= src_h))
+    return -5;
   Yuv420ClipArgs a;
   a.g.src_w = src_w; a.g.src_h = src_h; a.g.out_w = out_w; a.g.out_h = out_h;
   a.g.crop_x = crop[0]; a.g.crop_y = crop[1]; a.g.crop_w = crop[2]; a.g.crop_h = crop[3];
@@ -710,12 +882,45 @@ int rnb_yuv420_to_clip(const void* buf, long long buf_len, const long long* offs
   a.y_stride = plane_stride[0]; a.u_stride = plane_stride[1]; a.v_stride = plane_stride[2];
   const bool in_args = nclips <= YUV420_MAX_CLIPS;
   for (int c = 0; c < YUV420_MAX_CLIPS; ++c) a.offs[c] = in_args && c < nclips ? offs[c] : 0;
+  const long long* table = in_args ? (const long long*)nullptr : (const long long*)offs_dev;
+  if (filter) {
+    const long long tiles = (long long)((out_w + AA_TW - 1) / AA_TW) * ((out_h + AA_TH - 1) / AA_TH);
+    if (tiles > 0x7FFFFFFFLL) return -2;
+    const dim3 grid((unsigned)tiles, (unsigned)F, (unsigned)nclips);
+    auto kernel = in_args ? (matrix ? yuv420_clip_aa_kernel<false, true> : yuv420_clip_aa_kernel<false, false>)
+                          : (matrix ? yuv420_clip_aa_kernel<true, true> : yuv420_clip_aa_kernel<true, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (const uint8_t*)buf, table, out, a);
+    return (int)hipGetLastError();
+  }
   const dim3 grid((unsigned)((ohw + 255) / 256), (unsigned)F, (unsigned)nclips);
   auto kernel = in_args ? (matrix ? yuv420_clip_kernel<false, true> : yuv420_clip_kernel<false, false>)
                         : (matrix ? yuv420_clip_kernel<true, true> : yuv420_clip_kernel<true, false>);
-  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (const uint8_t*)buf,
-                     in_args ? (const long long*)nullptr : (const long long*)offs_dev, out, a);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (const uint8_t*)buf, table, out, a);
   return (int)hipGetLastError();
+}
+
+int rnb_yuv420_to_clip(const void* buf, long long buf_len, const long long* offs,
+                       const void* offs_dev, int nclips, int F, int src_w, int src_h,
+                       long long frame_stride, const long long* plane_off,
+                       const int* plane_stride, int c_step, void* out, int out_w, int out_h,
+                       const float* crop, const float* mean, const float* stdv, int bf16,
+                       int matrix, hipStream_t stream) {
+  return yuv420_to_clip_launch(buf, buf_len, offs, offs_dev, nclips, F, src_w, src_h,
+                               frame_stride, plane_off, plane_stride, c_step, out, out_w, out_h,
+                               crop, mean, stdv, bf16, matrix, 0, stream);
+}
+
+// The same arguments and checks; the antialiased triangle filter. -5: the crop
+// box does not lie inside [0, src_w] x [0, src_h] (a row of weights could be empty).
+int rnb_yuv420_to_clip_aa(const void* buf, long long buf_len, const long long* offs,
+                          const void* offs_dev, int nclips, int F, int src_w, int src_h,
+                          long long frame_stride, const long long* plane_off,
+                          const int* plane_stride, int c_step, void* out, int out_w, int out_h,
+                          const float* crop, const float* mean, const float* stdv, int bf16,
+                          int matrix, hipStream_t stream) {
+  return yuv420_to_clip_launch(buf, buf_len, offs, offs_dev, nclips, F, src_w, src_h,
+                               frame_stride, plane_off, plane_stride, c_step, out, out_w, out_h,
+                               crop, mean, stdv, bf16, matrix, 1, stream);
 }
 
 int rnb_preprocess(const void* in, void* out, long long npix, const float* mean,

@@ -190,10 +190,14 @@ class _StagedFileDecoder(Decoder):
     MAX_OPEN = 64            # memory maps kept open (least recently used first out)
 
     def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
-                 width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full"):
+                 width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full",
+                 filter: str = "bilinear"):
         name = type(self).__name__
         if crop not in ("full", "center"):
             raise ValueError("%s: crop must be 'full' or 'center', got %r" % (name, crop))
+        if filter not in vops.FILTERS:
+            raise ValueError("%s: filter must be one of %s, got %r"
+                             % (name, vops.FILTERS, filter))
         if depth < 1:
             raise ValueError("%s: ring depth must be >= 1, got %r" % (name, depth))
         self.device = device
@@ -201,6 +205,7 @@ class _StagedFileDecoder(Decoder):
         self.dtype = dtype
         self.depth = int(depth)
         self.crop = crop
+        self.filter = filter
         self._ids = {}
         self._videos = {}          # video id -> (path, header / index)
         self._maps = OrderedDict()  # video id -> (mmap, uint8 view), LRU
@@ -273,7 +278,10 @@ class Y4mDecoder(_StagedFileDecoder):
 
     ``crop``: ``"full"`` scales the whole frame to the output (what the
     synthetic NV12 path does), ``"center"`` the centred square of the short
-    side."""
+    side. ``filter``: ``"bilinear"`` (two taps per axis, the default) or
+    ``"antialias"``, the triangle filter widened by the downscale factor that
+    PIL's ``resize(BILINEAR)`` and torchvision's ``Resize(antialias=True)``
+    apply (``yuv420_to_clip(filter=)``); both boxes lie inside the frame."""
 
     def probe(self, path):
         vid = self._ids.get(path)
@@ -303,7 +311,8 @@ class Y4mDecoder(_StagedFileDecoder):
             e.dev[:self.F * stride].zero_()
             vops.yuv420_to_clip(e.dev, [0], self.F, W, H, stride,
                                 vops.i420_planes(W, H, len(y4m.FRAME_MARKER)), self.W,
-                                self.H, dtype=self.dtype, out=self._out(1, None))
+                                self.H, dtype=self.dtype, out=self._out(1, None),
+                                filter=self.filter)
             e.event.record(torch.cuda.current_stream(self.device))
             e.in_flight = True
 
@@ -349,7 +358,8 @@ class Y4mDecoder(_StagedFileDecoder):
             out = self._out(n, out)
             vops.yuv420_to_clip(buf[:n * span], offsets, self.F, hdr.width, hdr.height,
                                 hdr.frame_stride, planes, self.W, self.H,
-                                crop=self._crop_box(hdr), dtype=self.dtype, out=out)
+                                crop=self._crop_box(hdr), dtype=self.dtype, out=out,
+                                filter=self.filter)
         finally:
             if cuda:     # also behind the uploads of a request that raised
                 entry.event.record(torch.cuda.current_stream(self.device))
@@ -379,7 +389,8 @@ class MjpegDecoder(_StagedFileDecoder):
     its event discipline are ``Y4mDecoder``'s. On a CPU device the records go
     to the ops' CPU mirrors.
 
-    ``crop`` as for ``Y4mDecoder``; ``threads``: 1-16 entropy-decode threads.
+    ``crop`` and ``filter`` as for ``Y4mDecoder``; ``threads``: 1-16 entropy-decode
+    threads.
 
     ``entropy="gpu"`` (opt-in; ``"host"`` is the path above) moves the Huffman
     decode to the GPU. ``decode`` then only *packs* each clip's scans on the
@@ -415,7 +426,8 @@ class MjpegDecoder(_StagedFileDecoder):
 
     def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
                  width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full",
-                 threads: int = 4, entropy: str = "host", subseq_bytes: Optional[int] = None):
+                 threads: int = 4, entropy: str = "host", subseq_bytes: Optional[int] = None,
+                 filter: str = "bilinear"):
         if isinstance(threads, bool) or not isinstance(threads, int) or not 1 <= threads <= 16:
             raise ValueError("MjpegDecoder: threads must be an integer in 1..16, got %r"
                              % (threads,))
@@ -429,7 +441,7 @@ class MjpegDecoder(_StagedFileDecoder):
         if subseq_bytes is None:
             subseq_bytes = self.SUBSEQ_BYTES if entropy == "gpu" else 0
         subseq_bytes = mjpeg.check_subseq_bytes(subseq_bytes, "MjpegDecoder")
-        super().__init__(device, clip_length, height, width, dtype, depth, crop)
+        super().__init__(device, clip_length, height, width, dtype, depth, crop, filter)
         self.threads = threads
         self.entropy = entropy
         self.subseq_bytes = subseq_bytes
@@ -471,7 +483,8 @@ class MjpegDecoder(_StagedFileDecoder):
                               if self.device.type == "cuda" else None)
         return vops.yuv420_to_clip(surf, [i * self.F * fbytes for i in range(n)], self.F, W, H,
                                    fbytes, vops.jpeg_surface_planes(mw, mh), self.W, self.H,
-                                   crop=crop, dtype=self.dtype, out=out, matrix="jfif")
+                                   crop=crop, dtype=self.dtype, out=out, matrix="jfif",
+                                   filter=self.filter)
 
     def warmup(self, n: int) -> None:
         """Run both kernels on a zeroed record buffer (no file needed)."""
@@ -632,8 +645,8 @@ class MjpegDecoder(_StagedFileDecoder):
 def make_decoder(backend: str, device: torch.device, clip_length=8, height=112, width=112,
                  dtype=torch.bfloat16, decoder_args: Optional[dict] = None) -> Decoder:
     """``decoder_args``: backend-specific constructor arguments (``y4m``:
-    ``depth``, ``crop``; ``mjpeg``: ``depth``, ``crop``, ``threads``, ``entropy``,
-    ``subseq_bytes``); the other
+    ``depth``, ``crop``, ``filter``; ``mjpeg``: ``depth``, ``crop``, ``filter``,
+    ``threads``, ``entropy``, ``subseq_bytes``); the other
     backends take none and ignore it."""
     if backend == "y4m":
         return Y4mDecoder(device, clip_length, height, width, dtype, **(decoder_args or {}))

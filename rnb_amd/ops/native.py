@@ -218,6 +218,8 @@ class Kernels:
                                            ctypes.POINTER(ctypes.c_float), ctypes.c_int,
                                            ctypes.c_int, ctypes.c_void_p]
         lib.rnb_yuv420_to_clip.restype = ctypes.c_int
+        lib.rnb_yuv420_to_clip_aa.argtypes = lib.rnb_yuv420_to_clip.argtypes
+        lib.rnb_yuv420_to_clip_aa.restype = ctypes.c_int
         lib.rnb_jpeg_idct.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
@@ -813,11 +815,13 @@ class Kernels:
 
     def yuv420_to_clip(self, buf_ptr, buf_len, offsets, offsets_dev_ptr, F, src_w, src_h,
                        frame_stride, plane_offsets, plane_strides, c_step, out_ptr, out_w,
-                       out_h, crop, mean, std, bf16, stream, matrix=0):
+                       out_h, crop, mean, std, bf16, stream, matrix=0, antialias=False):
         """``offsets``: the per-clip byte offsets on the host (checked against
         ``buf_len`` by the launcher); ``offsets_dev_ptr``: the same table in
         device memory, needed for more than 32 clips (else None). ``matrix``:
-        0 BT.601 video range, 1 full-range JFIF."""
+        0 BT.601 video range, 1 full-range JFIF. ``antialias``: the
+        ``rnb_yuv420_to_clip_aa`` entry (triangle filter widened by the
+        downscale factor; the crop box must lie inside the frame)."""
         n = len(offsets)
         offs = (ctypes.c_longlong * max(1, n))(*offsets)
         po = (ctypes.c_longlong * 3)(*plane_offsets)
@@ -825,10 +829,11 @@ class Kernels:
         c = (ctypes.c_float * 4)(*crop)
         m = (ctypes.c_float * 3)(*mean)
         s = (ctypes.c_float * 3)(*std)
-        _check(self.lib.rnb_yuv420_to_clip(buf_ptr, buf_len, offs, offsets_dev_ptr, n, F,
-                                           src_w, src_h, frame_stride, po, ps, c_step,
-                                           out_ptr, out_w, out_h, c, m, s, 1 if bf16 else 0,
-                                           int(matrix), stream), "yuv420_to_clip")
+        fn = self.lib.rnb_yuv420_to_clip_aa if antialias else self.lib.rnb_yuv420_to_clip
+        _check(fn(buf_ptr, buf_len, offs, offsets_dev_ptr, n, F, src_w, src_h, frame_stride,
+                  po, ps, c_step, out_ptr, out_w, out_h, c, m, s, 1 if bf16 else 0,
+                  int(matrix), stream),
+               "yuv420_to_clip_aa" if antialias else "yuv420_to_clip")
 
     def jpeg_idct(self, rec_ptr, rec_len, record_bytes, nframes, mw, mh, surf_ptr, surf_len,
                   stream):

@@ -179,23 +179,52 @@ def nv12_to_clip(nv12: torch.Tensor, src_w: int, src_h: int, out_w: int = 112,
 
 
 MATRICES = ("bt601", "jfif")
+FILTERS = ("bilinear", "antialias")
+
+
+def _antialias_weights(n_src: int, n_out: int, start: float, size: float) -> torch.Tensor:
+    """fp32 [n_out, n_src]: the triangle filter widened by the downscale factor,
+    over the plane's own samples only, every row renormalised to 1."""
+    scale = torch.tensor(size, dtype=torch.float32) / n_out
+    fs = scale.clamp(min=1.0)
+    s = start + (torch.arange(n_out, dtype=torch.float32) + 0.5) * scale - 0.5
+    j = torch.arange(n_src, dtype=torch.float32)
+    w = (1.0 - (j.view(1, -1) - s.view(-1, 1)).abs() / fs).clamp(min=0.0)
+    return w / w.sum(dim=1, keepdim=True)
+
+
+def _antialias_torch(plane: torch.Tensor, out_w: int, out_h: int, box) -> torch.Tensor:
+    """plane [F, h, w] float -> [F, out_h, out_w]: rows first, then columns, as
+    ``yuv420_clip_aa_kernel`` does (horizontal pass into LDS, vertical sum)."""
+    _, h, w = plane.shape
+    mx = _antialias_weights(w, out_w, box[0], box[2])
+    my = _antialias_weights(h, out_h, box[1], box[3])
+    return torch.matmul(my, torch.matmul(plane, mx.t()))
 
 
 def _planes_to_clip(y_plane, u_plane, v_plane, shape, crop, dtype, mean, std, out,
-                    matrix="bt601"):
+                    matrix="bt601", filter="bilinear"):
     """CPU mirror shared by ``nv12_to_clip`` and ``yuv420_to_clip``: float Y
     [frames, h, w] and U, V [frames, h/2, w/2] planes -> ``shape`` =
     [..., out_h, out_w, C] normalised frames. ``matrix``: ``"bt601"`` (video
-    range) or ``"jfif"`` (full-range JFIF YCbCr)."""
+    range) or ``"jfif"`` (full-range JFIF YCbCr). ``filter``: ``"bilinear"``
+    (two taps) or ``"antialias"`` (``_antialias_torch``; chroma from the chroma
+    box = luma box / 2 on the chroma plane)."""
     out_h, out_w = shape[-3], shape[-2]
-    ox = torch.arange(out_w, dtype=torch.float32)
-    oy = torch.arange(out_h, dtype=torch.float32)
-    sx = crop[0] + (ox + 0.5) * (crop[2] / out_w) - 0.5
-    sy = crop[1] + (oy + 0.5) * (crop[3] / out_h) - 0.5
-    yv = _bilinear_torch(y_plane, sx, sy)
-    cx, cy = (sx + 0.5) * 0.5 - 0.5, (sy + 0.5) * 0.5 - 0.5
-    u = _bilinear_torch(u_plane, cx, cy) - 128.0
-    v = _bilinear_torch(v_plane, cx, cy) - 128.0
+    if filter == "antialias":
+        cbox = tuple(c / 2.0 for c in crop)
+        yv = _antialias_torch(y_plane, out_w, out_h, crop)
+        u = _antialias_torch(u_plane, out_w, out_h, cbox) - 128.0
+        v = _antialias_torch(v_plane, out_w, out_h, cbox) - 128.0
+    else:
+        ox = torch.arange(out_w, dtype=torch.float32)
+        oy = torch.arange(out_h, dtype=torch.float32)
+        sx = crop[0] + (ox + 0.5) * (crop[2] / out_w) - 0.5
+        sy = crop[1] + (oy + 0.5) * (crop[3] / out_h) - 0.5
+        yv = _bilinear_torch(y_plane, sx, sy)
+        cx, cy = (sx + 0.5) * 0.5 - 0.5, (sy + 0.5) * 0.5 - 0.5
+        u = _bilinear_torch(u_plane, cx, cy) - 128.0
+        v = _bilinear_torch(v_plane, cx, cy) - 128.0
     if matrix == "jfif":
         rgb = torch.stack([yv + 1.402 * v, yv - 0.344136 * u - 0.714136 * v, yv + 1.772 * u],
                           dim=-1)
@@ -241,7 +270,8 @@ def nv12_planes(W: int, H: int, header: int = 0) -> YuvPlanes:
 def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: int,
                    frame_stride: int, planes: YuvPlanes, out_w: int = 112, out_h: int = 112,
                    crop=None, dtype=torch.float32, mean=KINETICS_MEAN, std=KINETICS_STD,
-                   out: Optional[torch.Tensor] = None, matrix: str = "bt601") -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, matrix: str = "bt601",
+                   filter: str = "bilinear") -> torch.Tensor:
     """4:2:0 frames inside a byte buffer -> normalised NDHWC clips
     [n, F, out_h, out_w, C] (fp32 C=4 / bf16 C=8), with ``nv12_to_clip``'s
     arithmetic. ``buf`` is a flat uint8 tensor (uploaded file spans); clip ``c``
@@ -253,9 +283,19 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
     frame sizes; ``matrix="jfif"`` is the full-range JFIF YCbCr of JPEG frames
     (R = Y + 1.402 (Cr - 128), G = Y - 0.344136 (Cb - 128) - 0.714136 (Cr - 128),
     B = Y + 1.772 (Cb - 128)) and takes any size, with chroma planes of
-    ceil(w / 2) x ceil(h / 2)."""
+    ceil(w / 2) x ceil(h / 2).
+
+    ``filter="bilinear"`` (default) samples two taps per axis, whatever the
+    scale. ``filter="antialias"`` is the triangle filter widened by the
+    downscale factor, PIL's ``resize(BILINEAR)`` / torch's ``antialias=True``:
+    per axis ``scale = size / n_out``, ``fs = max(scale, 1)``, weights
+    ``max(0, 1 - |j - s_o| / fs)`` over the plane's own samples, renormalised
+    (``yuv420_clip_aa_kernel``; for ``scale <= 1`` the same as bilinear). It
+    needs ``crop`` inside the frame and raises ``ValueError`` otherwise."""
     if matrix not in MATRICES:
         raise ValueError("yuv420_to_clip: matrix must be one of %s, got %r" % (MATRICES, matrix))
+    if filter not in FILTERS:
+        raise ValueError("yuv420_to_clip: filter must be one of %s, got %r" % (FILTERS, filter))
     jfif = matrix == "jfif"
     offsets = [int(o) for o in (clip_offsets.tolist() if isinstance(clip_offsets, torch.Tensor)
                                 else clip_offsets)]
@@ -269,6 +309,14 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
     if out is not None and (out.dtype != dtype or not out.is_contiguous()
                             or out.numel() != math.prod(shape)):
         raise ValueError("yuv420_to_clip: out must be contiguous %s %s" % (dtype, shape))
+    antialias = filter == "antialias"
+    if antialias:
+        # the box as the kernel gets it (fp32), summed in double: the launcher's own check
+        bx, by, bw, bh = torch.tensor(crop, dtype=torch.float32).double().tolist()
+        if not (bx >= 0 and by >= 0 and bw > 0 and bh > 0
+                and bx + bw <= src_w and by + bh <= src_h):
+            raise ValueError("yuv420_to_clip: filter='antialias' needs the crop box inside "
+                             "the %d x %d frame, got %r" % (src_w, src_h, crop))
     if buf.is_cuda:
         from .native import kernels
         if out is None:
@@ -284,7 +332,7 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
                                  out.data_ptr(), out_w, out_h, crop, mean, std,
                                  dtype == torch.bfloat16,
                                  torch.cuda.current_stream(buf.device).cuda_stream,
-                                 matrix=1 if jfif else 0)
+                                 matrix=1 if jfif else 0, antialias=antialias)
         return out
     if (not jfif and (src_w % 2 or src_h % 2)) or planes.c_step not in (1, 2):
         raise ValueError("yuv420_to_clip: even frame sizes and a chroma step of 1 or 2")
@@ -301,7 +349,7 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
     return _planes_to_clip(gather(planes.y, planes.y_stride, src_h, src_w, 1),
                            gather(planes.u, planes.u_stride, ch, cw, planes.c_step),
                            gather(planes.v, planes.v_stride, ch, cw, planes.c_step),
-                           shape, crop, dtype, mean, std, out, matrix)
+                           shape, crop, dtype, mean, std, out, matrix, filter)
 
 
 # ---------------------------------------------------------------------------

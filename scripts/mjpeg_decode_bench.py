@@ -138,7 +138,7 @@ def huff_kernel(dev, encoded, reps, rounds, lines, subseq=()):
                  % (statistics.median(t), n, min(t)))
 
 
-def kernels(dev, dtype, encoded, reps, rounds, lines):
+def kernels(dev, dtype, encoded, reps, rounds, lines, filter="bilinear"):
     mw, mh, rb = mjpeg.geometry(W, H)
     n = CLIPS * F
     qt = mjpeg.quality_tables(75)[[0, 1, 1]]
@@ -167,6 +167,12 @@ def kernels(dev, dtype, encoded, reps, rounds, lines):
     fns = (("jpeg_idct_kernel", idct, moved), ("device copy, same bytes", copy, moved),
            ("yuv420_clip_kernel jfif", jfif, n * fb + out.numel() * out.element_size()),
            ("yuv420_clip_kernel bt601", bt601, n * fb + out.numel() * out.element_size()))
+    if filter == "antialias":
+        def jfif_aa():
+            vops.yuv420_to_clip(surf, offs, F, W, H, fb, planes, dtype=dtype, out=out,
+                                matrix="jfif", filter="antialias")
+        fns += (("yuv420_clip_aa_kernel jfif", jfif_aa,
+                 n * fb + out.numel() * out.element_size()),)
     for _, fn, _ in fns:
         event_ms(fn, reps)                                # warm
     times = {name: [] for name, _, _ in fns}
@@ -224,7 +230,7 @@ def decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines, label, *
 
 
 def host(dev, dtype, encoded, reqs, lines, sustained=60, entropy="host", restart=0,
-         subseq=()):
+         subseq=(), filter="bilinear"):
     frames = 300
     starts = [20 * c for c in range(CLIPS)]
     with tempfile.TemporaryDirectory() as d:
@@ -252,12 +258,12 @@ def host(dev, dtype, encoded, reqs, lines, sustained=60, entropy="host", restart
             lines.append("entropy decode alone, %2d threads: median %.2f ms per %d frames "
                          "(min %.2f)" % (threads, statistics.median(t), len(sel), min(t)))
             decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines,
-                         "threads=%d" % threads, threads=threads)
+                         "threads=%d" % threads, threads=threads, filter=filter)
         if entropy == "gpu":
             for sub in subseq or (None,):
                 decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines,
                              "entropy=gpu" if sub is None else "gpu S=%d" % sub,
-                             entropy="gpu", subseq_bytes=sub)
+                             entropy="gpu", subseq_bytes=sub, filter=filter)
 
 
 def main():
@@ -273,22 +279,26 @@ def main():
     ap.add_argument("--subseq-bytes", default="",
                     help="with --entropy gpu: comma-separated subsequence sizes for "
                          "jpeg_huff_subseq_kernel (0: jpeg_huff_kernel, always the baseline)")
+    ap.add_argument("--filter", choices=vops.FILTERS, default="bilinear",
+                    help="antialias: also time yuv420_clip_aa_kernel, and decode with "
+                         "MjpegDecoder(filter='antialias')")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mjpeg_decode_bench: needs a GPU")
     dev = torch.device("cuda:0")
-    lines = ["mjpeg decode path, per 15-clip request at %dx%d -> 112x112 (%s)"
-             % (W, H, torch.cuda.get_device_name(0))]
+    lines = ["mjpeg decode path, per 15-clip request at %dx%d -> 112x112%s (%s)"
+             % (W, H, ", filter antialias" if args.filter == "antialias" else "",
+                torch.cuda.get_device_name(0))]
     subseq = tuple(mjpeg.check_subseq_bytes(int(x), "--subseq-bytes")
                    for x in args.subseq_bytes.split(",") if x.strip())
     encoded = encode(75, args.restart_interval)
     for dtype in (torch.float32, torch.bfloat16):
-        kernels(dev, dtype, encoded, args.reps, args.rounds, lines)
+        kernels(dev, dtype, encoded, args.reps, args.rounds, lines, args.filter)
     if args.entropy == "gpu":
         huff_kernel(dev, encoded, args.reps, args.rounds, lines, subseq)
     host(dev, torch.float32, encoded, args.requests, lines, args.sustained, args.entropy,
-         args.restart_interval, subseq)
+         args.restart_interval, subseq, args.filter)
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if args.out:

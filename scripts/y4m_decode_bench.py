@@ -8,6 +8,13 @@
     the call itself, and of the call plus a device synchronise.
 
     python scripts/y4m_decode_bench.py --out profiles/y4m_decode.txt
+
+``--filter antialias`` times ``yuv420_clip_aa_kernel`` next to the bilinear
+``yuv420_clip_kernel`` on the same I420 buffer instead (alternating, one
+process; the ratio is reported) and ``Y4mDecoder(filter="antialias")`` on the
+host side. ``--size WxH`` and ``--clips N`` change that request, e.g.
+``--size 1920x1080 --clips 1``. Without ``--filter antialias`` the script runs
+and prints what it always did.
 """
 import argparse
 import os
@@ -77,6 +84,79 @@ def kernels(dev, dtype, reps, rounds, lines):
     lines.append("max |yuv420 - nv12| on the same pixels: %g" % diff)
 
 
+def kernels_antialias(dev, dtype, reps, rounds, lines, w, h, clips):
+    """``yuv420_clip_aa_kernel`` next to ``yuv420_clip_kernel`` on ``clips``
+    clips of random ``w`` x ``h`` I420 frames behind FRAME markers."""
+    rng = np.random.default_rng(0)
+    stride = 6 + vops.nv12_frame_bytes(w, h)
+    buf = torch.from_numpy(rng.integers(0, 256, clips * F * stride, dtype=np.uint8)).to(dev)
+    offs = [c * F * stride for c in range(clips)]
+    C = 4 if dtype == torch.float32 else 8
+    out = torch.empty((clips, F, 112, 112, C), dtype=dtype, device=dev)
+    planes = vops.i420_planes(w, h, 6)
+
+    def antialias():
+        vops.yuv420_to_clip(buf, offs, F, w, h, stride, planes, dtype=dtype, out=out,
+                            filter="antialias")
+
+    def bilinear():
+        vops.yuv420_to_clip(buf, offs, F, w, h, stride, planes, dtype=dtype, out=out)
+    for fn in (antialias, bilinear):
+        event_ms(fn, reps)                                # warm
+    t_aa, t_bil = [], []
+    for _ in range(rounds):
+        t_aa.append(event_ms(antialias, reps))
+        t_bil.append(event_ms(bilinear, reps))
+    src = clips * F * stride
+    dst = out.numel() * out.element_size()
+    name = str(dtype).split(".")[1]
+    for kernel, t in (("yuv420_clip_aa_kernel", t_aa), ("yuv420_clip_kernel   ", t_bil)):
+        med = statistics.median(t)
+        lines.append("%s %s: median %.2f us/launch (min %.2f, max %.2f over %d rounds of %d); "
+                     "%.0f GB/s of %d source + %d output bytes"
+                     % (kernel, name, med * 1e3, min(t) * 1e3, max(t) * 1e3, rounds, reps,
+                        (src + dst) / med / 1e6, src, dst))
+    lines.append("antialias / bilinear kernel time %s: %.2f"
+                 % (name, statistics.median(t_aa) / statistics.median(t_bil)))
+
+
+def host_antialias(dev, dtype, reqs, lines, w, h, clips):
+    """Host time of ``Y4mDecoder(filter="antialias").decode`` for ``clips`` clips
+    20 frames apart in a ``w`` x ``h`` file (warm page cache)."""
+    rng = np.random.default_rng(1)
+    starts = [20 * c for c in range(clips)]
+    frames = min(300, starts[-1] + F + 4)              # 1080p: do not write 300 frames
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "v.y4m")
+        y4m.write_y4m(path, [(rng.integers(0, 256, (h, w), dtype=np.uint8),
+                              rng.integers(0, 256, (h // 2, w // 2), dtype=np.uint8),
+                              rng.integers(0, 256, (h // 2, w // 2), dtype=np.uint8))
+                             for _ in range(frames)])
+        with open(path, "rb") as fp:                       # warm the page cache
+            while fp.read(1 << 24):
+                pass
+        C = 4 if dtype == torch.float32 else 8
+        out = torch.empty((clips, F, 112, 112, C), dtype=dtype, device=dev)
+        dec = Y4mDecoder(dev, dtype=dtype, filter="antialias")
+        vid, _ = dec.probe(path)
+        for _ in range(5):
+            dec.decode(vid, starts, out=out)
+        torch.cuda.synchronize()
+        call, total = [], []
+        for _ in range(reqs):
+            t0 = time.perf_counter()
+            dec.decode(vid, starts, out=out)
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            call.append((t1 - t0) * 1e3)
+            total.append((t2 - t0) * 1e3)
+        lines.append("Y4mDecoder.decode (%dx%d y4m, antialias) %s: host call median %.3f ms "
+                     "(min %.3f, max %.3f), call + sync median %.3f ms, %d requests of %d clips"
+                     % (w, h, str(dtype).split(".")[1], statistics.median(call), min(call),
+                        max(call), statistics.median(total), reqs, clips))
+
+
 def host(dev, dtype, reqs, lines):
     rng = np.random.default_rng(1)
     frames = 300
@@ -120,16 +200,28 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--requests", type=int, default=40)
+    ap.add_argument("--filter", choices=vops.FILTERS, default="bilinear")
+    ap.add_argument("--size", default="%dx%d" % (W, H),
+                    help="with --filter antialias: source WxH (even)")
+    ap.add_argument("--clips", type=int, default=CLIPS, help="with --filter antialias")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("y4m_decode_bench: needs a GPU")
     dev = torch.device("cuda:0")
-    lines = ["y4m decode path, per 15-clip request at %dx%d -> 112x112 (%s)"
-             % (W, H, torch.cuda.get_device_name(0))]
-    for dtype in (torch.float32, torch.bfloat16):
-        kernels(dev, dtype, args.reps, args.rounds, lines)
-    host(dev, torch.float32, args.requests, lines)
+    if args.filter == "antialias":
+        w, h = (int(x) for x in args.size.lower().split("x"))
+        lines = ["y4m decode path, filter antialias, per %d-clip request at %dx%d -> 112x112 (%s)"
+                 % (args.clips, w, h, torch.cuda.get_device_name(0))]
+        for dtype in (torch.float32, torch.bfloat16):
+            kernels_antialias(dev, dtype, args.reps, args.rounds, lines, w, h, args.clips)
+        host_antialias(dev, torch.float32, args.requests, lines, w, h, args.clips)
+    else:
+        lines = ["y4m decode path, per 15-clip request at %dx%d -> 112x112 (%s)"
+                 % (W, H, torch.cuda.get_device_name(0))]
+        for dtype in (torch.float32, torch.bfloat16):
+            kernels(dev, dtype, args.reps, args.rounds, lines)
+        host(dev, torch.float32, args.requests, lines)
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if args.out:

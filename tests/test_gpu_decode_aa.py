@@ -1,0 +1,195 @@
+"""All four instances of ``yuv420_clip_aa_kernel`` against the independent fp64
+oracle of ``decode_oracle_aa.py`` directly (not via the CPU mirror), the bf16
+outputs bit for bit, the stripe pattern, the launcher's refusals, the decoders
+and the loader with ``filter="antialias"``, and the default (``filter`` absent)
+byte for byte against ``filter="bilinear"``. Cases, inputs and bounds are those
+of ``test_decode_aa_cpu.py``; run with ``-s`` for the figures."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import decode_oracle as orc
+import decode_oracle_aa as aa
+from rnb_amd.models.r2p1d.decoder import MjpegDecoder, Y4mDecoder
+from rnb_amd.ops import video as vops
+from rnb_amd.utils import mjpeg, y4m
+from test_decode_aa_cpu import (check_against_oracle, check_case, check_jpeg_surface,
+                                check_pil_resized_rgb, check_refusals, check_stripes,
+                                check_table, check_two_clips)
+from test_mjpeg_cpu import GOLDEN, GOLDEN_STREAMS, frame_bytes
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+CPU = torch.device("cpu")
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("name", [c[0] for c in aa.AA_CASES])
+def test_aa_kernel_against_oracle(name, bf16):
+    """<= 32 clips: the kernel-argument instances (bt601 and jfif); bf16 is the
+    fp32 result rounded to nearest even, bit for bit."""
+    check_case(name, DEV, bf16)
+
+
+def test_aa_kernel_two_clips_at_non_monotonic_offsets():
+    check_two_clips(DEV)
+
+
+@pytest.mark.parametrize("matrix", ["bt601", "jfif"])
+def test_aa_kernel_device_offset_table(matrix):
+    """33 clips: the FROM_ARRAY instances, ``offs[clip]`` from device memory."""
+    check_table(matrix, DEV)
+
+
+def test_aa_kernel_ignores_the_padding_of_a_jpeg_surface():
+    check_jpeg_surface(DEV)
+
+
+def test_aa_kernel_stripes():
+    check_stripes(DEV)
+
+
+def test_aa_refusals_on_the_gpu():
+    check_refusals(DEV)
+
+
+def test_aa_launcher_refuses_what_the_bilinear_launcher_refuses():
+    """The same span and argument checks in front of the new kernel, and its own
+    box check when the op's is bypassed: nothing is launched."""
+    from rnb_amd.ops.native import kernels
+    y, u, v = orc.noise_planes(46, 34, 3, 5)
+    data, stride, pl = orc.pack_i420(y, u, v)
+    d = torch.from_numpy(data).to(DEV)
+    with pytest.raises(RuntimeError, match="contract"):
+        vops.yuv420_to_clip(d, [1], 3, 46, 34, stride, pl, 16, 12, filter="antialias")
+    with pytest.raises(RuntimeError, match="contract"):
+        vops.yuv420_to_clip(d, [-1], 3, 46, 34, stride, pl, 16, 12, filter="antialias")
+    with pytest.raises(RuntimeError, match="contract"):          # planes past the stride
+        vops.yuv420_to_clip(d, [0], 3, 46, 34, stride - 1, pl, 16, 12, filter="antialias")
+    out = torch.full((1, 3, 12, 16, 4), 7.0, device=DEV)
+    with pytest.raises(RuntimeError, match="code -5"):
+        kernels().yuv420_to_clip(d.data_ptr(), d.numel(), [0], None, 3, 46, 34, stride, pl[:3],
+                                 pl[3:6], 1, out.data_ptr(), 16, 12, (-2.0, -1.0, 50.0, 37.0),
+                                 vops.KINETICS_MEAN, vops.KINETICS_STD, False,
+                                 torch.cuda.current_stream(DEV).cuda_stream, antialias=True)
+    torch.cuda.synchronize()
+    assert torch.all(out == 7.0)
+
+
+# -- the default is untouched -------------------------------------------------------------------
+def y4m_file(path, w, h, frames, seed):
+    y, u, v = orc.noise_planes(w, h, frames, seed)
+    y4m.write_y4m(str(path), [(y[f], u[f], v[f]) for f in range(frames)])
+    return y, u, v
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_filter_absent_is_filter_bilinear_byte_for_byte(tmp_path, dtype):
+    y, u, v = orc.noise_planes(46, 34, 3, 77)
+    data, stride, pl = orc.pack_i420(y, u, v)
+    buf = torch.from_numpy(data).to(DEV)
+    for matrix in vops.MATRICES:
+        for crop in (None, (-2, -1, 50, 37)):
+            a = vops.yuv420_to_clip(buf, [0], 3, 46, 34, stride, pl, 24, 16, crop=crop,
+                                    dtype=dtype, matrix=matrix)
+            b = vops.yuv420_to_clip(buf, [0], 3, 46, 34, stride, pl, 24, 16, crop=crop,
+                                    dtype=dtype, matrix=matrix, filter="bilinear")
+            torch.cuda.synchronize()
+            assert torch.equal(a.view(torch.uint8), b.view(torch.uint8)), (matrix, crop)
+    y4m_file(tmp_path / "a.y4m", 98, 62, 10, 9862)
+    kw = dict(clip_length=4, height=12, width=16, dtype=dtype, crop="center")
+    outs = []
+    for extra in ({}, {"filter": "bilinear"}):
+        dec = Y4mDecoder(DEV, **kw, **extra)
+        vid, _ = dec.probe(str(tmp_path / "a.y4m"))
+        outs.append(dec.decode(vid, [5, 0]))
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0].view(torch.uint8), outs[1].view(torch.uint8))
+    for entropy in ("host", "gpu"):
+        outs = []
+        for extra in ({}, {"filter": "bilinear"}):
+            dec = MjpegDecoder(DEV, clip_length=2, height=11, width=15, dtype=dtype,
+                               entropy=entropy, **extra)
+            vid, _ = dec.probe(os.path.join(GOLDEN, "noise_q75_opt.mjpeg"))
+            outs.append(dec.decode(vid, [0]))
+            dec.drain()
+        torch.cuda.synchronize()
+        assert torch.equal(outs[0].view(torch.uint8), outs[1].view(torch.uint8)), entropy
+
+
+# -- the decoders and the loader ----------------------------------------------------------------
+def test_y4m_decoder_antialias_against_oracle(tmp_path):
+    """98x62, 10 frames, the centred 62x62 box -> 16x12 (scales 3.9 / 5.2)."""
+    y, u, v = y4m_file(tmp_path / "a.y4m", 98, 62, 10, 9862)
+    dec = Y4mDecoder(DEV, clip_length=4, height=12, width=16, dtype=torch.float32, crop="center",
+                     filter="antialias")
+    dec.warmup(1)
+    vid, n = dec.probe(str(tmp_path / "a.y4m"))
+    assert n == 10
+    starts = [5, 0]
+    got = dec.decode(vid, starts)
+    torch.cuda.synchronize()
+    assert tuple(got.shape) == (2, 4, 12, 16, 4)
+    frames = [s + f for s in starts for f in range(4)]
+    ref, _, d, tol = aa.tolerance_aa(y[frames], u[frames], v[frames], 16, 12, (18, 0, 62, 62),
+                                     "bt601")
+    assert tol <= orc.TOL_CEILING
+    check_against_oracle(got.view(8, 12, 16, 4), ref, d, tol, DEV, "Y4mDecoder antialias")
+
+
+def test_mjpeg_decoder_antialias_host_and_gpu_entropy_equal_the_cpu_decoder():
+    name = "noise_q75_opt"
+    W, H, _ = GOLDEN_STREAMS[name]
+    path = os.path.join(GOLDEN, name + ".mjpeg")
+    kw = dict(clip_length=2, height=H // 3, width=W // 3, dtype=torch.float32,
+              filter="antialias")
+    cpu = MjpegDecoder(CPU, **kw)
+    want = cpu.decode(cpu.probe(path)[0], [0])
+    # the tolerance of the clip stage on this stream's planes
+    data = np.fromfile(path, dtype=np.uint8)
+    idx = mjpeg.read_index(path)
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+    planes = [mjpeg.decode_reference(frame_bytes(data, idx, i))["planes_u8"] for i in range(2)]
+    py, pu, pv = (np.stack([np.asarray(p[k]) for p in planes]) for k in range(3))
+    _, _, d, tol = aa.tolerance_aa(py[:, :H, :W], pu[:, :ch, :cw], pv[:, :ch, :cw], W // 3,
+                                   H // 3, None, "jfif")
+    assert tol <= orc.TOL_CEILING
+    for entropy in ("host", "gpu"):
+        dec = MjpegDecoder(DEV, entropy=entropy, **kw)
+        dec.warmup(1)
+        got = dec.decode(dec.probe(path)[0], [0])
+        dec.drain()
+        torch.cuda.synchronize()
+        err = float((got.cpu() - want).abs().max())
+        print("MjpegDecoder antialias entropy=%s: d = %.3g, tolerance = %.3g, max |gpu - cpu "
+              "decoder| = %.3g" % (entropy, d, tol, err))
+        assert err <= tol, (entropy, err, tol)
+
+
+@pytest.mark.parametrize("entropy", ["host", "gpu"])
+def test_gpu_decoder_against_pils_resized_rgb(entropy):
+    for name in sorted(GOLDEN_STREAMS):
+        check_pil_resized_rgb(name, DEV, entropy=entropy)
+
+
+def test_loader_with_antialias_fills_a_slot_of_the_advertised_shape(tmp_path):
+    from rnb_amd.models.r2p1d.model import R2P1DLoader
+    from rnb_amd.timecard import TimeCard
+    y, u, v = y4m_file(tmp_path / "a.y4m", 98, 62, 10, 9862)
+    loader = R2P1DLoader(DEV, decoder="y4m", num_clips_population=[1], num_clips_weights=[1],
+                         seed=0, dtype="fp32", warmup=1, decoder_args={"filter": "antialias"})
+    assert isinstance(loader.decoder, Y4mDecoder) and loader.decoder.filter == "antialias"
+    (shape,) = R2P1DLoader.output_shape_for(dtype="fp32")
+    slot = torch.full(shape, 7.0, device=DEV)
+    tc = TimeCard(13)
+    (frames,), _, tc = loader.call_into((None,), str(tmp_path / "a.y4m"), tc, (slot,))
+    torch.cuda.synchronize()
+    assert tc.num_clips == 1 and frames.data_ptr() == slot.data_ptr()
+    assert tuple(frames.shape) == (1,) + tuple(shape[1:]) and torch.all(slot[1:] == 7.0)
+    _, starts = tc.extra["clip_src"]
+    fr = [starts[0] + f for f in range(8)]
+    ref, _, d, tol = aa.tolerance_aa(y[fr], u[fr], v[fr], 112, 112, None, "bt601")
+    assert tol <= orc.TOL_CEILING
+    check_against_oracle(frames.view((8,) + tuple(shape[2:])), ref, d, tol, DEV, "loader slot")
