@@ -17,7 +17,8 @@ Stacks ``batch`` incoming tensors along dim 0 and emits them with a
   straight into this stage's output slot (``gather_into_output``), so a video
   is copied once (producer slot -> batch slot) instead of clone + cat + slot
   copy;
-* ``dtype`` follows the pipeline's precision (fp32 NDHWC4 clips by default).
+* ``dtype`` follows the pipeline's precision (fp32 NDHWC4 clips by default),
+  ``clip_length`` its clips' frame count (8, 16 or 32; default 8).
 """
 import time
 
@@ -27,16 +28,16 @@ from .runner_model import RunnerModel
 from .timecard import TimeCardList
 
 
-def _clip_spec(dtype):
-    from .models.r2p1d.model import CLIP_SHAPE, _dtype, clip_channels
-    return CLIP_SHAPE + (clip_channels(dtype),), _dtype(dtype)
+def _clip_spec(dtype, clip_length=8):
+    from .models.r2p1d.model import _dtype, clip_channels, clip_shape
+    return clip_shape(clip_length) + (clip_channels(dtype),), _dtype(dtype)
 
 
 class Batcher(RunnerModel):
     gather_into_output = True
 
     def __init__(self, device, batch=1, max_rows=15, max_wait_ms=None, dtype=None,
-                 **unused):
+                 clip_length=8, **unused):
         super().__init__(device)
         self.batch = int(batch)
         self.max_rows = int(max_rows)
@@ -44,7 +45,7 @@ class Batcher(RunnerModel):
         self.stacked_tensors = []
         self.stacked_time_cards = []
         self.first_ts = None
-        self.clip_shape, self.dtype = _clip_spec(dtype)
+        self.clip_shape, self.dtype = _clip_spec(dtype, clip_length)
         self._buf = None
 
     @staticmethod
@@ -52,8 +53,8 @@ class Batcher(RunnerModel):
         return ((15,) + _clip_spec(None)[0],)
 
     @classmethod
-    def output_shape_for(cls, max_rows=15, dtype=None, **kwargs):
-        return ((int(max_rows),) + _clip_spec(dtype)[0],)
+    def output_shape_for(cls, max_rows=15, dtype=None, clip_length=8, **kwargs):
+        return ((int(max_rows),) + _clip_spec(dtype, clip_length)[0],)
 
     @classmethod
     def output_dtypes_for(cls, dtype=None, **kwargs):

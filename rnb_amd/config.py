@@ -232,11 +232,33 @@ def parse_pipeline(config: Dict[str, Any]) -> PipelineSpec:
                                 else DEFAULT_NUM_SHARED_TENSORS),
             kwargs=step_kwargs, slot_dtype=step.get("slot_dtype"),
             auto_slots=not isinstance(step.get("num_shared_tensors"), int)))
+    _check_clip_lengths(steps)
     return PipelineSpec(video_path_iterator=config["video_path_iterator"],
                         steps=steps,
                         iterator_kwargs=config.get("video_path_iterator_kwargs",
                                                    {}),
                         raw=config)
+
+
+def _check_clip_lengths(steps: List[StepSpec]) -> None:
+    """Producer and consumer steps must agree on ``clip_length`` (frames per
+    clip; set once in 'defaults' or per step / queue group, default 8): the
+    producer's output slots and the consumer's input are sized by it."""
+    def lengths(step: StepSpec) -> set:
+        return {g.kwargs.get("clip_length", 8) for g in step.groups}
+
+    def name(i: int) -> str:
+        return "step %d (%s)" % (i, steps[i].model)
+
+    for i, step in enumerate(steps):
+        mine = lengths(step)
+        if len(mine) > 1:
+            raise ConfigError("queue groups of %s disagree on clip_length: %s"
+                              % (name(i), sorted(mine, key=repr)))
+        if i > 0 and mine != lengths(steps[i - 1]):
+            raise ConfigError("clip_length %r of producer %s does not match clip_length %r "
+                              "of consumer %s" % (next(iter(lengths(steps[i - 1]))),
+                                                  name(i - 1), next(iter(mine)), name(i)))
 
 
 def load_pipeline(path: str) -> PipelineSpec:

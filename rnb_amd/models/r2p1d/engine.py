@@ -47,8 +47,9 @@ from ...ops.conv_f32 import (F32_ALIGN, WINOT_MIN_T, ConvLayerF32, RangeGuard, f
                               h3_enabled)
 from ...ops.video import (Head, IN_CHANNELS_P, ndhwc_to_ncdhw, ncdhw_to_ndhwc,
                           packed_input_shape)
-from .network import (LAYER_CHANNELS, LAYER_INPUT_CTHW, LAYER_OUTPUT_CTHW,
-                      R2Plus1DLayerWrapper, SpatioTemporalConv)
+from .network import (DEFAULT_CLIP_LENGTH, LAYER_CHANNELS, LAYER_INPUT_CTHW,
+                      LAYER_OUTPUT_CTHW, R2Plus1DLayerWrapper, SpatioTemporalConv,
+                      check_clip_length, intermediate_channels, layer_geometry)
 
 DEFAULT_BUCKETS = (1, 2, 3, 4, 5, 6, 8, 10, 12, 15, 16, 20, 24, 30, 32, 40, 45, 48,
                    60, 64, 80, 96, 128)
@@ -97,9 +98,75 @@ def boundary_channels_p(layer_idx: int, dtype=torch.bfloat16) -> int:
     return pad_to(LAYER_INPUT_CTHW[layer_idx][0], align)
 
 
-def boundary_shape(layer_idx: int, n: int, dtype=torch.bfloat16) -> Tuple[int, ...]:
-    c, t, h, w = LAYER_INPUT_CTHW[layer_idx]
+def boundary_shape(layer_idx: int, n: int, dtype=torch.bfloat16,
+                   clip_length: int = DEFAULT_CLIP_LENGTH) -> Tuple[int, ...]:
+    c, t, h, w = layer_geometry(clip_length)[0][layer_idx]
     return (n, t, h, w, boundary_channels_p(layer_idx, dtype))
+
+
+# per-launch size limits of the kernels (size arithmetic only, no allocation):
+# the conv launchers take tensors up to the buffer-resource limit in bytes
+# (csrc: 0x7FFFFF00, error -5 / -6), the BatchNorm kernels index float4s with
+# 32 bits (csrc/bn_ops.hip, error -3)
+CONV_MAX_BYTES = 0x7FFFFF00
+BN_MAX_ELEMS = 0x7FFFFFFF * 4
+
+
+def activation_elems_per_clip(start_idx: int, end_idx: int, dtype=torch.float32,
+                              clip_length: int = DEFAULT_CLIP_LENGTH) -> int:
+    """Elements per clip of the largest activation layers [start_idx, end_idx]
+    hold: the boundary tensors of the geometry table and each layer's largest
+    (2+1)D intermediate (the first spatial conv's output: the layer's input
+    frame count at its output H x W, channels padded as the engine pads them)."""
+    inp, out = layer_geometry(clip_length)
+    f32 = dtype == torch.float32
+    align = F32_ALIGN if f32 else CH_ALIGN
+    worst = 0
+    for idx in range(start_idx, end_idx + 1):
+        c, t, h, w = inp[idx]
+        cp = boundary_channels_p(idx, dtype)
+        worst = max(worst, t * h * w * cp)
+        cin, cout = LAYER_CHANNELS[idx]
+        ho, wo = (h // 2, w // 2) if idx != 2 else (h, w)
+        kernel = (3, 7, 7) if idx == 1 else (3, 3, 3)
+        mids = [intermediate_channels(cin, cout, kernel)]
+        if idx > 1:
+            mids.append(intermediate_channels(cout, cout, kernel))
+        # fp32 pads a temporal Winograd conv's input to 16 channels (_stconv)
+        midp = max(pad_to(m, 16 if f32 else align) for m in mids)
+        worst = max(worst, t * ho * wo * midp)
+        if out[idx] is not None:
+            co, to, ho2, wo2 = out[idx]
+            worst = max(worst, to * ho2 * wo2 * pad_to(co, align))
+    return worst
+
+
+def max_clips_limit(start_idx: int, end_idx: int, dtype=torch.float32,
+                    clip_length: int = DEFAULT_CLIP_LENGTH) -> int:
+    """Largest ``max_clips`` whose calls every kernel of the layer range can
+    index. Rows per clip grow with the clip length, so the bound shrinks with
+    it. The fp32 conv launches are split by clips (ConvLayerF32.chunk_clips),
+    so at fp32 the per-call bound is the BatchNorm kernels' element limit; the
+    bf16 conv launchers take a whole call, so at bf16 it is their byte limit."""
+    per = activation_elems_per_clip(start_idx, end_idx, dtype, clip_length)
+    if dtype == torch.float32:
+        return BN_MAX_ELEMS // per
+    return CONV_MAX_BYTES // (2 * per)
+
+
+def check_max_clips(max_clips: int, start_idx: int, end_idx: int, dtype=torch.float32,
+                    clip_length: int = DEFAULT_CLIP_LENGTH) -> int:
+    """``max_clips`` if calls of that many clips fit the kernels' per-launch
+    limits, else ValueError -- raised at construction, so that no launcher
+    error surfaces while a graph bucket is captured."""
+    fit = max_clips_limit(start_idx, end_idx, dtype, clip_length)
+    if int(max_clips) > fit:
+        raise ValueError("max_clips %d is too large at clip_length %d for layers %d..%d (%s): "
+                         "the largest activation passes the kernels' per-launch limit; the "
+                         "largest max_clips that fits is %d"
+                         % (max_clips, clip_length, start_idx, end_idx,
+                            "fp32" if dtype == torch.float32 else "bf16", fit))
+    return int(max_clips)
 
 
 class PlanOp:
@@ -117,7 +184,10 @@ class PlanOp:
 
 class R2P1DEngine:
     def __init__(self, net: R2Plus1DLayerWrapper, device: torch.device,
-                 backend: str = "hip", bn_mode: str = "eval", dtype=torch.bfloat16):
+                 backend: str = "hip", bn_mode: str = "eval", dtype=torch.bfloat16,
+                 clip_length: int = DEFAULT_CLIP_LENGTH):
+        self.clip_length = check_clip_length(clip_length)
+        self.layer_in, self.layer_out = layer_geometry(self.clip_length)
         if backend not in ("hip", "torch", "module"):
             raise ValueError("unknown backend %r" % backend)
         if bn_mode not in ("eval", "batch"):
@@ -275,7 +345,7 @@ class R2P1DEngine:
 
     def _build(self, body):
         cur = "x"
-        self._thw = {"x": tuple(LAYER_INPUT_CTHW[self.start_idx][1:])}
+        self._thw = {"x": tuple(self.layer_in[self.start_idx][1:])}
         for idx in range(self.start_idx, self.end_idx + 1):
             if idx == 1:
                 cur = self._stconv(body.conv1, cur, None, False, None, "conv1")
@@ -330,7 +400,7 @@ class R2P1DEngine:
     def input_shape(self, n: int, packed: bool = False) -> Tuple[int, ...]:
         """Boundary input shape; ``packed`` = the stem's pair-packed layout
         (only when ``accepts_packed_input``)."""
-        shape = boundary_shape(self.start_idx, n, self.dtype)
+        shape = boundary_shape(self.start_idx, n, self.dtype, self.clip_length)
         if not packed:
             return shape
         if not self.accepts_packed_input:
@@ -347,15 +417,15 @@ class R2P1DEngine:
     def output_shape(self, n: int) -> Tuple[int, ...]:
         if self.end_idx == 5:
             return (n, self.num_classes)
-        return boundary_shape(self.end_idx + 1, n, self.dtype)
+        return boundary_shape(self.end_idx + 1, n, self.dtype, self.clip_length)
 
     def output_dtype(self):
         return torch.float32 if self.end_idx == 5 else self.dtype
 
     def flops_per_clip(self) -> int:
-        """Useful FLOPs for one 8x112x112 clip through this layer range."""
+        """Useful FLOPs for one clip_length x 112 x 112 clip through this layer range."""
         total = 0
-        c, t, h, w = LAYER_INPUT_CTHW[self.start_idx]
+        c, t, h, w = self.layer_in[self.start_idx]
         shapes = {"x": (t, h, w)}
         for op in self.ops:
             g = getattr(op.layer, "nominal_geom", op.layer.geom)
@@ -764,6 +834,9 @@ class GraphedEngine:
         if engine.bn_mode == "batch" and not engine.f32:
             raise ValueError("graphed bn_mode='batch' (per-video statistics) is fp32 only")
         self.engine = engine
+        self.clip_length = engine.clip_length
+        check_max_clips(max_clips, engine.start_idx, engine.end_idx, engine.dtype,
+                        engine.clip_length)
         # bn_mode='batch': each bucket graph reads its videos' clip offsets
         # from a static device tensor [b + 1] (padded with empty videos), so
         # the bucket's padding rows stay outside every video's statistics

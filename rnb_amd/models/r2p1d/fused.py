@@ -27,8 +27,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from ...ops import video as vops
-from .engine import R2P1DEngine
-from .model import CLIP_SHAPE, build_network
+from .engine import R2P1DEngine, _as_dtype, check_max_clips
+from .model import build_network, clip_shape
+from .network import DEFAULT_CLIP_LENGTH, check_clip_length
 
 DEFAULT_BUCKETS = (1, 2, 4, 8, 12, 16, 24, 32, 48, 64, 80, 96, 128, 160, 192, 256)
 
@@ -71,7 +72,7 @@ class Replica:
         """Decoder stage of the graph: fp32 runs NVVL's per-frame work on NV12
         surfaces at 340x256 (as the pipeline loader does); the bf16 path keeps
         the 112x112 generator + the stem's packed preprocess."""
-        F, H, W = CLIP_SHAPE
+        F, H, W = clip_shape(self.engine.clip_length)
         if self.dtype == torch.float32:
             surf = vops.nv12gen(bg.meta[0], bg.meta[1], F, vops.SOURCE_H, vops.SOURCE_W,
                                 self.device)
@@ -82,7 +83,6 @@ class Replica:
             vops.preprocess(surf, out=bg.frames, packed=self.packed, dtype=self.dtype)
 
     def _body(self, bg: _BucketGraph, b: int):
-        F, H, W = CLIP_SHAPE
         self._decode(bg)
         logits = self.engine.forward(bg.frames, packed=self.packed)
         bg.logits = logits
@@ -105,7 +105,6 @@ class Replica:
             self.stream.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self.pool, stream=self.stream):
-                F, H, W = CLIP_SHAPE
                 self._decode(bg)
                 bg.logits = self.engine.forward(bg.frames, packed=self.packed)
                 _, bg.argmax = vops.video_reduce(bg.logits, bg.offsets, sums=bg.sums)
@@ -115,7 +114,6 @@ class Replica:
         return bg
 
     def _run_eager(self, bg):
-        F, H, W = CLIP_SHAPE
         self._decode(bg)
         logits = self.engine.forward(bg.frames, packed=self.packed)
         vops.video_reduce(logits, bg.offsets, sums=bg.sums)
@@ -168,9 +166,13 @@ class FusedR2P1D:
     def __init__(self, device: torch.device, depth: int = 34, num_classes: int = 400,
                  replicas: int = 1, max_clips: int = 256, max_videos: int = 64,
                  buckets: Sequence[int] = DEFAULT_BUCKETS, autotune: bool = True,
-                 seed: int = 0, ckpt_path: Optional[str] = None, dtype="bf16"):
+                 seed: int = 0, ckpt_path: Optional[str] = None, dtype="bf16",
+                 clip_length: int = DEFAULT_CLIP_LENGTH):
+        clip_length = check_clip_length(clip_length)
+        check_max_clips(max_clips, 1, 5, _as_dtype(dtype), clip_length)
         net = build_network(1, 5, num_classes, depth=depth, seed=seed, ckpt_path=ckpt_path)
-        self.engine = R2P1DEngine(net, device, backend="hip", dtype=dtype)
+        self.engine = R2P1DEngine(net, device, backend="hip", dtype=dtype,
+                                  clip_length=clip_length)
         self.device = device
         self.autotune = autotune
         self.replicas = [Replica(self.engine, max_clips, max_videos, buckets)

@@ -47,13 +47,19 @@ from ...video_path_provider import (DirectoryVideoPathIterator,
                                     SyntheticVideoPathIterator, VideoPathIterator)
 from .decoder import make_decoder
 from .engine import (GraphedEngine, R2P1DEngine, boundary_channels_p, boundary_shape,
-                     parse_bucket_step)
-from .network import (LAYER_INPUT_CTHW, R2Plus1DLayerWrapper, init_random_,
-                      load_reference_state_dict, normalize_layer_sizes)
+                     check_max_clips, parse_bucket_step)
+from .network import (DEFAULT_CLIP_LENGTH, LAYER_INPUT_CTHW, R2Plus1DLayerWrapper,
+                      check_clip_length, init_random_, load_reference_state_dict,
+                      normalize_layer_sizes)
 from .sampler import R2P1DSampler
 
 DEFAULT_MAX_CLIPS = 15
 CLIP_SHAPE = (8, 112, 112)
+
+
+def clip_shape(clip_length=DEFAULT_CLIP_LENGTH):
+    """(frames, height, width) of a decoded clip; CLIP_SHAPE at the default."""
+    return (check_clip_length(clip_length),) + CLIP_SHAPE[1:]
 # output sampling for numerics checks of a served run (bench.py): the loader
 # tags every CHECK_EVERY-th video with its decode source, and a final-step
 # runner with RNB_CHECK_DIR set writes those videos' logits there
@@ -114,11 +120,18 @@ def build_network(start_index: int, end_index: int, num_classes: int = 400,
 def build_engine(device: torch.device, start_index=1, end_index=5, num_classes=400,
                  layer_sizes=None, depth=None, backend="auto", bn_mode="eval", seed=0,
                  ckpt_path=None, max_clips=DEFAULT_MAX_CLIPS, use_graphs=True,
-                 autotune=True, dtype=None, buckets=None):
+                 autotune=True, dtype=None, buckets=None,
+                 clip_length=DEFAULT_CLIP_LENGTH):
+    clip_length = check_clip_length(clip_length)
+    backend = _resolve_backend(backend, device)
+    if backend == "hip":
+        # before any weight is built: a call of max_clips clips must fit the
+        # kernels' per-launch limits at this clip length
+        check_max_clips(max_clips, start_index, end_index, _dtype(dtype), clip_length)
     net = build_network(start_index, end_index, num_classes, layer_sizes, depth, seed,
                         ckpt_path)
-    backend = _resolve_backend(backend, device)
-    eng = R2P1DEngine(net, device, backend=backend, bn_mode=bn_mode, dtype=_dtype(dtype))
+    eng = R2P1DEngine(net, device, backend=backend, bn_mode=bn_mode, dtype=_dtype(dtype),
+                      clip_length=clip_length)
     # batch-statistics BN is graphed for fp32 (per-video segments from a
     # static offsets tensor); bf16 batch BN runs eagerly
     if backend == "hip" and use_graphs and (bn_mode == "eval" or _dtype(dtype) == torch.float32):
@@ -127,8 +140,10 @@ def build_engine(device: torch.device, start_index=1, end_index=5, num_classes=4
     return eng
 
 
-def _to_boundary(x: torch.Tensor, start_index: int, dtype=torch.float32) -> torch.Tensor:
-    """Accept the reference NCDHW fp32 layout as well as the NDHWC boundary."""
+def _to_boundary(x: torch.Tensor, start_index: int, dtype=torch.float32,
+                 clip_length=DEFAULT_CLIP_LENGTH) -> torch.Tensor:
+    """Accept the reference NCDHW fp32 layout as well as the NDHWC boundary
+    (the frame count is the tensor's own: both layouts carry it)."""
     cp = boundary_channels_p(start_index, dtype)
     if x.dim() == 5 and x.shape[-1] == cp and x.shape[1] != LAYER_INPUT_CTHW[start_index][0]:
         return x.to(dtype).contiguous()
@@ -148,8 +163,9 @@ class R2P1DRunner(RunnerModel):
                  bn_mode=None, seed=0, ckpt_path=None, max_clips=DEFAULT_MAX_CLIPS,
                  warmup=3, use_graphs=True, autotune=True, dtype=None,
                  max_batch_videos=1, batch_wait_ms=0.0, bucket_step=None, lanes=1,
-                 stream_priority=0, **unused):
+                 stream_priority=0, clip_length=DEFAULT_CLIP_LENGTH, **unused):
         super().__init__(device)
+        self.clip_length = clip_length = check_clip_length(clip_length)
         if start_index < 1:
             raise ValueError("Wrong layer index for the starting layer! The start_index "
                              "(%d) should be more than or equal to 1." % start_index)
@@ -166,7 +182,8 @@ class R2P1DRunner(RunnerModel):
         buckets = parse_bucket_step(bucket_step, self.max_clips)
         self.engine = build_engine(device, start_index, end_index, num_classes,
                                    layer_sizes, depth, backend, bn_mode, seed, ckpt_path,
-                                   self.max_clips, use_graphs, autotune, self.dtype, buckets)
+                                   self.max_clips, use_graphs, autotune, self.dtype, buckets,
+                                   clip_length)
         # lanes > 1: that many graphed engines (own weights copy, BN buffers and
         # graph pool each; the same seed / checkpoint, so identical outputs) on
         # their own streams, calls rotating over them. One-video calls leave
@@ -181,7 +198,7 @@ class R2P1DRunner(RunnerModel):
             self._lane_engines.append(build_engine(
                 device, start_index, end_index, num_classes, layer_sizes, depth, backend,
                 bn_mode, seed, ckpt_path, self.max_clips, use_graphs, autotune, self.dtype,
-                buckets))
+                buckets, clip_length))
         # lane streams at DEFAULT priority, not the runner's (runner.py passes
         # the queue group's, e.g. the high-priority 15-clip replica's): the
         # round-4 advice asked for the runner's; measured interleaved, it costs
@@ -209,7 +226,8 @@ class R2P1DRunner(RunnerModel):
                                             torch.cuda.memory_reserved(device) / 2 ** 30),
                       flush=True)
         n = min(10, self.max_clips)
-        tmp = torch.randn(boundary_shape(start_index, n, self.dtype)).to(self.dtype).to(device)
+        tmp = torch.randn(boundary_shape(start_index, n, self.dtype, clip_length)
+                          ).to(self.dtype).to(device)
         for _ in range(warmup):
             self.engine(tmp)
         if device.type == "cuda":
@@ -337,14 +355,16 @@ class R2P1DRunner(RunnerModel):
         else:
             if self._gather_buf is None:
                 self._gather_buf = torch.empty(
-                    boundary_shape(self.start_index, self.max_clips, self.dtype),
+                    boundary_shape(self.start_index, self.max_clips, self.dtype,
+                                   self.clip_length),
                     dtype=self.dtype, device=self.device)
             static_in = self._gather_buf
         self._gather_ptr = static_in.data_ptr()
         return (static_in,)
 
     def input_shape(self):
-        return (boundary_shape(self.start_index, self.max_clips, self.dtype),)
+        return (boundary_shape(self.start_index, self.max_clips, self.dtype,
+                               self.clip_length),)
 
     @staticmethod
     def output_shape():
@@ -352,10 +372,12 @@ class R2P1DRunner(RunnerModel):
 
     @classmethod
     def output_shape_for(cls, start_index=1, end_index=5, num_classes=400,
-                         max_clips=DEFAULT_MAX_CLIPS, dtype=None, **kwargs):
+                         max_clips=DEFAULT_MAX_CLIPS, dtype=None,
+                         clip_length=DEFAULT_CLIP_LENGTH, **kwargs):
+        clip_length = check_clip_length(clip_length)
         if end_index == 5:
             return ((max_clips, num_classes),)
-        return (boundary_shape(end_index + 1, max_clips, _dtype(dtype)),)
+        return (boundary_shape(end_index + 1, max_clips, _dtype(dtype), clip_length),)
 
     @classmethod
     def output_dtypes_for(cls, end_index=5, dtype=None, **kwargs):
@@ -402,7 +424,8 @@ class R2P1DRunner(RunnerModel):
                         torch.cuda.current_stream(self.device).wait_event(self.last_event)
                     write_sample(self._check_dir, tc.id, "runner", src[0], src[1],
                                  y[off:off + n].float().cpu().numpy(), self.bn_mode,
-                                 str(self.dtype), call_rows=call_rows)
+                                 str(self.dtype), call_rows=call_rows,
+                                 clip_length=self.clip_length)
             off += n
 
     def __call__(self, tensors, non_tensors, time_card):
@@ -439,7 +462,7 @@ class R2P1DRunner(RunnerModel):
                 self._guard_calls.append((eng, y, eng.last_call))
             return y
         self._gather_ptr = None
-        x = _to_boundary(x, self.start_index, self.dtype)
+        x = _to_boundary(x, self.start_index, self.dtype, self.clip_length)
         if isinstance(eng, GraphedEngine) and x.shape[0] > 0:
             y = eng.forward(x, clip_offsets=offs) if self.bn_mode == "batch" else eng(x)
             if eng.range_guard is not None:
@@ -472,7 +495,8 @@ class R2P1DVideoPathIterator(VideoPathIterator):
 
 
 class R2P1DLoader(RunnerModel):
-    """Video path -> sampled clips, NDHWC [n, 8, 112, 112, C] (fp32 C=4, bf16 C=8)."""
+    """Video path -> sampled clips, NDHWC [n, clip_length, 112, 112, C] (fp32 C=4,
+    bf16 C=8; clip_length 8, 16 or 32 frames, default 8)."""
 
     # decode kernels are tiny and gate the consumers: run them on a
     # high-priority HIP stream so they do not queue behind the conv kernels
@@ -480,13 +504,16 @@ class R2P1DLoader(RunnerModel):
 
     def __init__(self, device, num_clips_population=(1, 15), num_clips_weights=(10, 1),
                  decoder="synthetic", seed=None, max_clips=DEFAULT_MAX_CLIPS,
-                 warmup=3, dtype=None, decoder_args=None, **unused):
+                 warmup=3, dtype=None, decoder_args=None,
+                 clip_length=DEFAULT_CLIP_LENGTH, **unused):
         super().__init__(device)
-        self.sampler = R2P1DSampler(clip_length=CLIP_SHAPE[0],
+        self.clip_length = check_clip_length(clip_length)
+        self.sampler = R2P1DSampler(clip_length=self.clip_length,
                                     num_clips_population=num_clips_population,
                                     num_clips_weights=num_clips_weights, seed=seed)
         self.dtype = _dtype(dtype)
-        self.decoder = make_decoder(decoder, device, *CLIP_SHAPE, dtype=self.dtype,
+        self.decoder = make_decoder(decoder, device, *clip_shape(self.clip_length),
+                                    dtype=self.dtype,
                                     decoder_args=decoder_args)
         self.max_clips = max_clips
         self.decoder.warmup(warmup)
@@ -546,8 +573,9 @@ class R2P1DLoader(RunnerModel):
         return ((DEFAULT_MAX_CLIPS,) + CLIP_SHAPE + (clip_channels(None),),)
 
     @classmethod
-    def output_shape_for(cls, max_clips=DEFAULT_MAX_CLIPS, dtype=None, **kwargs):
-        return ((max_clips,) + CLIP_SHAPE + (clip_channels(dtype),),)
+    def output_shape_for(cls, max_clips=DEFAULT_MAX_CLIPS, dtype=None,
+                         clip_length=DEFAULT_CLIP_LENGTH, **kwargs):
+        return ((max_clips,) + clip_shape(clip_length) + (clip_channels(dtype),),)
 
     @classmethod
     def output_dtypes_for(cls, dtype=None, **kwargs):
@@ -561,16 +589,20 @@ class R2P1DSingleStep(RunnerModel):
                  block_type=None, num_clips_population=(1, 15), num_clips_weights=(10, 1),
                  decoder="synthetic", seed=None, model_seed=0, backend="auto",
                  bn_mode=None, ckpt_path=None, max_clips=DEFAULT_MAX_CLIPS, warmup=3,
-                 use_graphs=True, autotune=True, dtype=None, decoder_args=None, **unused):
+                 use_graphs=True, autotune=True, dtype=None, decoder_args=None,
+                 clip_length=DEFAULT_CLIP_LENGTH, **unused):
         super().__init__(device)
+        clip_length = check_clip_length(clip_length)
         self.loader = R2P1DLoader(device, num_clips_population, num_clips_weights,
                                   decoder=decoder, seed=seed, max_clips=max_clips,
-                                  warmup=warmup, dtype=dtype, decoder_args=decoder_args)
+                                  warmup=warmup, dtype=dtype, decoder_args=decoder_args,
+                                  clip_length=clip_length)
         self.runner = R2P1DRunner(device, 1, 5, num_classes,
                                   layer_sizes=layer_sizes, depth=depth, backend=backend,
                                   bn_mode=bn_mode, seed=model_seed, ckpt_path=ckpt_path,
                                   max_clips=max_clips, warmup=warmup,
-                                  use_graphs=use_graphs, autotune=autotune, dtype=dtype)
+                                  use_graphs=use_graphs, autotune=autotune, dtype=dtype,
+                                  clip_length=clip_length)
 
     @property
     def range_guarded(self) -> bool:
@@ -626,8 +658,11 @@ class R2P1DAggregator(RunnerModel):
     different batches; a video is emitted once all ``aggregate`` segments
     arrived (reference model.py:238-285, with batching added)."""
 
-    def __init__(self, device, aggregate=1, **unused):
+    def __init__(self, device, aggregate=1, clip_length=DEFAULT_CLIP_LENGTH, **unused):
         super().__init__(device)
+        # sizes nothing by it (logit rows only); checked so that a pipeline's
+        # "defaults" value is validated at every step
+        self.clip_length = check_clip_length(clip_length)
         self.aggregate = int(aggregate)
         self.results = {}
         self._check_dir = os.environ.get("RNB_CHECK_DIR") or None
@@ -672,7 +707,7 @@ class R2P1DAggregator(RunnerModel):
                 from ...numerics import write_sample
                 self._checked += 1
                 write_sample(self._check_dir, tc.id, "aggregate", src[0], src[1], total,
-                             segments=self.aggregate)
+                             segments=self.aggregate, clip_length=self.clip_length)
             done_cards.append(TimeCard.merge(got))
             outs.append(int(total.argmax()))
         if not done_cards:

@@ -44,6 +44,34 @@ LAYER_OUTPUT_CTHW = {1: (64, 8, 56, 56), 2: (64, 8, 56, 56),
 LAYER_CHANNELS = {1: (3, 64), 2: (64, 64), 3: (64, 128), 4: (128, 256),
                   5: (256, 512)}
 
+DEFAULT_CLIP_LENGTH = 8
+# 8: the reference's clips; 16: the paper's / torchvision r2plus1d_18;
+# 32: the Kinetics / IG-65M R(2+1)D-34 checkpoints
+CLIP_LENGTHS = (8, 16, 32)
+
+
+def check_clip_length(clip_length, key: str = "clip_length") -> int:
+    """``clip_length`` as an int; ValueError (naming ``key``) unless 8, 16 or 32."""
+    if isinstance(clip_length, bool) or clip_length not in CLIP_LENGTHS:
+        raise ValueError("%s must be one of %s, got %r"
+                         % (key, ", ".join(str(c) for c in CLIP_LENGTHS), clip_length))
+    return int(clip_length)
+
+
+def layer_geometry(clip_length: int = DEFAULT_CLIP_LENGTH):
+    """(LAYER_INPUT_CTHW, LAYER_OUTPUT_CTHW) for ``clip_length`` x 112 x 112
+    clips: T is unchanged through conv1 and conv2 and ``(T - 1) // 2 + 1``
+    after each of conv3, conv4 and conv5 (their first block's stride-2
+    temporal conv, k 3, pad 1); H x W as at 8 frames."""
+    t = check_clip_length(clip_length)
+    t3 = (t - 1) // 2 + 1
+    t4 = (t3 - 1) // 2 + 1
+    inp = {1: (3, t, 112, 112), 2: (64, t, 56, 56), 3: (64, t, 56, 56),
+           4: (128, t3, 28, 28), 5: (256, t4, 14, 14)}
+    out = {1: (64, t, 56, 56), 2: (64, t, 56, 56), 3: (128, t3, 28, 28),
+           4: (256, t4, 14, 14), 5: None}
+    return inp, out
+
 
 def _triple(v):
     if isinstance(v, (list, tuple)):

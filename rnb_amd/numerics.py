@@ -43,14 +43,14 @@ def stratum_of(kind: str, clips: int, call_rows: int, large_clips: int = 15) -> 
 
 def write_sample(check_dir: str, card_id: int, kind: str, vid: int, starts, logits,
                  bn_mode: Optional[str] = None, dtype: Optional[str] = None,
-                 segments: int = 1, call_rows: int = 0) -> None:
+                 segments: int = 1, call_rows: int = 0, clip_length: int = 8) -> None:
     starts = np.asarray(starts, dtype=np.int64)
     stratum = stratum_of(kind, len(starts), int(call_rows))
     path = os.path.join(check_dir, "%s_v%d_p%d.npz" % (kind, card_id, os.getpid()))
     np.savez(path, kind=kind, vid=int(vid), starts=starts,
              logits=np.asarray(logits, dtype=np.float32), bn_mode=str(bn_mode),
              dtype=str(dtype), segments=int(segments), call_rows=int(call_rows),
-             stratum=stratum)
+             stratum=stratum, clip_length=int(clip_length))
 
 
 def recheck(check_dir: str, depth: int, device=None, seed: int = 0,
@@ -60,7 +60,7 @@ def recheck(check_dir: str, depth: int, device=None, seed: int = 0,
     none: pass the mode the runners served)."""
     import torch
     from .control import segment_bounds
-    from .models.r2p1d.model import CLIP_SHAPE, build_network
+    from .models.r2p1d.model import build_network, clip_shape
     from .models.r2p1d.engine import R2P1DEngine
     from .models.r2p1d.decoder import make_decoder
     files = sorted(glob.glob(os.path.join(check_dir, "*.npz")))
@@ -74,9 +74,14 @@ def recheck(check_dir: str, depth: int, device=None, seed: int = 0,
     if "None" in modes or len(modes) != 1:
         raise ValueError("BN mode of the samples is %s: pass bn_mode" % sorted(modes))
     mode = modes.pop()
+    # samples written before clips had a length carry none: 8 frames
+    lengths = {int(s["clip_length"]) if "clip_length" in s else 8 for s in samples}
+    if len(lengths) != 1:
+        raise ValueError("samples of several clip lengths %s in one check" % sorted(lengths))
+    clip_length = lengths.pop()
     mod = R2P1DEngine(build_network(1, 5, depth=depth, seed=seed), dev, backend="module",
-                      bn_mode=mode, dtype=torch.float32)
-    dec = make_decoder("synthetic", dev, *CLIP_SHAPE, dtype=torch.float32)
+                      bn_mode=mode, dtype=torch.float32, clip_length=clip_length)
+    dec = make_decoder("synthetic", dev, *clip_shape(clip_length), dtype=torch.float32)
     strata = {}
     t0 = time.time()
     with torch.no_grad():

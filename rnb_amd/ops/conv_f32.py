@@ -603,8 +603,11 @@ class ConvLayerF32:
         return x_shape is None or kernels().conv_h3t_pixels(variant, x_shape[1]) > 0
 
     def h3p_ok(self, x_shape=None) -> bool:
-        """The pixel-major temporal h3 kernel: h3t's conditions with T 8,
-        H * W % 16 == 0, Cin_p <= 160 and Cout_p <= 64 (its weights in LDS)."""
+        """The pixel-major temporal h3 kernel: h3t's conditions with H * W %
+        16 == 0 and the layer's weights in LDS -- Cin_p <= 160, Cout_p <= 64
+        at T 8, or in bands of 8 frames at 16 and 32; 256 < Cin_p <= 288 at
+        T 4 or 8, or in bands of 8 frames at 16 (csrc/conv_h3p.hip
+        rnb_conv_h3p_ok)."""
         if not self.h3t_ok(x_shape) or os.environ.get("RNB_H3P", "1") == "0":
             return False
         from .native import kernels

@@ -596,9 +596,10 @@ class Kernels:
                  out_scale: float, sums: int = 0, clip_seg: int = 0, stats_c: int = 0,
                  in_ss: int = 0, in_seg: int = 0) -> None:
         """Pixel-major persistent temporal h3 conv (csrc/conv_h3p.hip: 3x1x1
-        stride 1 pad (1, 0, 0), T 8, Cin_p <= 160, Cout_p <= 64, all weights
-        in LDS; ``blocks_per_cu`` persistent blocks per CU); the weights and
-        the other arguments as ``conv_h3t``."""
+        stride 1 pad (1, 0, 0), the shapes ``conv_h3p_ok`` accepts -- T 8 or a
+        multiple in 8-frame bands, Cin_p <= 160, Cout_p <= 64, or the conv3
+        form -- all weights in LDS; ``blocks_per_cu`` persistent blocks per
+        CU); the weights and the other arguments as ``conv_h3t``."""
         _check(self.lib.rnb_conv_h3p_launch(ctypes.byref(params), blocks_per_cu, stream,
                                             sums or None, clip_seg or None, stats_c, in_scale,
                                             out_scale, in_ss or None, in_seg or None),

@@ -6,6 +6,10 @@ interleaved rounds (alternating order, best round kept: the clocks settle
 differently per position, profiles/r3_x6_exp_interleaved.txt).
 
     python scripts/h3_layer_bench.py --clips 128 --cases k4,k8,k14 [--cids 1395,1396]
+    python scripts/h3_layer_bench.py --clip-length 16 --clips 64 --cases stemt,k4,k8 --only-h3
+
+``--clip-length`` (8, 16 or 32) scales every case's frame count from the
+8-frame table to that clip length's geometry (network.layer_geometry).
 
 Prints one line per (case, config): ms, fp32-equivalent TF/s and the
 16-bit MFMA utilisation an h3 config implies (3 products per fp32 product,
@@ -62,13 +66,21 @@ def main():
     ap.add_argument("--only-h3", action="store_true")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--clip-length", type=int, default=8,
+                    help="frames per clip (8, 16 or 32): the cases' T follows the geometry")
     args = ap.parse_args()
+    from rnb_amd.models.r2p1d.network import layer_geometry
+    t8, tl = layer_geometry(8)[0], layer_geometry(args.clip_length)[0]
+    # frame count at 8-frame clips -> at --clip-length (conv5's inner T = 1: its output's)
+    frames = {t8[i][1]: tl[i][1] for i in (1, 4, 5)}
+    frames[1] = (frames[2] - 1) // 2 + 1
     from rnb_amd.ops.conv import ConvGeom
     from rnb_amd.ops.conv_f32 import (F32_ALIGN, WINO_ALL, ConvLayerF32, is_h3, is_x6d)
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream(dev)
     for name in args.cases.split(","):
         cin, cout, k, s, p, (T, H, W), aff, ost = CASES[name]
+        T = frames[T]
         g = torch.Generator().manual_seed(0)
         fan = cin * k[0] * k[1] * k[2]
         w = torch.randn((cout, cin) + k, generator=g) * (2.0 / fan) ** 0.5
@@ -124,8 +136,8 @@ def main():
         for cid in sorted(times, key=times.get):
             tf = fl / times[cid] / 1e9
             util = "%5.1f%%" % (300.0 * tf / PEAK_16) if is_h3(cid) else "   - "
-            print("%-5s N=%d cid %4d  %8.3f ms  %6.1f TF/s fp32-eq  MFMA16 %s"
-                  % (name, n, cid, times[cid], tf, util), flush=True)
+            print("%-5s N=%d T=%d cid %4d  %8.3f ms  %6.1f TF/s fp32-eq  MFMA16 %s"
+                  % (name, n, T, cid, times[cid], tf, util), flush=True)
 
 
 if __name__ == "__main__":

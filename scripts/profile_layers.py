@@ -91,10 +91,12 @@ def main():
     ap.add_argument("--fuse", action="store_true",
                     help="time the conv2 (2+1)D pairs with the fused kernel (without "
                          "--autotune: always; with it: where the autotuner picked it)")
+    ap.add_argument("--clip-length", type=int, default=8,
+                    help="frames per clip: 8, 16 or 32")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     eng = R2P1DEngine(build_network(1, 5, depth=args.depth), dev, backend="hip",
-                      dtype=args.dtype)
+                      dtype=args.dtype, clip_length=args.clip_length)
     f32 = eng.f32
     n = args.clips
     if args.fuse and not args.autotune:
