@@ -6,7 +6,11 @@
 //
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all
 //       jpeg_entropy.cpp bench/jpeg_scan_check.cpp -lpthread -o check
-//   ./check stream.mjpeg
+//   ./check [--sampling N] stream.mjpeg
+//
+// N: 0 4:2:0, 1 4:2:2, 2 4:4:4, which must be the stream's (default: whatever
+// its first frame has); everything below runs through the entry points that
+// carry the sampling, and the scan record corruptions include its sampling word.
 //
 // For every frame of the stream: pack + interval decode must equal
 // rnb_jpeg_decode_frames. Then, on the first frame: every truncation length
@@ -20,9 +24,9 @@
 // write one byte outside is a sanitizer report. Exit status 0 and "no fault":
 // all of that held.
 //
-//   ./check --records W H record.bin ...
+//   ./check [--sampling N] --records W H record.bin ...
 // runs the interval decoder, twice, on each file as one scan record of a
-// W x H frame (the fixed damaged records that the GPU tests then give the
+// W x H frame of sampling N (default 0) (the fixed damaged records that the GPU tests then give the
 // kernel) and prints each status.
 #include <cstdint>
 #include <cstdio>
@@ -31,19 +35,19 @@
 #include <vector>
 
 extern "C" {
-long long rnb_mjpeg_index(const uint8_t* data, long long len, long long* offs, long long* lens,
-                          long long cap, int* info);
-int rnb_jpeg_decode_frames(const uint8_t* data, long long len, const long long* frame_offs,
-                           const long long* frame_lens, int nframes, uint8_t* out,
-                           long long record_bytes, int threads);
-long long rnb_jpeg_pack_scans(const uint8_t* data, long long len, const long long* frame_offs,
-                              const long long* frame_lens, int nframes, uint8_t* out,
-                              long long out_cap, long long* scan_offs, int want_w, int want_h,
-                              int* info);
-int rnb_jpeg_decode_scans_host(const uint8_t* scans, long long scans_len,
-                               const long long* scan_offs, int nframes, int mw, int mh,
-                               uint8_t* out, long long out_len, long long record_bytes,
-                               int* status);
+long long rnb_mjpeg_index_s(const uint8_t* data, long long len, long long* offs, long long* lens,
+                            long long cap, int* info);
+int rnb_jpeg_decode_frames_s(const uint8_t* data, long long len, const long long* frame_offs,
+                             const long long* frame_lens, int nframes, uint8_t* out,
+                             long long record_bytes, int threads, int sampling);
+long long rnb_jpeg_pack_scans_s(const uint8_t* data, long long len, const long long* frame_offs,
+                                const long long* frame_lens, int nframes, uint8_t* out,
+                                long long out_cap, long long* scan_offs, int want_w, int want_h,
+                                int* info, int sampling);
+int rnb_jpeg_decode_scans_host_s(const uint8_t* scans, long long scans_len,
+                                 const long long* scan_offs, int nframes, int mw, int mh,
+                                 uint8_t* out, long long out_len, long long record_bytes,
+                                 int* status, int sampling);
 }
 
 static uint32_t rng_state = 0x2468ACEu;
@@ -54,8 +58,17 @@ static uint32_t rng() {                       // xorshift32
   return rng_state;
 }
 
-static int g_mw, g_mh, g_w, g_h;
+static int g_mw, g_mh, g_w, g_h, g_sampling;
 static long long g_record_bytes;
+static int g_resized = 0;        // disagreements on a frame whose header announces another size
+
+// MCU grid and record size of a g_w x g_h frame of g_sampling
+static void set_geometry() {
+  const int hs = g_sampling == 2 ? 1 : 2, vs = g_sampling == 0 ? 2 : 1;
+  g_mw = (g_w + 8 * hs - 1) / (8 * hs);
+  g_mh = (g_h + 8 * vs - 1) / (8 * vs);
+  g_record_bytes = 384 + 128LL * (hs * vs + 2) * g_mw * g_mh;
+}
 
 // a heap block of exactly n bytes holding src (operator new aligns to 16)
 static uint8_t* exact(const uint8_t* src, size_t n) {
@@ -69,7 +82,8 @@ static int host_decode(const std::vector<uint8_t>& bytes, std::vector<uint8_t>& 
   uint8_t* data = exact(bytes.data(), bytes.size());
   const long long off = 0, len = (long long)bytes.size();
   uint8_t* out = new uint8_t[g_record_bytes];
-  const int rc = rnb_jpeg_decode_frames(data, len, &off, &len, 1, out, g_record_bytes, 1);
+  const int rc = rnb_jpeg_decode_frames_s(data, len, &off, &len, 1, out, g_record_bytes, 1,
+                                          g_sampling);
   rec.assign(out, out + g_record_bytes);
   delete[] out;
   delete[] data;
@@ -84,7 +98,8 @@ static long long pack(const std::vector<uint8_t>& bytes, std::vector<uint8_t>& s
   uint8_t* out = new uint8_t[cap];
   long long offs[2];
   int info[3];
-  const long long n = rnb_jpeg_pack_scans(data, len, &off, &len, 1, out, cap, offs, g_w, g_h, info);
+  const long long n = rnb_jpeg_pack_scans_s(data, len, &off, &len, 1, out, cap, offs, g_w, g_h,
+                                            info, g_sampling);
   if (n >= 0) {
     if (offs[0] != 0 || offs[1] != n || n % 16 != 0 || n > cap) {
       fprintf(stderr, "the packer's offsets do not fit what it wrote\n");
@@ -106,8 +121,8 @@ static int mirror(const std::vector<uint8_t>& scans, std::vector<uint8_t>& rec, 
   memset(out, 0xA5, (size_t)g_record_bytes);
   const long long offs[2] = {0, (long long)scans.size()};
   *status = 12345;
-  const int rc = rnb_jpeg_decode_scans_host(s, (long long)scans.size(), offs, 1, g_mw, g_mh, out,
-                                            g_record_bytes, g_record_bytes, status);
+  const int rc = rnb_jpeg_decode_scans_host_s(s, (long long)scans.size(), offs, 1, g_mw, g_mh, out,
+                                              g_record_bytes, g_record_bytes, status, g_sampling);
   rec.assign(out, out + g_record_bytes);
   delete[] out;
   delete[] s;
@@ -133,6 +148,19 @@ static int compare_paths(const std::vector<uint8_t>& bytes, int* ok, int* refuse
     accepted = status == 0;
   }
   if (accepted != (host_rc == 0)) {
+    // Damage to the size in the frame header: the frame decoder is given one
+    // frame and takes its size from that header (it decodes the MCUs the header
+    // announces), the packer is told the stream's size and refuses another. The
+    // two were not asked the same question then; both returned cleanly.
+    int info[5];
+    long long o = 0, l = 0;
+    uint8_t* data = exact(bytes.data(), bytes.size());
+    const long long c = rnb_mjpeg_index_s(data, (long long)bytes.size(), &o, &l, 1, info);
+    delete[] data;
+    if (c >= 1 && (info[0] != g_w || info[1] != g_h)) {
+      ++g_resized;
+      return 0;
+    }
     fprintf(stderr, "%s %lld: host decoder %d, packed path %s\n", what, which, host_rc,
             accepted ? "accepts" : "refuses");
     return 1;
@@ -160,8 +188,7 @@ static bool read_file(const char* path, std::vector<uint8_t>& file) {
 static int check_records(int argc, char** argv) {
   g_w = atoi(argv[2]); g_h = atoi(argv[3]);
   if (g_w < 1 || g_h < 1 || g_w > 65535 || g_h > 65535) return 2;
-  g_mw = (g_w + 15) / 16; g_mh = (g_h + 15) / 16;
-  g_record_bytes = 384 + 768LL * g_mw * g_mh;
+  set_geometry();
   for (int i = 4; i < argc; ++i) {
     std::vector<uint8_t> scans, r1, r2;
     if (!read_file(argv[i], scans)) return 2;
@@ -178,22 +205,36 @@ static int check_records(int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
+  int want_sampling = -1;
+  if (argc >= 3 && !strcmp(argv[1], "--sampling")) {
+    want_sampling = atoi(argv[2]);
+    if (want_sampling < 0 || want_sampling > 2) return 2;
+    argv[2] = argv[0];
+    argv += 2;
+    argc -= 2;
+  }
+  g_sampling = want_sampling < 0 ? 0 : want_sampling;
   if (argc >= 5 && !strcmp(argv[1], "--records")) return check_records(argc, argv);
   if (argc != 2) {
-    fprintf(stderr, "usage: %s stream.mjpeg | --records W H record...\n", argv[0]);
+    fprintf(stderr, "usage: %s [--sampling N] stream.mjpeg | --records W H record...\n", argv[0]);
     return 2;
   }
   std::vector<uint8_t> file;
   if (!read_file(argv[1], file)) return 2;
-  int info[4];
-  long long count = rnb_mjpeg_index(file.data(), (long long)file.size(), nullptr, nullptr, 0, info);
+  int info[5];
+  long long count = rnb_mjpeg_index_s(file.data(), (long long)file.size(), nullptr, nullptr, 0,
+                                      info);
   if (count < 1) { fprintf(stderr, "index of the intact stream failed: %lld\n", count); return 1; }
   std::vector<long long> offs((size_t)count), lens((size_t)count);
-  count = rnb_mjpeg_index(file.data(), (long long)file.size(), offs.data(), lens.data(), count,
-                          info);
+  count = rnb_mjpeg_index_s(file.data(), (long long)file.size(), offs.data(), lens.data(), count,
+                            info);
   g_w = info[0]; g_h = info[1];
-  g_mw = (g_w + 15) / 16; g_mh = (g_h + 15) / 16;
-  g_record_bytes = 384 + 768LL * g_mw * g_mh;
+  if (want_sampling >= 0 && want_sampling != info[4]) {
+    fprintf(stderr, "the stream's sampling is %d, not %d\n", info[4], want_sampling);
+    return 2;
+  }
+  g_sampling = info[4];
+  set_geometry();
   int ok = 0, refused = 0;
   // 1. every intact frame
   for (long long i = 0; i < count; ++i) {
@@ -243,10 +284,12 @@ int main(int argc, char** argv) {
     int status = 0;
     const long long o[2] = {0, (long long)scans.size()};
     const long long past[2] = {0, (long long)scans.size() + 16};
-    if (rnb_jpeg_decode_scans_host(scans.data(), (long long)scans.size(), past, 1, g_mw, g_mh,
-                                   rec.data(), g_record_bytes, g_record_bytes, &status) >= 0 ||
-        rnb_jpeg_decode_scans_host(scans.data(), (long long)scans.size(), o, 1, g_mw, g_mh,
-                                   rec.data(), g_record_bytes - 16, g_record_bytes, &status) >= 0) {
+    if (rnb_jpeg_decode_scans_host_s(scans.data(), (long long)scans.size(), past, 1, g_mw, g_mh,
+                                     rec.data(), g_record_bytes, g_record_bytes, &status,
+                                     g_sampling) >= 0 ||
+        rnb_jpeg_decode_scans_host_s(scans.data(), (long long)scans.size(), o, 1, g_mw, g_mh,
+                                     rec.data(), g_record_bytes - 16, g_record_bytes, &status,
+                                     g_sampling) >= 0) {
       fprintf(stderr, "a scan record / frame record outside its buffer was accepted\n");
       return 1;
     }
@@ -254,14 +297,15 @@ int main(int argc, char** argv) {
     const long long off = 0, len = (long long)frame.size();
     long long so[2];
     int pinfo[3];
-    if (rnb_jpeg_pack_scans(frame.data(), len, &off, &len, 1, out, (long long)scans.size() - 16,
-                            so, 0, 0, pinfo) >= 0) {
+    if (rnb_jpeg_pack_scans_s(frame.data(), len, &off, &len, 1, out, (long long)scans.size() - 16,
+                              so, 0, 0, pinfo, g_sampling) >= 0) {
       fprintf(stderr, "a short out_cap was accepted\n");
       return 1;
     }
     delete[] out;
   }
-  printf("jpeg_scan_check: %d streams accepted by both paths, %d refused by both; "
-         "%d damaged scan records decoded, %d refused; no fault\n", ok, refused, rec_ok, rec_bad);
+  printf("jpeg_scan_check: sampling %d: %d streams accepted by both paths, %d refused by both, "
+         "%d apart on a damaged size; %d damaged scan records decoded, %d refused; no fault\n",
+         g_sampling, ok, refused, g_resized, rec_ok, rec_bad);
   return 0;
 }

@@ -6,7 +6,12 @@
 //
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all
 //       jpeg_entropy.cpp bench/jpeg_subseq_check.cpp -lpthread -o check
-//   ./check stream.mjpeg ...
+//   ./check [--sampling N] stream.mjpeg ...
+//
+// N: 0 4:2:0, 1 4:2:2, 2 4:4:4, which must be every stream's (default: whatever
+// each stream's first frame has); both decoders are called through the entry
+// points that carry the sampling, and the record corruptions include the
+// sampling word.
 //
 // For S in {16, 64, 256} and every frame of every stream: the frame is packed,
 // and the clean scan record and a list of damaged copies go through both
@@ -19,10 +24,10 @@
 // one byte outside is a sanitizer report. Exit status 0 and "no fault": all of
 // that held.
 //
-//   ./check --records W H record.bin ...
+//   ./check [--sampling N] --records W H record.bin ...
 // runs both decoders at S = 16, 64, 128 and 256 on each file as one scan record
-// of a W x H frame (the fixed damaged records that the GPU tests then give the
-// kernel) and prints each status.
+// of a W x H frame of sampling N (default 0) (the fixed damaged records that the
+// GPU tests then give the kernel) and prints each status.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -30,20 +35,20 @@
 #include <vector>
 
 extern "C" {
-long long rnb_mjpeg_index(const uint8_t* data, long long len, long long* offs, long long* lens,
-                          long long cap, int* info);
-long long rnb_jpeg_pack_scans(const uint8_t* data, long long len, const long long* frame_offs,
-                              const long long* frame_lens, int nframes, uint8_t* out,
-                              long long out_cap, long long* scan_offs, int want_w, int want_h,
-                              int* info);
-int rnb_jpeg_decode_scans_host(const uint8_t* scans, long long scans_len,
-                               const long long* scan_offs, int nframes, int mw, int mh,
-                               uint8_t* out, long long out_len, long long record_bytes,
-                               int* status);
-int rnb_jpeg_decode_scans_subseq_host(const uint8_t* scans, long long scans_len,
-                                      const long long* scan_offs, int nframes, int mw, int mh,
-                                      uint8_t* out, long long out_len, long long record_bytes,
-                                      int* status, int subseq_bytes, int* rounds);
+long long rnb_mjpeg_index_s(const uint8_t* data, long long len, long long* offs, long long* lens,
+                            long long cap, int* info);
+long long rnb_jpeg_pack_scans_s(const uint8_t* data, long long len, const long long* frame_offs,
+                                const long long* frame_lens, int nframes, uint8_t* out,
+                                long long out_cap, long long* scan_offs, int want_w, int want_h,
+                                int* info, int sampling);
+int rnb_jpeg_decode_scans_host_s(const uint8_t* scans, long long scans_len,
+                                 const long long* scan_offs, int nframes, int mw, int mh,
+                                 uint8_t* out, long long out_len, long long record_bytes,
+                                 int* status, int sampling);
+int rnb_jpeg_decode_scans_subseq_host_s(const uint8_t* scans, long long scans_len,
+                                        const long long* scan_offs, int nframes, int mw, int mh,
+                                        uint8_t* out, long long out_len, long long record_bytes,
+                                        int* status, int subseq_bytes, int* rounds, int sampling);
 }
 
 static uint32_t rng_state = 0x13579BDu;
@@ -54,8 +59,16 @@ static uint32_t rng() {                       // xorshift32
   return rng_state;
 }
 
-static int g_mw, g_mh;
+static int g_mw, g_mh, g_sampling;
 static long long g_record_bytes;
+
+// MCU grid and record size of a w x h frame of g_sampling
+static void set_geometry(int w, int h) {
+  const int hs = g_sampling == 2 ? 1 : 2, vs = g_sampling == 0 ? 2 : 1;
+  g_mw = (w + 8 * hs - 1) / (8 * hs);
+  g_mh = (h + 8 * vs - 1) / (8 * vs);
+  g_record_bytes = 384 + 128LL * (hs * vs + 2) * g_mw * g_mh;
+}
 static long long g_cases = 0, g_failed = 0, g_rounds = 0;
 
 // one scan record (an exact-size heap block) through a decoder; S = 0: the serial one
@@ -69,10 +82,11 @@ static int decode(const std::vector<uint8_t>& scans, int S, std::vector<uint8_t>
   *status = 12345;
   *rounds = 0;
   const int rc =
-      S ? rnb_jpeg_decode_scans_subseq_host(s, (long long)scans.size(), offs, 1, g_mw, g_mh, out,
-                                            g_record_bytes, g_record_bytes, status, S, rounds)
-        : rnb_jpeg_decode_scans_host(s, (long long)scans.size(), offs, 1, g_mw, g_mh, out,
-                                     g_record_bytes, g_record_bytes, status);
+      S ? rnb_jpeg_decode_scans_subseq_host_s(s, (long long)scans.size(), offs, 1, g_mw, g_mh, out,
+                                              g_record_bytes, g_record_bytes, status, S, rounds,
+                                              g_sampling)
+        : rnb_jpeg_decode_scans_host_s(s, (long long)scans.size(), offs, 1, g_mw, g_mh, out,
+                                       g_record_bytes, g_record_bytes, status, g_sampling);
   rec.assign(out, out + g_record_bytes);
   delete[] out;
   delete[] s;
@@ -183,8 +197,7 @@ static int damage(const std::vector<uint8_t>& scans, int S) {
 static int check_records(int argc, char** argv) {
   const int w = atoi(argv[2]), h = atoi(argv[3]);
   if (w < 1 || h < 1 || w > 65535 || h > 65535) return 2;
-  g_mw = (w + 15) / 16; g_mh = (h + 15) / 16;
-  g_record_bytes = 384 + 768LL * g_mw * g_mh;
+  set_geometry(w, h);
   const int sizes[4] = {16, 64, 128, 256};
   for (int i = 4; i < argc; ++i) {
     std::vector<uint8_t> scans;
@@ -199,9 +212,19 @@ static int check_records(int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
+  int want_sampling = -1;
+  if (argc >= 3 && !strcmp(argv[1], "--sampling")) {
+    want_sampling = atoi(argv[2]);
+    if (want_sampling < 0 || want_sampling > 2) return 2;
+    argv[2] = argv[0];
+    argv += 2;
+    argc -= 2;
+  }
+  g_sampling = want_sampling < 0 ? 0 : want_sampling;
   if (argc >= 5 && !strcmp(argv[1], "--records")) return check_records(argc, argv);
   if (argc < 2) {
-    fprintf(stderr, "usage: %s stream.mjpeg ... | --records W H record...\n", argv[0]);
+    fprintf(stderr, "usage: %s [--sampling N] stream.mjpeg ... | --records W H record...\n",
+            argv[0]);
     return 2;
   }
   const int sizes[3] = {16, 64, 256};
@@ -209,21 +232,27 @@ int main(int argc, char** argv) {
   for (int a = 1; a < argc; ++a) {
     std::vector<uint8_t> file;
     if (!read_file(argv[a], file)) return 2;
-    int info[4];
-    long long count = rnb_mjpeg_index(file.data(), (long long)file.size(), nullptr, nullptr, 0, info);
+    int info[5];
+    long long count = rnb_mjpeg_index_s(file.data(), (long long)file.size(), nullptr, nullptr, 0,
+                                        info);
     if (count < 1) { fprintf(stderr, "%s: index failed: %lld\n", argv[a], count); return 1; }
     std::vector<long long> offs((size_t)count), lens((size_t)count);
-    count = rnb_mjpeg_index(file.data(), (long long)file.size(), offs.data(), lens.data(), count,
-                            info);
-    g_mw = (info[0] + 15) / 16; g_mh = (info[1] + 15) / 16;
-    g_record_bytes = 384 + 768LL * g_mw * g_mh;
+    count = rnb_mjpeg_index_s(file.data(), (long long)file.size(), offs.data(), lens.data(), count,
+                              info);
+    if (want_sampling >= 0 && want_sampling != info[4]) {
+      fprintf(stderr, "%s: the stream's sampling is %d, not %d\n", argv[a], info[4], want_sampling);
+      return 2;
+    }
+    g_sampling = info[4];
+    set_geometry(info[0], info[1]);
     for (long long i = 0; i < count; ++i, ++frames) {
       const long long cap = (2048 + 8LL * g_mw * g_mh + lens[(size_t)i] + 31) & ~15LL;
       uint8_t* out = new uint8_t[cap];
       long long so[2];
       int pinfo[3];
-      const long long n = rnb_jpeg_pack_scans(file.data(), (long long)file.size(), &offs[(size_t)i],
-                                              &lens[(size_t)i], 1, out, cap, so, 0, 0, pinfo);
+      const long long n = rnb_jpeg_pack_scans_s(file.data(), (long long)file.size(),
+                                                &offs[(size_t)i], &lens[(size_t)i], 1, out, cap, so,
+                                                0, 0, pinfo, g_sampling);
       if (n < 0) { fprintf(stderr, "%s: frame %lld is not packed: %lld\n", argv[a], i, n); return 1; }
       const std::vector<uint8_t> scans(out, out + n);
       delete[] out;
@@ -238,15 +267,15 @@ int main(int argc, char** argv) {
     int status = 0, rounds = 0;
     const int bad[5] = {0, 8, 24, 4112, -16};
     for (int k = 0; k < 5; ++k)
-      if (rnb_jpeg_decode_scans_subseq_host(scans.data(), 4096, o, 1, g_mw, g_mh, rec.data(),
-                                            g_record_bytes, g_record_bytes, &status, bad[k],
-                                            &rounds) >= 0) {
+      if (rnb_jpeg_decode_scans_subseq_host_s(scans.data(), 4096, o, 1, g_mw, g_mh, rec.data(),
+                                              g_record_bytes, g_record_bytes, &status, bad[k],
+                                              &rounds, g_sampling) >= 0) {
         fprintf(stderr, "subseq_bytes %d was accepted\n", bad[k]);
         return 1;
       }
-    if (rnb_jpeg_decode_scans_subseq_host(scans.data(), 4096, o, 1, g_mw, g_mh, rec.data(),
-                                          g_record_bytes, g_record_bytes, &status, 64,
-                                          nullptr) >= 0)
+    if (rnb_jpeg_decode_scans_subseq_host_s(scans.data(), 4096, o, 1, g_mw, g_mh, rec.data(),
+                                            g_record_bytes, g_record_bytes, &status, 64, nullptr,
+                                            g_sampling) >= 0)
       return 1;
   }
   printf("jpeg_subseq_check: %lld frames, %lld records through both decoders (%lld refused by "

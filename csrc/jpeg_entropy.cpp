@@ -10,17 +10,24 @@
 // kernel on the host (rnb_jpeg_decode_scans_host).
 //
 // Read: baseline sequential Huffman (SOF0), 8-bit samples, three components
-// sampled 2x2 / 1x1 / 1x1 (4:2:0) in one interleaved scan, up to 4 + 4 Huffman
+// sampled 2x2 / 1x1 / 1x1 (4:2:0), 2x1 / 1x1 / 1x1 (4:2:2) or 1x1 / 1x1 / 1x1
+// (4:4:4) in one interleaved scan, all frames of a stream alike, up to 4 + 4 Huffman
 // tables and 4 8-bit quantisation tables redefined per frame, restart
 // intervals, any size >= 1x1. Everything else is refused with its own code
 // (rnb_jpeg_error_name).
 //
-// Frame record (the upload format), record_bytes >= 384 + 768 * mw * mh with
-// mw = ceil(W / 16), mh = ceil(H / 16):
+// Frame record (the upload format), record_bytes >= 384 + 128 * B * mw * mh
+// with luma factors Hs x Vs (jpeg_huff.h: Geo), B = Hs Vs + 2,
+// mw = ceil(W / (8 Hs)), mh = ceil(H / (8 Vs)); 4:2:0: 384 + 768 * mw * mh:
 //   uint16 qt[3][64]   the quantisation table of Y, Cb, Cr, natural order
 //   int16  blocks[][64] QUANTISED coefficients in natural order: the Y blocks
-//                      row-major over the padded 2*mh x 2*mw grid, then the
+//                      row-major over the padded Vs*mh x Hs*mw grid, then the
 //                      mh x mw Cb blocks, then the Cr blocks
+//
+// The entry points without a sampling argument are the 4:2:0 forms: they refuse
+// a 4:2:2 or 4:4:4 frame with E_SAMPLING. The *_s forms take or report the
+// sampling (0 4:2:0, 1 4:2:2, 2 4:4:4); there a frame whose sampling is not the
+// stream's gets E_SAMPLING_CHANGE.
 //
 // The input is untrusted: every read is checked against the frame's length
 // and every write lands inside the record by construction (block indices come
@@ -41,6 +48,7 @@ namespace {
 
 struct Frame {
   int w = 0, h = 0;
+  int sampling = SAMPLING_420;
   int tq[3], td[3], ta[3];
   int restart = 0;
   bool qset[4] = {false, false, false, false};
@@ -104,7 +112,12 @@ int parse_frame(const uint8_t* p, long long n, Frame& f, int tables) {
       for (int c = 0; c < 3; ++c) {
         comp_id[c] = s[6 + 3 * c];
         const int hv = s[7 + 3 * c];
-        if (hv != (c == 0 ? 0x22 : 0x11)) return E_SAMPLING;
+        if (c == 0) {
+          if (hv != 0x22 && hv != 0x21 && hv != 0x11) return E_SAMPLING;
+          f.sampling = hv == 0x22 ? SAMPLING_420 : hv == 0x21 ? SAMPLING_422 : SAMPLING_444;
+        } else if (hv != 0x11) {
+          return E_SAMPLING;
+        }
         f.tq[c] = s[8 + 3 * c];
         if (f.tq[c] > 3) return E_MARKER;
       }
@@ -189,17 +202,32 @@ int parse_frame(const uint8_t* p, long long n, Frame& f, int tables) {
   }
 }
 
-// one frame -> one record; rec has room for 384 + 768 * mw * mh bytes
+// MCU grid of a w x h frame
+inline void mcu_grid(int w, int h, const Geo& g, long long& mw, long long& mh) {
+  mw = (w + 8 * g.hs - 1) / (8 * g.hs);
+  mh = (h + 8 * g.vs - 1) / (8 * g.vs);
+}
+
+// what a frame of another (readable) sampling than `want` gets: the 4:2:0 entry
+// points (legacy) keep refusing it as before
+inline int sampling_mismatch(bool legacy) { return legacy ? E_SAMPLING : E_SAMPLING_CHANGE; }
+
+// one frame -> one record; rec has room for 384 + 128 * B * mw * mh bytes.
+// sampling: the one the frame must have.
 int decode_frame(const uint8_t* p, long long n, int want_w, int want_h, uint8_t* rec,
-                 long long record_bytes, int* dims) {
+                 long long record_bytes, int* dims, int sampling, bool legacy) {
   std::vector<Frame> holder(1);            // ~14 KB of tables: off the thread's stack
   Frame& f = holder[0];
   int rc = parse_frame(p, n, f, TABLES_BUILD);
   if (rc) return rc;
   if (dims) { dims[0] = f.w; dims[1] = f.h; }
+  if (f.sampling != sampling) return sampling_mismatch(legacy);
   if (want_w > 0 && (f.w != want_w || f.h != want_h)) return E_SIZE_CHANGE;
-  const long long mw = (f.w + 15) / 16, mh = (f.h + 15) / 16;
-  if (384 + 768 * mw * mh > record_bytes) return E_RECORD;
+  Geo g = geo_420();
+  if (!geo_of(sampling, g)) return E_ARG;
+  long long mw, mh;
+  mcu_grid(f.w, f.h, g, mw, mh);
+  if (384 + 128 * g.nb * mw * mh > record_bytes) return E_RECORD;
   uint16_t* qt = (uint16_t*)rec;
   for (int c = 0; c < 3; ++c) memcpy(qt + 64 * c, f.qt[f.tq[c]], 128);
   int16_t* coef = (int16_t*)(rec + 384);      // every block is visited and zeroed first
@@ -215,7 +243,7 @@ int decode_frame(const uint8_t* p, long long n, int want_w, int want_h, uint8_t*
   for (long long m0 = 0; m0 < nmcu; m0 += per) {
     Bits b;
     rc = decode_interval(b, p, pos, n, t, m0, nmcu - m0 < per ? nmcu - m0 : per, mw, nmcu, coef,
-                         false);
+                         false, g);
     if (rc) return rc;
     if (m0 + per >= nmcu) break;
     // the marker follows the byte the interval ended in
@@ -226,6 +254,37 @@ int decode_frame(const uint8_t* p, long long n, int want_w, int want_h, uint8_t*
     next_rst = (next_rst + 1) & 7;
   }
   return E_OK;
+}
+
+long long mjpeg_index(const uint8_t* data, long long len, long long* offs, long long* lens,
+                      long long cap, int* info, bool legacy) {
+  if (!data || len < 0 || cap < 0 || (cap > 0 && (!offs || !lens)) || !info) return E_ARG;
+  info[0] = info[1] = info[2] = info[3] = 0;
+  if (!legacy) info[4] = 0;
+  int sampling = SAMPLING_420;
+  std::vector<Frame> holder(1);
+  long long pos = 0, count = 0;
+  while (pos < len) {
+    holder[0] = Frame();
+    Frame& f = holder[0];
+    info[2] = (int)count;
+    const int rc = parse_frame(data + pos, len - pos, f, TABLES_NONE);
+    if (rc) return rc;
+    if (legacy && f.sampling != SAMPLING_420) return E_SAMPLING;
+    if (count == 0) {
+      info[0] = f.w; info[1] = f.h; info[3] = f.restart;
+      sampling = f.sampling;
+      if (!legacy) info[4] = sampling;
+    } else if (f.sampling != sampling) {
+      return E_SAMPLING_CHANGE;
+    } else if (f.w != info[0] || f.h != info[1]) {
+      return E_SIZE_CHANGE;
+    }
+    if (count < cap) { offs[count] = pos; lens[count] = f.frame_end; }
+    ++count;
+    pos += f.frame_end;
+  }
+  return count;
 }
 
 }  // namespace
@@ -256,6 +315,7 @@ const char* rnb_jpeg_error_name(int code) {
     case E_DC_RANGE: return "dc_range";
     case E_SIZE: return "dimensions";
     case E_SCANREC: return "scan record";
+    case E_SAMPLING_CHANGE: return "sampling change";
     default: return "unknown";
   }
 }
@@ -267,35 +327,26 @@ const char* rnb_jpeg_error_name(int code) {
 // its size compared with the first frame's.
 long long rnb_mjpeg_index(const uint8_t* data, long long len, long long* offs, long long* lens,
                           long long cap, int* info) {
-  if (!data || len < 0 || cap < 0 || (cap > 0 && (!offs || !lens)) || !info) return E_ARG;
-  info[0] = info[1] = info[2] = info[3] = 0;
-  std::vector<Frame> holder(1);
-  long long pos = 0, count = 0;
-  while (pos < len) {
-    holder[0] = Frame();
-    Frame& f = holder[0];
-    info[2] = (int)count;
-    const int rc = parse_frame(data + pos, len - pos, f, TABLES_NONE);
-    if (rc) return rc;
-    if (count == 0) {
-      info[0] = f.w; info[1] = f.h; info[3] = f.restart;
-    } else if (f.w != info[0] || f.h != info[1]) {
-      return E_SIZE_CHANGE;
-    }
-    if (count < cap) { offs[count] = pos; lens[count] = f.frame_end; }
-    ++count;
-    pos += f.frame_end;
-  }
-  return count;
+  return mjpeg_index(data, len, offs, lens, cap, info, true);
+}
+
+// The same for 4:2:0, 4:2:2 and 4:4:4 streams: info has a fifth word, the
+// sampling of the first frame (0 / 1 / 2), which every frame must share
+// (E_SAMPLING_CHANGE otherwise).
+long long rnb_mjpeg_index_s(const uint8_t* data, long long len, long long* offs, long long* lens,
+                            long long cap, int* info) {
+  return mjpeg_index(data, len, offs, lens, cap, info, false);
 }
 
 // Entropy-decode nframes frames (data + frame_offs[i], frame_lens[i] bytes)
 // into records of record_bytes each at out + i * record_bytes, on up to
 // `threads` (<= 16) threads. All frames must have the first one's size.
 // Returns 0, or the code of the lowest-numbered frame that failed.
-int rnb_jpeg_decode_frames(const uint8_t* data, long long len, const long long* frame_offs,
-                           const long long* frame_lens, int nframes, uint8_t* out,
-                           long long record_bytes, int threads) {
+static int decode_frames(const uint8_t* data, long long len, const long long* frame_offs,
+                         const long long* frame_lens, int nframes, uint8_t* out,
+                         long long record_bytes, int threads, int sampling, bool legacy) {
+  Geo geo;
+  if (!geo_of(sampling, geo)) return E_ARG;
   if (nframes == 0) return E_OK;
   if (!data || !frame_offs || !frame_lens || !out || len < 0 || nframes < 0 || threads < 1 ||
       record_bytes < 384)
@@ -306,7 +357,8 @@ int rnb_jpeg_decode_frames(const uint8_t* data, long long len, const long long* 
       return E_ARG;
   int dims[2] = {0, 0};
   std::vector<int> codes((size_t)nframes, 0);
-  codes[0] = decode_frame(data + frame_offs[0], frame_lens[0], 0, 0, out, record_bytes, dims);
+  codes[0] = decode_frame(data + frame_offs[0], frame_lens[0], 0, 0, out, record_bytes, dims,
+                          sampling, legacy);
   if (codes[0]) return codes[0];
   if (threads > 16) threads = 16;
   if (threads > nframes - 1) threads = nframes - 1;
@@ -316,7 +368,8 @@ int rnb_jpeg_decode_frames(const uint8_t* data, long long len, const long long* 
       const int i = next.fetch_add(1);
       if (i >= nframes) return;
       codes[(size_t)i] = decode_frame(data + frame_offs[i], frame_lens[i], dims[0], dims[1],
-                                      out + (long long)i * record_bytes, record_bytes, nullptr);
+                                      out + (long long)i * record_bytes, record_bytes, nullptr,
+                                      sampling, legacy);
     }
   };
   if (threads <= 1) {
@@ -331,6 +384,23 @@ int rnb_jpeg_decode_frames(const uint8_t* data, long long len, const long long* 
   return E_OK;
 }
 
+int rnb_jpeg_decode_frames(const uint8_t* data, long long len, const long long* frame_offs,
+                           const long long* frame_lens, int nframes, uint8_t* out,
+                           long long record_bytes, int threads) {
+  return decode_frames(data, len, frame_offs, frame_lens, nframes, out, record_bytes, threads,
+                       SAMPLING_420, true);
+}
+
+// The same for frames of `sampling` (0 4:2:0, 1 4:2:2, 2 4:4:4; E_ARG otherwise),
+// which is the stream's, from rnb_mjpeg_index_s: records of 384 + 128 B mw mh
+// bytes. A frame of another sampling: E_SAMPLING_CHANGE.
+int rnb_jpeg_decode_frames_s(const uint8_t* data, long long len, const long long* frame_offs,
+                             const long long* frame_lens, int nframes, uint8_t* out,
+                             long long record_bytes, int threads, int sampling) {
+  return decode_frames(data, len, frame_offs, frame_lens, nframes, out, record_bytes, threads,
+                       sampling, false);
+}
+
 // Pack the scans of nframes frames into scan records (layout: jpeg_huff.h) for
 // the interval decoders, back to back in out[0 .. out_cap). Per frame:
 // parse_frame with its refusals, then one walk over the scan for RSTn markers,
@@ -341,10 +411,12 @@ int rnb_jpeg_decode_frames(const uint8_t* data, long long len, const long long* 
 // frame's). info[0..2] = width, height, index of the frame a refusal is in.
 // Returns the number of bytes written, or a negative code (E_RECORD: out_cap
 // is too small).
-long long rnb_jpeg_pack_scans(const uint8_t* data, long long len, const long long* frame_offs,
-                              const long long* frame_lens, int nframes, uint8_t* out,
-                              long long out_cap, long long* scan_offs, int want_w, int want_h,
-                              int* info) {
+static long long pack_scans(const uint8_t* data, long long len, const long long* frame_offs,
+                            const long long* frame_lens, int nframes, uint8_t* out,
+                            long long out_cap, long long* scan_offs, int want_w, int want_h,
+                            int* info, int sampling, bool legacy) {
+  Geo geo;
+  if (!geo_of(sampling, geo)) return E_ARG;
   if (!data || !frame_offs || !frame_lens || !out || !scan_offs || !info || len < 0 ||
       nframes < 0 || out_cap < 0 || want_w < 0 || want_h < 0 || ((uintptr_t)out & 15u) != 0)
     return E_ARG;
@@ -363,9 +435,12 @@ long long rnb_jpeg_pack_scans(const uint8_t* data, long long len, const long lon
     const uint8_t* p = data + frame_offs[i];
     const int rc = parse_frame(p, frame_lens[i], f, TABLES_RAW);
     if (rc) return rc;
+    if (f.sampling != sampling) return sampling_mismatch(legacy);
     if (info[0] == 0) { info[0] = f.w; info[1] = f.h; }
     if (f.w != info[0] || f.h != info[1]) return E_SIZE_CHANGE;
-    const long long nmcu = (long long)((f.w + 15) / 16) * ((f.h + 15) / 16);
+    long long mw, mh;
+    mcu_grid(f.w, f.h, geo, mw, mh);
+    const long long nmcu = mw * mh;
     const long long per = f.restart && f.restart < nmcu ? f.restart : nmcu;
     const long long n_int = (nmcu + per - 1) / per;
     const long long scan_len = f.scan_end - f.scan_begin;
@@ -378,7 +453,8 @@ long long rnb_jpeg_pack_scans(const uint8_t* data, long long len, const long lon
       memcpy(rec + SR_HUFF + SR_TABLE * (2 * c), f.raw[0][f.td[c]], SR_TABLE);
       memcpy(rec + SR_HUFF + SR_TABLE * (2 * c + 1), f.raw[1][f.ta[c]], SR_TABLE);
     }
-    const uint32_t head[4] = {(uint32_t)n_int, (uint32_t)per, (uint32_t)scan_len, 0u};
+    const uint32_t head[4] = {(uint32_t)n_int, (uint32_t)per, (uint32_t)scan_len,
+                              (uint32_t)sampling};
     memcpy(rec + SR_HEADER, head, 16);
     uint8_t* spans = rec + SR_SPANS;
     const uint8_t* scan = p + f.scan_begin;
@@ -415,6 +491,25 @@ long long rnb_jpeg_pack_scans(const uint8_t* data, long long len, const long lon
   return at;
 }
 
+long long rnb_jpeg_pack_scans(const uint8_t* data, long long len, const long long* frame_offs,
+                              const long long* frame_lens, int nframes, uint8_t* out,
+                              long long out_cap, long long* scan_offs, int want_w, int want_h,
+                              int* info) {
+  return pack_scans(data, len, frame_offs, frame_lens, nframes, out, out_cap, scan_offs, want_w,
+                    want_h, info, SAMPLING_420, true);
+}
+
+// The same for frames of `sampling` (0 / 1 / 2, the stream's; E_ARG otherwise):
+// the record's fourth header word carries it. A frame of another sampling:
+// E_SAMPLING_CHANGE.
+long long rnb_jpeg_pack_scans_s(const uint8_t* data, long long len, const long long* frame_offs,
+                                const long long* frame_lens, int nframes, uint8_t* out,
+                                long long out_cap, long long* scan_offs, int want_w, int want_h,
+                                int* info, int sampling) {
+  return pack_scans(data, len, frame_offs, frame_lens, nframes, out, out_cap, scan_offs, want_w,
+                    want_h, info, sampling, false);
+}
+
 // The GPU interval decoder's host mirror: nframes scan records (record i at
 // scans[scan_offs[i] .. scan_offs[i + 1])) into frame records record_bytes
 // apart in out, with what jpeg_huff_kernel does in the same order: the tables
@@ -424,16 +519,20 @@ long long rnb_jpeg_pack_scans(const uint8_t* data, long long len, const long lon
 // table that is refused as a whole: all blocks zero then). Every block of
 // every record is written. Returns 0, or E_ARG when a buffer, an offset or an
 // alignment is refused (nothing is written then).
-int rnb_jpeg_decode_scans_host(const uint8_t* scans, long long scans_len,
-                               const long long* scan_offs, int nframes, int mw, int mh,
-                               uint8_t* out, long long out_len, long long record_bytes,
-                               int* status) {
+static int decode_scans_host(const uint8_t* scans, long long scans_len,
+                             const long long* scan_offs, int nframes, int mw, int mh,
+                             uint8_t* out, long long out_len, long long record_bytes,
+                             int* status, int sampling) {
+  Geo geo;
+  if (!geo_of(sampling, geo)) return E_ARG;
+  const long long coef_bytes = 128LL * geo.nb;          // per MCU
   if (nframes == 0) return E_OK;
   if (!scans || !scan_offs || !out || !status || nframes < 0 || mw < 1 || mh < 1 || mw > 4096 ||
       mh > 4096 || scans_len < 0 || out_len < 0)
     return E_ARG;
   const long long nmcu = (long long)mw * mh;
-  if (((uintptr_t)out & 15u) != 0 || record_bytes % 16 != 0 || record_bytes < 384 + 768 * nmcu ||
+  if (((uintptr_t)out & 15u) != 0 || record_bytes % 16 != 0 ||
+      record_bytes < 384 + coef_bytes * nmcu ||
       record_bytes > out_len / nframes)
     return E_ARG;
   if (scan_offs[0] < 0 || scan_offs[nframes] > scans_len) return E_ARG;
@@ -445,7 +544,7 @@ int rnb_jpeg_decode_scans_host(const uint8_t* scans, long long scans_len,
     uint8_t* dst = out + (long long)i * record_bytes;
     int16_t* coef = (int16_t*)(dst + 384);
     ScanHeader h;
-    int rc = scan_record_check(rec, scan_offs[i + 1] - scan_offs[i], nmcu, h);
+    int rc = scan_record_check(rec, scan_offs[i + 1] - scan_offs[i], nmcu, h, sampling);
     memcpy(dst, rec, 384);
     Tables t;
     for (int k = 0; k < 6 && !rc; ++k) {
@@ -460,17 +559,36 @@ int rnb_jpeg_decode_scans_host(const uint8_t* scans, long long scans_len,
       t.ac[c] = &tabs[(size_t)(2 * c + 1)];
     }
     if (rc) {
-      memset(coef, 0, (size_t)(768 * nmcu));
+      memset(coef, 0, (size_t)(coef_bytes * nmcu));
       status[i] = rc;
       continue;
     }
     status[i] = E_OK;
     for (long long v = 0; v < (long long)h.n_intervals; ++v) {
-      rc = decode_record_interval(rec, h, v, t, mw, nmcu, coef);
+      rc = decode_record_interval(rec, h, v, t, mw, nmcu, coef, geo);
       if (rc && !status[i]) status[i] = rc;
     }
   }
   return E_OK;
+}
+
+int rnb_jpeg_decode_scans_host(const uint8_t* scans, long long scans_len,
+                               const long long* scan_offs, int nframes, int mw, int mh,
+                               uint8_t* out, long long out_len, long long record_bytes,
+                               int* status) {
+  return decode_scans_host(scans, scans_len, scan_offs, nframes, mw, mh, out, out_len,
+                           record_bytes, status, SAMPLING_420);
+}
+
+// The same with the geometry of `sampling` (0 / 1 / 2; E_ARG otherwise): (mw,
+// mh) count its MCUs, records are >= 384 + 128 B mw mh bytes, and a scan record
+// whose sampling word is another gets E_SCANREC.
+int rnb_jpeg_decode_scans_host_s(const uint8_t* scans, long long scans_len,
+                                 const long long* scan_offs, int nframes, int mw, int mh,
+                                 uint8_t* out, long long out_len, long long record_bytes,
+                                 int* status, int sampling) {
+  return decode_scans_host(scans, scans_len, scan_offs, nframes, mw, mh, out, out_len,
+                           record_bytes, status, sampling);
 }
 
 // The host emulation of jpeg_huff_subseq_kernel: as rnb_jpeg_decode_scans_host,
@@ -480,17 +598,21 @@ int rnb_jpeg_decode_scans_host(const uint8_t* scans, long long scans_len,
 // by pass, as loops over the subsequences. Records and status equal
 // rnb_jpeg_decode_scans_host's byte for byte; rounds[i] receives the number of
 // synchronisation rounds frame i took (0 for every other frame).
-int rnb_jpeg_decode_scans_subseq_host(const uint8_t* scans, long long scans_len,
-                                      const long long* scan_offs, int nframes, int mw, int mh,
-                                      uint8_t* out, long long out_len, long long record_bytes,
-                                      int* status, int subseq_bytes, int* rounds) {
+static int decode_scans_subseq_host(const uint8_t* scans, long long scans_len,
+                                    const long long* scan_offs, int nframes, int mw, int mh,
+                                    uint8_t* out, long long out_len, long long record_bytes,
+                                    int* status, int subseq_bytes, int* rounds, int sampling) {
+  Geo geo;
+  if (!geo_of(sampling, geo)) return E_ARG;
+  const long long coef_bytes = 128LL * geo.nb;          // per MCU
   if (!rounds || !subseq_bytes_ok(subseq_bytes)) return E_ARG;
   if (nframes == 0) return E_OK;
   if (!scans || !scan_offs || !out || !status || nframes < 0 || mw < 1 || mh < 1 || mw > 4096 ||
       mh > 4096 || scans_len < 0 || out_len < 0)
     return E_ARG;
   const long long nmcu = (long long)mw * mh;
-  if (((uintptr_t)out & 15u) != 0 || record_bytes % 16 != 0 || record_bytes < 384 + 768 * nmcu ||
+  if (((uintptr_t)out & 15u) != 0 || record_bytes % 16 != 0 ||
+      record_bytes < 384 + coef_bytes * nmcu ||
       record_bytes > out_len / nframes)
     return E_ARG;
   if (scan_offs[0] < 0 || scan_offs[nframes] > scans_len) return E_ARG;
@@ -506,7 +628,7 @@ int rnb_jpeg_decode_scans_subseq_host(const uint8_t* scans, long long scans_len,
     uint8_t* dst = out + (long long)i * record_bytes;
     int16_t* coef = (int16_t*)(dst + 384);
     ScanHeader h;
-    int rc = scan_record_check(rec, scan_offs[i + 1] - scan_offs[i], nmcu, h);
+    int rc = scan_record_check(rec, scan_offs[i + 1] - scan_offs[i], nmcu, h, sampling);
     memcpy(dst, rec, 384);
     rounds[i] = 0;
     for (int k = 0; k < 6 && !rc; ++k) {
@@ -517,7 +639,7 @@ int rnb_jpeg_decode_scans_subseq_host(const uint8_t* scans, long long scans_len,
       rc = build_huff(tb, tb + 16, total, tabs[(size_t)k]);
     }
     if (rc) {
-      memset(coef, 0, (size_t)(768 * nmcu));
+      memset(coef, 0, (size_t)(coef_bytes * nmcu));
       status[i] = rc;
       continue;
     }
@@ -530,13 +652,13 @@ int rnb_jpeg_decode_scans_subseq_host(const uint8_t* scans, long long scans_len,
         t.ac[c] = &tabs[(size_t)(2 * c + 1)];
       }
       for (long long v = 0; v < (long long)h.n_intervals; ++v) {
-        rc = decode_record_interval(rec, h, v, t, mw, nmcu, coef);
+        rc = decode_record_interval(rec, h, v, t, mw, nmcu, coef, geo);
         if (rc && !status[i]) status[i] = rc;
       }
       continue;
     }
     const uint8_t* scan = rec + SR_SPANS + 8;
-    memset(coef, 0, (size_t)(768 * nmcu));
+    memset(coef, 0, (size_t)(coef_bytes * nmcu));
     // pre-pass: data bytes per subsequence; the first marker ends the span
     bits.assign((size_t)pl.n_sub + 1, 0u);
     long long end = pl.end;
@@ -553,7 +675,7 @@ int rnb_jpeg_decode_scans_subseq_host(const uint8_t* scans, long long scans_len,
     exits.resize((size_t)n_sub);
     for (int s = 0; s < n_sub; ++s)
       subseq_scan(scan, start(s), end, (int)(8 * bits[(size_t)s]), tabs.data(), 0u,
-                  exits[(size_t)s]);
+                  exits[(size_t)s], geo);
     // synchronisation rounds
     dirty.assign((size_t)n_sub, 0);
     for (int r = 0; r < n_sub - 1; ++r) {
@@ -570,7 +692,7 @@ int rnb_jpeg_decode_scans_subseq_host(const uint8_t* scans, long long scans_len,
       for (int s = 1; s < n_sub; ++s)
         if (dirty[(size_t)s])
           subseq_scan(scan, start(s), end, (int)(8 * bits[(size_t)s]), tabs.data(),
-                      entry[(size_t)s], exits[(size_t)s]);
+                      entry[(size_t)s], exits[(size_t)s], geo);
     }
     // prefix sums: boundary bit positions, block indices, predictors
     blocks.assign((size_t)n_sub, 0u);
@@ -591,28 +713,48 @@ int rnb_jpeg_decode_scans_subseq_host(const uint8_t* scans, long long scans_len,
         d0 += exits[(size_t)s].dc0;
         d1 += exits[(size_t)s].dc1;
         d2 += exits[(size_t)s].dc2;
-        if (s + 1 < n_sub && ((entry[(size_t)s + 1] >> 6) & 7) != g % 6) return E_ARG;
+        if (s + 1 < n_sub && ((entry[(size_t)s + 1] >> 6) & 7) != g % geo.nb)
+          return E_ARG;
       }
       bits[(size_t)n_sub] = at;
     }
     // write pass; the lowest subsequence that fails holds the first error
-    long long bad_block = 6 * nmcu;
+    const long long total = geo.nb * nmcu;
+    long long bad_block = total;
     for (int s = 0; s < n_sub; ++s) {
-      if ((long long)blocks[(size_t)s] >= 6 * nmcu) break;
+      if ((long long)blocks[(size_t)s] >= total) break;
       rc = subseq_write(scan, start(s), end, (int)(bits[(size_t)s + 1] - bits[(size_t)s]),
                         s == n_sub - 1, (long long)bits[(size_t)n_sub] - bits[(size_t)s],
                         tabs.data(), entry[(size_t)s], blocks[(size_t)s], pred[3 * (size_t)s],
                         pred[3 * (size_t)s + 1], pred[3 * (size_t)s + 2], mw, nmcu, coef,
-                        bad_block);
+                        bad_block, geo);
       if (rc) {
         status[i] = rc;
         break;
       }
     }
-    for (long long g = bad_block; g < 6 * nmcu; ++g)
-      zero_block(mcu_block(coef, g / 6, (int)(g % 6), mw, nmcu));
+    for (long long g = bad_block; g < total; ++g)
+      zero_block(mcu_block(coef, g / geo.nb, (int)(g % geo.nb), mw, nmcu, geo));
   }
   return E_OK;
+}
+
+int rnb_jpeg_decode_scans_subseq_host(const uint8_t* scans, long long scans_len,
+                                      const long long* scan_offs, int nframes, int mw, int mh,
+                                      uint8_t* out, long long out_len, long long record_bytes,
+                                      int* status, int subseq_bytes, int* rounds) {
+  return decode_scans_subseq_host(scans, scans_len, scan_offs, nframes, mw, mh, out, out_len,
+                                  record_bytes, status, subseq_bytes, rounds, SAMPLING_420);
+}
+
+// The same with the geometry of `sampling`, as rnb_jpeg_decode_scans_host_s.
+int rnb_jpeg_decode_scans_subseq_host_s(const uint8_t* scans, long long scans_len,
+                                        const long long* scan_offs, int nframes, int mw, int mh,
+                                        uint8_t* out, long long out_len, long long record_bytes,
+                                        int* status, int subseq_bytes, int* rounds,
+                                        int sampling) {
+  return decode_scans_subseq_host(scans, scans_len, scan_offs, nframes, mw, mh, out, out_len,
+                                  record_bytes, status, subseq_bytes, rounds, sampling);
 }
 
 }  // extern "C"

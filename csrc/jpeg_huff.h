@@ -7,7 +7,9 @@
 // hipcc, and nothing here needs a HIP header.
 //
 // Frame record (what both decoders write; see jpeg_entropy.cpp):
-//   uint16 qt[3][64], then int16 blocks[6 * mw * mh][64] in natural order.
+//   uint16 qt[3][64], then int16 blocks[B * mw * mh][64] in natural order,
+//   B = Hs Vs + 2 blocks per MCU for luma sampling factors Hs x Vs: 6 (4:2:0,
+//   2x2), 4 (4:2:2, 2x1) or 3 (4:4:4, 1x1); see Geo below.
 //
 // Scan record (what rnb_jpeg_pack_scans writes and the interval decoders
 // read), 16-byte aligned, all integers little endian:
@@ -16,7 +18,12 @@
 //                                          the AC table of component c: the 16
 //                                          counts of codes of length 1..16,
 //                                          then the values, zero padded
-//   offset 2016  uint32 n_intervals, mcus_per_interval, scan_len, 0
+//   offset 2016  uint32 n_intervals, mcus_per_interval, scan_len, sampling
+//                                          sampling: 0 2x2, 1 2x1, 2 1x1 (so a
+//                                          4:2:0 record ends in 0, as it always
+//                                          did). It sizes nothing: the decoders
+//                                          take the geometry from their caller
+//                                          and refuse a record that disagrees.
 //                                          mcus_per_interval = min(DRI, nmcu),
 //                                          nmcu when DRI = 0; n_intervals =
 //                                          ceil(nmcu / mcus_per_interval)
@@ -53,7 +60,7 @@ enum {
   E_PRECISION = -6,    // sample precision other than 8 bits
   E_QT16 = -7,         // 16-bit quantisation table
   E_COMPONENTS = -8,   // component count other than 3
-  E_SAMPLING = -9,     // sampling factors other than 2x2, 1x1, 1x1
+  E_SAMPLING = -9,     // luma factors other than 2x2, 2x1, 1x1, or chroma other than 1x1
   E_MULTISCAN = -10,   // more than one scan, or a scan that is not all three components
   E_SIZE_CHANGE = -11, // frame size differs from the first frame's
   E_HUFFMAN = -12,     // a code that matches no entry / an invalid table
@@ -65,8 +72,35 @@ enum {
   E_RECORD = -18,      // record_bytes / out_cap too small for the frame
   E_DC_RANGE = -19,    // DC category > 11 or predictor outside int16
   E_SIZE = -20,        // zero width or height
-  E_SCANREC = -21,     // malformed scan record (header, span table or extent)
+  E_SCANREC = -21,     // malformed scan record (header, span table, extent, sampling word)
+  E_SAMPLING_CHANGE = -22,   // sampling differs from the first frame's
 };
+
+// The MCU of a sampling: luma factors (hs, vs) and nb = hs * vs + 2 blocks, the
+// Y blocks row-major, then Cb, then Cr. It covers 8 hs x 8 vs luma pixels.
+struct Geo {
+  int hs, vs, nb;
+};
+
+enum { SAMPLING_420 = 0, SAMPLING_422 = 1, SAMPLING_444 = 2 };
+
+// the sampling word of a scan record / the `sampling` argument of the entry
+// points -> its geometry; false for anything else
+RNB_HD inline bool geo_of(int sampling, Geo& g) {
+  if (sampling < SAMPLING_420 || sampling > SAMPLING_444) return false;
+  g.hs = sampling == SAMPLING_444 ? 1 : 2;
+  g.vs = sampling == SAMPLING_420 ? 2 : 1;
+  g.nb = g.hs * g.vs + 2;
+  return true;
+}
+
+RNB_HD inline Geo geo_420() {
+  Geo g = {2, 2, 6};
+  return g;
+}
+
+// component of block j of an MCU
+RNB_HD inline int block_comp(int j, const Geo& g) { return j < g.nb - 2 ? 0 : j - (g.nb - 3); }
 
 #define RNB_JPEG_ZIGZAG                                                                   \
   {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, \
@@ -249,12 +283,14 @@ struct Tables {
   const Huff* ac[3];
 };
 
-// block j = 0..5 of MCU m (4 Y blocks, Cb, Cr) inside a record's coefficients:
-// a function of the geometry alone
-RNB_HD inline int16_t* mcu_block(int16_t* coef, long long m, int j, long long mw, long long nmcu) {
-  if (j >= 4) return coef + 64 * (j * nmcu + m);         // (3 + c) * nmcu + m, c = j - 3
+// block j = 0..nb-1 of MCU m (the Y blocks, Cb, Cr) inside a record's
+// coefficients: a function of the geometry alone
+RNB_HD inline int16_t* mcu_block(int16_t* coef, long long m, int j, long long mw, long long nmcu,
+                                 const Geo& g = geo_420()) {
+  if (j >= g.nb - 2) return coef + 64 * (j * nmcu + m);   // (hs vs - 1 + c) * nmcu + m
   const long long my = m / mw, mx = m - my * mw;
-  return coef + 64 * ((2 * my + (j >> 1)) * (2 * mw) + 2 * mx + (j & 1));
+  // hs is 1 or 2: j / hs and j % hs
+  return coef + 64 * ((g.vs * my + (j >> (g.hs - 1))) * (g.hs * mw) + g.hs * mx + (j & (g.hs - 1)));
 }
 
 // One restart interval: n_mcu MCUs from MCU m0 on, decoded from p[begin .. end)
@@ -266,7 +302,8 @@ RNB_HD inline int16_t* mcu_block(int16_t* coef, long long m, int j, long long mw
 // it happened in and the interval's remaining blocks are zeroed.
 RNB_HD inline int decode_interval(Bits& b, const uint8_t* p, long long begin, long long end,
                                   const Tables& t, long long m0, long long n_mcu, long long mw,
-                                  long long nmcu, int16_t* coef, bool zero_tail) {
+                                  long long nmcu, int16_t* coef, bool zero_tail,
+                                  const Geo& g = geo_420()) {
   b.p = p;
   b.pos = begin;
   b.end = end;
@@ -275,21 +312,22 @@ RNB_HD inline int decode_interval(Bits& b, const uint8_t* p, long long begin, lo
   int rc = E_OK;
   long long i = 0;
   int j = 0;
+  const int ny = g.nb - 2;
   for (; i < n_mcu; ++i) {
     const long long m = m0 + i;
-    for (j = 0; j < 4; ++j) {
-      rc = decode_block(b, *t.dc[0], *t.ac[0], pred0, mcu_block(coef, m, j, mw, nmcu));
+    for (j = 0; j < ny; ++j) {
+      rc = decode_block(b, *t.dc[0], *t.ac[0], pred0, mcu_block(coef, m, j, mw, nmcu, g));
       if (rc) break;
     }
     if (rc) break;
-    rc = decode_block(b, *t.dc[1], *t.ac[1], pred1, mcu_block(coef, m, 4, mw, nmcu));
-    if (rc) { j = 4; break; }
-    rc = decode_block(b, *t.dc[2], *t.ac[2], pred2, mcu_block(coef, m, 5, mw, nmcu));
-    if (rc) { j = 5; break; }
+    rc = decode_block(b, *t.dc[1], *t.ac[1], pred1, mcu_block(coef, m, ny, mw, nmcu, g));
+    if (rc) { j = ny; break; }
+    rc = decode_block(b, *t.dc[2], *t.ac[2], pred2, mcu_block(coef, m, ny + 1, mw, nmcu, g));
+    if (rc) { j = ny + 1; break; }
   }
   if (rc && zero_tail) {
     for (; i < n_mcu; ++i, j = 0)
-      for (; j < 6; ++j) zero_block(mcu_block(coef, m0 + i, j, mw, nmcu));
+      for (; j < g.nb; ++j) zero_block(mcu_block(coef, m0 + i, j, mw, nmcu, g));
   }
   return rc;
 }
@@ -312,11 +350,14 @@ RNB_HD inline uint32_t load_u32(const uint8_t* p) {
 
 // Validate the header of the scan record at rec, which may use `extent` bytes,
 // for a frame of nmcu MCUs: afterwards the span table and scan[] lie inside
-// the extent and the intervals tile the frame's MCUs exactly.
+// the extent, the intervals tile the frame's MCUs exactly, and the record's
+// sampling word is the caller's `sampling` (SAMPLING_420 ..): the word is only
+// compared, the geometry is the caller's.
 RNB_HD inline int scan_record_check(const uint8_t* rec, long long extent, long long nmcu,
-                                    ScanHeader& h) {
+                                    ScanHeader& h, int sampling = SAMPLING_420) {
   h.n_intervals = h.mcus_per_interval = h.scan_len = 0;
   if (extent < SR_SPANS + 8) return E_SCANREC;
+  if (load_u32(rec + SR_HEADER + 12) != (uint32_t)sampling) return E_SCANREC;
   h.n_intervals = load_u32(rec + SR_HEADER);
   h.mcus_per_interval = load_u32(rec + SR_HEADER + 4);
   h.scan_len = load_u32(rec + SR_HEADER + 8);
@@ -333,7 +374,7 @@ RNB_HD inline int scan_record_check(const uint8_t* rec, long long extent, long l
 // overrun (E_TRUNCATED, from decode_block).
 RNB_HD inline int decode_record_interval(const uint8_t* rec, const ScanHeader& h, long long i,
                                          const Tables& t, long long mw, long long nmcu,
-                                         int16_t* coef) {
+                                         int16_t* coef, const Geo& g = geo_420()) {
   const long long per = h.mcus_per_interval;
   const long long m0 = i * per;
   const long long n_mcu = nmcu - m0 < per ? nmcu - m0 : per;
@@ -341,12 +382,12 @@ RNB_HD inline int decode_record_interval(const uint8_t* rec, const ScanHeader& h
   const long long begin = load_u32(sp), end = load_u32(sp + 4);
   if (begin > end || end > (long long)h.scan_len) {
     for (long long k = 0; k < n_mcu; ++k)
-      for (int j = 0; j < 6; ++j) zero_block(mcu_block(coef, m0 + k, j, mw, nmcu));
+      for (int j = 0; j < g.nb; ++j) zero_block(mcu_block(coef, m0 + k, j, mw, nmcu, g));
     return E_SCANREC;
   }
   const uint8_t* scan = rec + SR_SPANS + 8LL * h.n_intervals;
   Bits b;
-  const int rc = decode_interval(b, scan, begin, end, t, m0, n_mcu, mw, nmcu, coef, true);
+  const int rc = decode_interval(b, scan, begin, end, t, m0, n_mcu, mw, nmcu, coef, true, g);
   if (rc) return rc;
   if (i + 1 < (long long)h.n_intervals && (!interval_ended(b) || b.pos != end)) return E_RESTART;
   return E_OK;
@@ -463,7 +504,8 @@ RNB_HD inline long long subseq_start(const uint8_t* p, long long begin, long lon
   return b0 + ((b0 > begin && p[b0] == 0x00 && p[b0 - 1] == 0xFF) ? 1 : 0);
 }
 
-// state: (bits behind the boundary << 9) | (j << 6) | k
+// state: (bits behind the boundary << 9) | (j << 6) | k; an MCU has at most 6
+// blocks whatever the sampling, so j fits its three bits
 RNB_HD inline uint32_t subseq_state(int off, int j, int k) {
   return ((uint32_t)(off > 63 ? 63 : off) << 9) | ((uint32_t)j << 6) | (uint32_t)k;
 }
@@ -495,7 +537,8 @@ struct SubseqExit {
 // the exit state lies fewer than 31 bits behind the next boundary. tabs: the
 // six tables of the scan record (2c: DC, 2c + 1: AC of component c).
 RNB_HD inline void subseq_scan(const uint8_t* p, long long at, long long end, int limit,
-                               const Huff* tabs, uint32_t entry, SubseqExit& x) {
+                               const Huff* tabs, uint32_t entry, SubseqExit& x,
+                               const Geo& geo = geo_420()) {
   int j = (int)(entry >> 6) & 7, k = (int)(entry & 63);
   int pos = (int)(entry >> 9);
   Bits b;
@@ -505,7 +548,7 @@ RNB_HD inline void subseq_scan(const uint8_t* p, long long at, long long end, in
   while (pos < limit) {
     if (b.n < 32) b.fill();
     const int n0 = b.n;
-    const int c = j < 4 ? 0 : j - 3;
+    const int c = block_comp(j, geo);
     bool done = false;
     if (k == 0) {
       const int s = decode_symbol(b, tabs[2 * c]);
@@ -546,7 +589,7 @@ RNB_HD inline void subseq_scan(const uint8_t* p, long long at, long long end, in
     pos += n0 - b.n;
     if (done) {
       k = 0;
-      j = j == 5 ? 0 : j + 1;
+      j = j >= geo.nb - 1 ? 0 : j + 1;
       ++nb;
     }
   }
@@ -567,7 +610,7 @@ RNB_HD inline int subseq_clamp_pred(long long v) {
 // index g and predictors, decode every symbol that starts in front of `limit`
 // (`last`: no limit, the span's last subsequence goes on over the reader's zero
 // bits until its block ends, as the serial loop does) and store the non-zero
-// coefficients of blocks g < 6 nmcu; `rem` is the number of real bits from the
+// coefficients of blocks g < nb nmcu; `rem` is the number of real bits from the
 // subsequence's boundary to the end of the span, for E_TRUNCATED. Stops at the
 // first error and returns its code, the block in bad_block: with decode_block's
 // checks in decode_block's order, so the lowest subsequence that reports one
@@ -575,17 +618,17 @@ RNB_HD inline int subseq_clamp_pred(long long v) {
 RNB_HD inline int subseq_write(const uint8_t* p, long long at, long long end, int limit, bool last,
                                long long rem, const Huff* tabs, uint32_t entry, long long g,
                                int p0, int p1, int p2, long long mw, long long nmcu, int16_t* coef,
-                               long long& bad_block) {
-  const long long total = 6 * nmcu;
+                               long long& bad_block, const Geo& geo = geo_420()) {
+  const long long total = geo.nb * nmcu;
   int k = (int)(entry & 63);
   long long pos = (long long)(entry >> 9);
-  long long m = g / 6;
-  int j = (int)(g - 6 * m);
+  long long m = g / geo.nb;
+  int j = (int)(g - geo.nb * m);
   Bits b;
   subseq_open(b, p, at, end, (int)pos);
   while (g < total && (last || pos < limit)) {
-    int16_t* blk = mcu_block(coef, m, j, mw, nmcu);
-    const int c = j < 4 ? 0 : j - 3;
+    int16_t* blk = mcu_block(coef, m, j, mw, nmcu, geo);
+    const int c = block_comp(j, geo);
     bool done = false;
     while (!done && (last || pos < limit)) {
       if (b.n < 32) b.fill();
@@ -648,7 +691,7 @@ RNB_HD inline int subseq_write(const uint8_t* p, long long at, long long end, in
     }
     k = 0;
     ++g;
-    if (++j == 6) {
+    if (++j == geo.nb) {
       j = 0;
       ++m;
     }

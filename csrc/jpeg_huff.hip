@@ -17,13 +17,18 @@
 //                    by synchronised subsequences (jpeg_huff_subseq_kernel
 //                    below; the passes are in jpeg_huff.h) and every other
 //                    frame as above.
+//  * rnb_jpeg_huff_s / rnb_jpeg_huff_subseq_s  the same for 4:2:0, 4:2:2 and
+//                    4:4:4 records (sampling 0 / 1 / 2): the kernels are
+//                    instantiated per MCU geometry (jpeg_huff.h: Geo), which
+//                    comes from the launcher's argument; a scan record whose
+//                    sampling word is another one is refused (E_SCANREC).
 //
 // Addresses and trip counts: every block address is a function of (interval,
 // MCU, block) and the launcher's geometry (mcu_block); every byte read is
 // checked against the lane's span, the span against scan_len, and scan_len and
 // the span table against the record's extent (scan_record_check), which the
-// kernel checks against the buffer. A block takes at most 64 symbols, an MCU 6
-// blocks, an interval mcus_per_interval MCUs. Corrupt data gives a code in
+// kernel checks against the buffer. A block takes at most 64 symbols, an MCU
+// B <= 6 blocks, an interval mcus_per_interval MCUs. Corrupt data gives a code in
 // status[frame] and zeroed blocks, never another address or a long loop.
 //
 // Every block of every frame record is written (zeroed, then filled), and
@@ -46,6 +51,14 @@ struct JpegHuffArgs {
   int mw, mh;
 };
 
+template <int SAMPLING>
+static __device__ __forceinline__ Geo kernel_geo() {
+  constexpr int hs = SAMPLING == SAMPLING_444 ? 1 : 2, vs = SAMPLING == SAMPLING_420 ? 2 : 1;
+  Geo g = {hs, vs, hs * vs + 2};
+  return g;
+}
+
+template <int SAMPLING>
 __global__ __launch_bounds__(JPEG_HUFF_LANES) void jpeg_huff_kernel(
     const uint8_t* __restrict__ scans, const long long* __restrict__ scan_offs,
     uint8_t* __restrict__ records, int* __restrict__ status, JpegHuffArgs a) {
@@ -55,6 +68,7 @@ __global__ __launch_bounds__(JPEG_HUFF_LANES) void jpeg_huff_kernel(
   const int t = (int)threadIdx.x;
   const long long frame = blockIdx.x;
   const long long nmcu = (long long)a.mw * a.mh;
+  const Geo geo = kernel_geo<SAMPLING>();
   uint8_t* dst = records + frame * a.record_bytes;
   int16_t* coef = (int16_t*)(dst + 384);
   // the record's extent, from the device copy of the offset table: checked
@@ -63,7 +77,7 @@ __global__ __launch_bounds__(JPEG_HUFF_LANES) void jpeg_huff_kernel(
   const bool inside = o0 >= 0 && (o0 & 15) == 0 && o1 <= a.scans_len && o1 - o0 >= SR_SPANS + 8;
   const uint8_t* rec = scans + (inside ? o0 : 0);
   ScanHeader h = {0u, 0u, 0u};
-  const int head_rc = inside ? scan_record_check(rec, o1 - o0, nmcu, h) : (int)E_SCANREC;
+  const int head_rc = inside ? scan_record_check(rec, o1 - o0, nmcu, h, SAMPLING) : (int)E_SCANREC;
   if (t == 0) {
     table_rc = E_OK;
     first_bad = 0xFFFFFFFFu;
@@ -82,7 +96,7 @@ __global__ __launch_bounds__(JPEG_HUFF_LANES) void jpeg_huff_kernel(
   __syncthreads();
   const int frame_rc = head_rc ? head_rc : table_rc;
   if (frame_rc) {
-    for (long long i = t; i < 48 * nmcu; i += JPEG_HUFF_LANES)     // 768 nmcu bytes
+    for (long long i = t; i < 8 * geo.nb * nmcu; i += JPEG_HUFF_LANES)     // 128 B nmcu bytes
       ((uint4*)coef)[i] = make_uint4(0u, 0u, 0u, 0u);
     if (t == 0) status[frame] = frame_rc;
     return;
@@ -94,8 +108,8 @@ __global__ __launch_bounds__(JPEG_HUFF_LANES) void jpeg_huff_kernel(
   }
   bool failed = false;
   for (long long i = t; i < (long long)h.n_intervals; i += JPEG_HUFF_LANES) {
-    const int rc = decode_record_interval(rec, h, i, tb, a.mw, nmcu, coef);
-    if (rc && !failed) {                // a lane's intervals ascend: its first failure is its lowest
+    const int rc = decode_record_interval(rec, h, i, tb, a.mw, nmcu, coef, geo);
+    if (rc && !failed) {              // a lane's intervals ascend: its first failure is its lowest
       failed = true;
       atomicMin(&first_bad, ((unsigned)i << 5) | (unsigned)(-rc));
     }
@@ -114,10 +128,10 @@ __global__ __launch_bounds__(JPEG_HUFF_LANES) void jpeg_huff_kernel(
 // behind a barrier, so the round loop's trip count is uniform. Every other
 // frame goes lane per interval through decode_record_interval, as before.
 // Bounds: a subsequence is scanned in at most 8 S iterations, at most
-// n_sub - 1 rounds run, the write pass stops at block 6 nmcu or its first
+// n_sub - 1 rounds run, the write pass stops at block B nmcu or its first
 // error; every block address comes from mcu_block with a block index below
-// 6 nmcu, every byte read lies inside the span.
-template <int LANES>
+// B nmcu, every byte read lies inside the span.
+template <int LANES, int SAMPLING>
 __global__ __launch_bounds__(LANES) void jpeg_huff_subseq_kernel(
     const uint8_t* __restrict__ scans, const long long* __restrict__ scan_offs,
     uint8_t* __restrict__ records, int* __restrict__ status, int* __restrict__ rounds,
@@ -136,13 +150,14 @@ __global__ __launch_bounds__(LANES) void jpeg_huff_subseq_kernel(
   const int t = (int)threadIdx.x;
   const long long frame = blockIdx.x;
   const long long nmcu = (long long)a.mw * a.mh;
+  const Geo geo = kernel_geo<SAMPLING>();
   uint8_t* dst = records + frame * a.record_bytes;
   int16_t* coef = (int16_t*)(dst + 384);
   const long long o0 = scan_offs[frame], o1 = scan_offs[frame + 1];
   const bool inside = o0 >= 0 && (o0 & 15) == 0 && o1 <= a.scans_len && o1 - o0 >= SR_SPANS + 8;
   const uint8_t* rec = scans + (inside ? o0 : 0);
   ScanHeader h = {0u, 0u, 0u};
-  const int head_rc = inside ? scan_record_check(rec, o1 - o0, nmcu, h) : (int)E_SCANREC;
+  const int head_rc = inside ? scan_record_check(rec, o1 - o0, nmcu, h, SAMPLING) : (int)E_SCANREC;
   SubseqPlan pl;
   const bool split = head_rc == E_OK && subseq_plan(rec, h, subseq_bytes, pl);
   if (t == 0) {
@@ -150,7 +165,7 @@ __global__ __launch_bounds__(LANES) void jpeg_huff_subseq_kernel(
     first_bad = 0xFFFFFFFFu;
     span_end = split ? (unsigned)pl.end : 0u;
     changed[0] = changed[1] = 0;
-    bad_block = 6 * nmcu;
+    bad_block = geo.nb * nmcu;
   }
   __syncthreads();
   if (t < 24)                           // qt: 384 bytes, 16 per lane
@@ -166,7 +181,7 @@ __global__ __launch_bounds__(LANES) void jpeg_huff_subseq_kernel(
   __syncthreads();
   const int frame_rc = head_rc ? head_rc : table_rc;
   if (frame_rc || split) {              // refused: all zero; split: zero, then only non-zeros
-    for (long long i = t; i < 48 * nmcu; i += LANES)
+    for (long long i = t; i < 8 * geo.nb * nmcu; i += LANES)
       ((uint4*)coef)[i] = make_uint4(0u, 0u, 0u, 0u);
   }
   if (frame_rc) {
@@ -184,7 +199,7 @@ __global__ __launch_bounds__(LANES) void jpeg_huff_subseq_kernel(
     }
     bool failed = false;
     for (long long i = t; i < (long long)h.n_intervals; i += LANES) {
-      const int rc = decode_record_interval(rec, h, i, tb, a.mw, nmcu, coef);
+      const int rc = decode_record_interval(rec, h, i, tb, a.mw, nmcu, coef, geo);
       if (rc && !failed) {
         failed = true;
         atomicMin(&first_bad, ((unsigned)i << 5) | (unsigned)(-rc));
@@ -214,7 +229,7 @@ __global__ __launch_bounds__(LANES) void jpeg_huff_subseq_kernel(
   for (int i = t; i < n_sub; i += LANES) {
     SubseqExit x;
     subseq_scan(scan, subseq_start(scan, pl.begin, pl.begin + i * pl.S), end, (int)(8u * s_bits[i]),
-                tabs, 0u, x);
+                tabs, 0u, x, geo);
     s_entry[i] = 0;
     s_exit[i] = (uint16_t)x.state;
     s_blocks[i] = x.blocks;
@@ -243,7 +258,7 @@ __global__ __launch_bounds__(LANES) void jpeg_huff_subseq_kernel(
       if (dirty >> q & 1u) {
         SubseqExit x;
         subseq_scan(scan, subseq_start(scan, pl.begin, pl.begin + i * pl.S), end,
-                    (int)(8u * s_bits[i]), tabs, s_entry[i], x);
+                    (int)(8u * s_bits[i]), tabs, s_entry[i], x, geo);
         s_exit[i] = (uint16_t)x.state;
         s_blocks[i] = x.blocks;
         s_dc[0][i] = x.dc0; s_dc[1][i] = x.dc1; s_dc[2][i] = x.dc2;
@@ -281,11 +296,12 @@ __global__ __launch_bounds__(LANES) void jpeg_huff_subseq_kernel(
   long long my_bad = 0;
   for (int i = t; i < n_sub; i += LANES) {
     const long long g = s_blocks[i];
-    if (g >= 6 * nmcu) break;
+    if (g >= geo.nb * nmcu) break;
     const int rc = subseq_write(scan, subseq_start(scan, pl.begin, pl.begin + i * pl.S), end,
                                 (int)(s_bits[i + 1] - s_bits[i]), i == n_sub - 1,
                                 (long long)s_bits[n_sub] - s_bits[i], tabs, s_entry[i], g,
-                                s_dc[0][i], s_dc[1][i], s_dc[2][i], a.mw, nmcu, coef, my_bad);
+                                s_dc[0][i], s_dc[1][i], s_dc[2][i], a.mw, nmcu, coef, my_bad,
+                                geo);
     if (rc) {
       my_sub = i;
       atomicMin(&first_bad, ((unsigned)i << 5) | (unsigned)(-rc));
@@ -296,8 +312,8 @@ __global__ __launch_bounds__(LANES) void jpeg_huff_subseq_kernel(
   const unsigned bad = first_bad;
   if (bad != 0xFFFFFFFFu && (int)(bad >> 5) == my_sub) bad_block = my_bad;
   __syncthreads();
-  for (long long g = bad_block + t; g < 6 * nmcu; g += LANES)
-    zero_block(mcu_block(coef, g / 6, (int)(g % 6), a.mw, nmcu));
+  for (long long g = bad_block + t; g < geo.nb * nmcu; g += LANES)
+    zero_block(mcu_block(coef, g / geo.nb, (int)(g % geo.nb), a.mw, nmcu, geo));
   if (t == 0) {
     status[frame] = bad == 0xFFFFFFFFu ? 0 : -(int)(bad & 31u);
     rounds[frame] = nrounds;
@@ -310,7 +326,9 @@ __global__ __launch_bounds__(LANES) void jpeg_huff_subseq_kernel(
 static int jpeg_huff_checks(const void* scans, long long scans_len,
                             const long long* scan_offs_host, const void* scan_offs_dev,
                             int nframes, int mw, int mh, void* records, long long rec_len,
-                            long long record_bytes, void* status) {
+                            long long record_bytes, void* status, int sampling) {
+  Geo geo;
+  if (!geo_of(sampling, geo)) return -2;
   if (nframes == 0) return 1;
   if (nframes < 0 || mw < 1 || mh < 1 || mw > 4096 || mh > 4096) return -2;
   if (!scans || !scan_offs_host || !scan_offs_dev || !records || !status) return -2;
@@ -319,7 +337,7 @@ static int jpeg_huff_checks(const void* scans, long long scans_len,
       ((uintptr_t)scan_offs_dev & 7u) != 0 || ((uintptr_t)status & 3u) != 0 ||
       record_bytes % 16 != 0)
     return -2;
-  if (record_bytes < 384 + 768 * n) return -4;
+  if (record_bytes < 384 + 128 * geo.nb * n) return -4;
   if (rec_len < 0 || scans_len < 0 || record_bytes > rec_len / nframes) return -4;
   if (scan_offs_host[0] < 0 || scan_offs_host[nframes] > scans_len) return -4;
   for (int i = 0; i < nframes; ++i) {
@@ -327,6 +345,55 @@ static int jpeg_huff_checks(const void* scans, long long scans_len,
     if (scan_offs_host[i + 1] - scan_offs_host[i] < SR_SPANS + 8) return -4;
   }
   return 0;
+}
+
+static int jpeg_huff_launch(const void* scans, long long scans_len,
+                            const long long* scan_offs_host, const void* scan_offs_dev,
+                            int nframes, int mw, int mh, void* records, long long rec_len,
+                            long long record_bytes, void* status, int sampling,
+                            hipStream_t stream) {
+  const int rc = jpeg_huff_checks(scans, scans_len, scan_offs_host, scan_offs_dev, nframes, mw, mh,
+                                  records, rec_len, record_bytes, status, sampling);
+  if (rc) return rc > 0 ? 0 : rc;
+  JpegHuffArgs a;
+  a.scans_len = scans_len;
+  a.record_bytes = record_bytes;
+  a.mw = mw;
+  a.mh = mh;
+  auto kernel = sampling == SAMPLING_420 ? jpeg_huff_kernel<SAMPLING_420>
+                : sampling == SAMPLING_422 ? jpeg_huff_kernel<SAMPLING_422>
+                                           : jpeg_huff_kernel<SAMPLING_444>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nframes), dim3(JPEG_HUFF_LANES), 0, stream,
+                     (const uint8_t*)scans, (const long long*)scan_offs_dev, (uint8_t*)records,
+                     (int*)status, a);
+  return (int)hipGetLastError();
+}
+
+static int jpeg_huff_subseq_launch(const void* scans, long long scans_len,
+                                   const long long* scan_offs_host, const void* scan_offs_dev,
+                                   int nframes, int mw, int mh, void* records, long long rec_len,
+                                   long long record_bytes, void* status, int subseq_bytes,
+                                   void* rounds, int sampling, hipStream_t stream) {
+  const int rc = jpeg_huff_checks(scans, scans_len, scan_offs_host, scan_offs_dev, nframes, mw, mh,
+                                  records, rec_len, record_bytes, status, sampling);
+  if (rc < 0) return rc;
+  if (!subseq_bytes_ok(subseq_bytes)) return -2;
+  if (rc > 0) return 0;
+  if (!rounds || ((uintptr_t)rounds & 3u) != 0) return -2;
+  JpegHuffArgs a;
+  a.scans_len = scans_len;
+  a.record_bytes = record_bytes;
+  a.mw = mw;
+  a.mh = mh;
+  auto kernel = sampling == SAMPLING_420
+                    ? jpeg_huff_subseq_kernel<JPEG_SUBSEQ_LANES, SAMPLING_420>
+                    : sampling == SAMPLING_422
+                          ? jpeg_huff_subseq_kernel<JPEG_SUBSEQ_LANES, SAMPLING_422>
+                          : jpeg_huff_subseq_kernel<JPEG_SUBSEQ_LANES, SAMPLING_444>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nframes), dim3(JPEG_SUBSEQ_LANES), 0, stream,
+                     (const uint8_t*)scans, (const long long*)scan_offs_dev, (uint8_t*)records,
+                     (int*)status, (int*)rounds, a, subseq_bytes);
+  return (int)hipGetLastError();
 }
 
 extern "C" {
@@ -342,18 +409,18 @@ extern "C" {
 int rnb_jpeg_huff(const void* scans, long long scans_len, const long long* scan_offs_host,
                   const void* scan_offs_dev, int nframes, int mw, int mh, void* records,
                   long long rec_len, long long record_bytes, void* status, hipStream_t stream) {
-  const int rc = jpeg_huff_checks(scans, scans_len, scan_offs_host, scan_offs_dev, nframes, mw, mh,
-                                  records, rec_len, record_bytes, status);
-  if (rc) return rc > 0 ? 0 : rc;
-  JpegHuffArgs a;
-  a.scans_len = scans_len;
-  a.record_bytes = record_bytes;
-  a.mw = mw;
-  a.mh = mh;
-  hipLaunchKernelGGL(jpeg_huff_kernel, dim3((unsigned)nframes), dim3(JPEG_HUFF_LANES), 0, stream,
-                     (const uint8_t*)scans, (const long long*)scan_offs_dev, (uint8_t*)records,
-                     (int*)status, a);
-  return (int)hipGetLastError();
+  return jpeg_huff_launch(scans, scans_len, scan_offs_host, scan_offs_dev, nframes, mw, mh,
+                          records, rec_len, record_bytes, status, SAMPLING_420, stream);
+}
+
+// The same for records of `sampling` (0 4:2:0, 1 4:2:2, 2 4:4:4; -2 otherwise):
+// (mw, mh) count its MCUs and a frame record is >= 384 + 128 B mw mh bytes.
+int rnb_jpeg_huff_s(const void* scans, long long scans_len, const long long* scan_offs_host,
+                    const void* scan_offs_dev, int nframes, int mw, int mh, void* records,
+                    long long rec_len, long long record_bytes, void* status, int sampling,
+                    hipStream_t stream) {
+  return jpeg_huff_launch(scans, scans_len, scan_offs_host, scan_offs_dev, nframes, mw, mh,
+                          records, rec_len, record_bytes, status, sampling, stream);
 }
 
 // As rnb_jpeg_huff, with frames of one interval decoded by synchronised
@@ -366,22 +433,20 @@ int rnb_jpeg_huff_subseq(const void* scans, long long scans_len, const long long
                          const void* scan_offs_dev, int nframes, int mw, int mh, void* records,
                          long long rec_len, long long record_bytes, void* status,
                          int subseq_bytes, void* rounds, hipStream_t stream) {
-  const int rc = jpeg_huff_checks(scans, scans_len, scan_offs_host, scan_offs_dev, nframes, mw, mh,
-                                  records, rec_len, record_bytes, status);
-  if (rc < 0) return rc;
-  if (!subseq_bytes_ok(subseq_bytes)) return -2;
-  if (rc > 0) return 0;
-  if (!rounds || ((uintptr_t)rounds & 3u) != 0) return -2;
-  JpegHuffArgs a;
-  a.scans_len = scans_len;
-  a.record_bytes = record_bytes;
-  a.mw = mw;
-  a.mh = mh;
-  hipLaunchKernelGGL(jpeg_huff_subseq_kernel<JPEG_SUBSEQ_LANES>, dim3((unsigned)nframes),
-                     dim3(JPEG_SUBSEQ_LANES), 0, stream, (const uint8_t*)scans,
-                     (const long long*)scan_offs_dev, (uint8_t*)records, (int*)status,
-                     (int*)rounds, a, subseq_bytes);
-  return (int)hipGetLastError();
+  return jpeg_huff_subseq_launch(scans, scans_len, scan_offs_host, scan_offs_dev, nframes, mw, mh,
+                                 records, rec_len, record_bytes, status, subseq_bytes, rounds,
+                                 SAMPLING_420, stream);
+}
+
+// The same for records of `sampling`, as rnb_jpeg_huff_s.
+int rnb_jpeg_huff_subseq_s(const void* scans, long long scans_len,
+                           const long long* scan_offs_host, const void* scan_offs_dev,
+                           int nframes, int mw, int mh, void* records, long long rec_len,
+                           long long record_bytes, void* status, int subseq_bytes, void* rounds,
+                           int sampling, hipStream_t stream) {
+  return jpeg_huff_subseq_launch(scans, scans_len, scan_offs_host, scan_offs_dev, nframes, mw, mh,
+                                 records, rec_len, record_bytes, status, subseq_bytes, rounds,
+                                 sampling, stream);
 }
 
 }  // extern "C"

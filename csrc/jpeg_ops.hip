@@ -9,6 +9,13 @@
 //                    [8*mh][8*mw], 384*mw*mh bytes per frame. Per sample:
 //                    coefficient x table entry, separable 8-point IDCT in
 //                    fp32, + 128, round to nearest, clamp to [0, 255].
+//  * rnb_jpeg_idct_s the same for any of the three chroma layouts (sampling 0:
+//                    4:2:0 as above, 1: 4:2:2, 2: 4:4:4; luma factors Hs x Vs =
+//                    2x2, 2x1, 1x1): a record holds B = Hs Vs + 2 blocks per MCU,
+//                    the Y blocks row-major over the padded (Vs mh) x (Hs mw)
+//                    grid, then Cb, then Cr (384 + 128 B mw mh bytes); the frame
+//                    is Y [8 Vs mh][8 Hs mw], Cb and Cr [8 mh][8 mw], 64 B mw mh
+//                    bytes.
 //
 // Every address is a function of (frame, block, line) and the geometry the
 // launcher validated, never of a coefficient: corrupt coefficients give wrong
@@ -39,7 +46,7 @@ __device__ __attribute__((aligned(16))) const float kJpegBasis[8][8] = {
 
 struct JpegIdctArgs {
   long long record_bytes;
-  long long total_blocks;          // nframes * 6 * mw * mh
+  long long total_blocks;          // nframes * B * mw * mh
   int mw, mh;
 };
 
@@ -54,7 +61,10 @@ static __device__ __forceinline__ uint32_t jpeg_sample(float s) {
 // registers; the 8x8 intermediate goes through LDS; thread x then transforms
 // along the columns for output row x and ends with 8 adjacent samples, written
 // with one 8-byte store. Blocks that are neighbours in x are neighbours in the
-// record, so a wave's stores form 64-byte runs per row.
+// record, so a wave's stores form 64-byte runs per row. HS, VS: the luma
+// sampling factors; block -> (component, plane position) follows from them and
+// (mw, mh) alone.
+template <int HS, int VS>
 __global__ __launch_bounds__(256) void jpeg_idct_kernel(const uint8_t* __restrict__ rec,
                                                         uint8_t* __restrict__ surf,
                                                         JpegIdctArgs a) {
@@ -64,10 +74,11 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const uint8_t* __restric
   const long long gb = (long long)blockIdx.x * JPEG_BLOCKS_PER_WG + lb;
   const bool live = gb < a.total_blocks;
   const int n = a.mw * a.mh;                     // MCUs per frame
-  const int per_frame = 6 * n;
+  constexpr int NY = HS * VS;                    // Y blocks per MCU
+  const int per_frame = (NY + 2) * n;
   const long long frame = live ? gb / per_frame : 0;
   const int b = live ? (int)(gb - frame * per_frame) : 0;
-  const int comp = b < 4 * n ? 0 : (b < 5 * n ? 1 : 2);
+  const int comp = b < NY * n ? 0 : (b < (NY + 1) * n ? 1 : 2);
   float* tile = lds + lb * JPEG_BLK_STRIDE;
   if (live) {
     const uint8_t* r = rec + frame * a.record_bytes;
@@ -110,17 +121,47 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const uint8_t* __restric
   const uint32_t w1 = jpeg_sample(s[4]) | (jpeg_sample(s[5]) << 8) | (jpeg_sample(s[6]) << 16) |
                       (jpeg_sample(s[7]) << 24);
   // block -> plane position (all from the geometry)
-  int pb = b, cols = 2 * a.mw;
+  int pb = b, cols = HS * a.mw;
   long long plane = 0;
   if (comp) {
-    pb = b - (3 + comp) * n;
+    pb = b - (NY - 1 + comp) * n;
     cols = a.mw;
-    plane = (long long)(192 + 64 * comp) * n;    // 256 n (Cb), 320 n (Cr)
+    plane = (long long)(64 * (NY - 1) + 64 * comp) * n;    // 4:2:0: 256 n (Cb), 320 n (Cr)
   }
   const int by = pb / cols, bx = pb - by * cols;
-  uint8_t* dst = surf + frame * (384LL * n) + plane + ((long long)by * 8 + line) * (8 * cols) +
-                 bx * 8;
+  uint8_t* dst = surf + frame * (64LL * (NY + 2) * n) + plane +
+                 ((long long)by * 8 + line) * (8 * cols) + bx * 8;
   *(uint2*)dst = make_uint2(w0, w1);
+}
+
+// sampling: 0 4:2:0, 1 4:2:2, 2 4:4:4 (-2 otherwise)
+static int jpeg_idct_launch(const void* rec, long long rec_len, long long record_bytes,
+                            int nframes, int mw, int mh, void* surf, long long surf_len,
+                            int sampling, hipStream_t stream) {
+  if (nframes == 0) return 0;
+  if (nframes < 0 || mw < 1 || mh < 1 || mw > 4096 || mh > 4096) return -2;
+  if (sampling < 0 || sampling > 2) return -2;
+  const long long nb = sampling == 0 ? 6 : sampling == 1 ? 4 : 3;    // blocks per MCU
+  const long long n = (long long)mw * mh;
+  if (((uintptr_t)rec & 15u) != 0 || ((uintptr_t)surf & 7u) != 0 || record_bytes % 16 != 0)
+    return -2;
+  if (record_bytes < 384 + 128 * nb * n) return -4;
+  if (rec_len < 0 || surf_len < 0 || record_bytes > rec_len / nframes ||
+      64 * nb * n > surf_len / nframes)
+    return -4;
+  const long long total = nb * n * nframes;
+  const long long groups = (total + JPEG_BLOCKS_PER_WG - 1) / JPEG_BLOCKS_PER_WG;
+  if (groups > 0x7FFFFFFFLL) return -2;
+  JpegIdctArgs a;
+  a.record_bytes = record_bytes;
+  a.total_blocks = total;
+  a.mw = mw;
+  a.mh = mh;
+  auto kernel = sampling == 0 ? jpeg_idct_kernel<2, 2>
+                              : sampling == 1 ? jpeg_idct_kernel<2, 1> : jpeg_idct_kernel<1, 1>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(256), 0, stream, (const uint8_t*)rec,
+                     (uint8_t*)surf, a);
+  return (int)hipGetLastError();
 }
 
 extern "C" {
@@ -131,26 +172,16 @@ extern "C" {
 // is launched).
 int rnb_jpeg_idct(const void* rec, long long rec_len, long long record_bytes, int nframes,
                   int mw, int mh, void* surf, long long surf_len, hipStream_t stream) {
-  if (nframes == 0) return 0;
-  if (nframes < 0 || mw < 1 || mh < 1 || mw > 4096 || mh > 4096) return -2;
-  const long long n = (long long)mw * mh;
-  if (((uintptr_t)rec & 15u) != 0 || ((uintptr_t)surf & 7u) != 0 || record_bytes % 16 != 0)
-    return -2;
-  if (record_bytes < 384 + 768 * n) return -4;
-  if (rec_len < 0 || surf_len < 0 || record_bytes > rec_len / nframes ||
-      384 * n > surf_len / nframes)
-    return -4;
-  const long long total = 6 * n * nframes;
-  const long long groups = (total + JPEG_BLOCKS_PER_WG - 1) / JPEG_BLOCKS_PER_WG;
-  if (groups > 0x7FFFFFFFLL) return -2;
-  JpegIdctArgs a;
-  a.record_bytes = record_bytes;
-  a.total_blocks = total;
-  a.mw = mw;
-  a.mh = mh;
-  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)groups), dim3(256), 0, stream,
-                     (const uint8_t*)rec, (uint8_t*)surf, a);
-  return (int)hipGetLastError();
+  return jpeg_idct_launch(rec, rec_len, record_bytes, nframes, mw, mh, surf, surf_len, 0, stream);
+}
+
+// The same for 4:2:0 / 4:2:2 / 4:4:4 records (sampling 0 / 1 / 2): records of
+// >= 384 + 128 B mw mh bytes, frames of 64 B mw mh bytes, B = 6 / 4 / 3.
+int rnb_jpeg_idct_s(const void* rec, long long rec_len, long long record_bytes, int nframes,
+                    int mw, int mh, void* surf, long long surf_len, int sampling,
+                    hipStream_t stream) {
+  return jpeg_idct_launch(rec, rec_len, record_bytes, nframes, mw, mh, surf, surf_len, sampling,
+                          stream);
 }
 
 }  // extern "C"

@@ -258,7 +258,45 @@ struct Yuv420ClipArgs {
 
 // JFIF: full-range JFIF YCbCr (what JPEG frames hold) instead of the video-range
 // BT.601 matrix; the chroma planes of an odd-sized frame then round up.
-template <bool FROM_ARRAY, bool JFIF>
+// HS, VS: the luma sampling factors per axis, 2x2 (4:2:0), 2x1 (4:2:2) or 1x1
+// (4:4:4); the chroma planes are 1x1. Chroma sample j sits at luma coordinate
+// HS j + (HS - 1) / 2 (centre siting), so along an axis with factor 1 the
+// chroma coordinate is the luma coordinate and the plane has the luma size.
+template <int S>
+static __device__ __forceinline__ int chroma_dim(int n, bool round_up) {
+  return S == 2 ? (round_up ? (n + 1) / 2 : n / 2) : n;
+}
+
+// nv12_sample with the taps split from the fetch: with 1x1 factors the three
+// planes share indices and weights, which are then computed once per pixel
+struct BilinearTaps {
+  int x0, x1, y0, y1;
+  float fx, fy;
+};
+
+static __device__ __forceinline__ BilinearTaps bilinear_taps(int w, int h, float sx, float sy) {
+  BilinearTaps t;
+  sx = fminf(fmaxf(sx, 0.f), (float)(w - 1));
+  sy = fminf(fmaxf(sy, 0.f), (float)(h - 1));
+  t.x0 = (int)sx; t.y0 = (int)sy;
+  t.x1 = min(t.x0 + 1, w - 1); t.y1 = min(t.y0 + 1, h - 1);
+  t.fx = sx - (float)t.x0; t.fy = sy - (float)t.y0;
+  return t;
+}
+
+static __device__ __forceinline__ float bilinear_fetch(const uint8_t* __restrict__ plane,
+                                                       int stride, int comps,
+                                                       const BilinearTaps& t) {
+  const float p00 = plane[t.y0 * stride + t.x0 * comps];
+  const float p01 = plane[t.y0 * stride + t.x1 * comps];
+  const float p10 = plane[t.y1 * stride + t.x0 * comps];
+  const float p11 = plane[t.y1 * stride + t.x1 * comps];
+  const float top = p00 + (p01 - p00) * t.fx;
+  const float bot = p10 + (p11 - p10) * t.fx;
+  return top + (bot - top) * t.fy;
+}
+
+template <bool FROM_ARRAY, bool JFIF, int HS = 2, int VS = 2>
 __global__ __launch_bounds__(256) void yuv420_clip_kernel(const uint8_t* __restrict__ buf,
                                                           const long long* __restrict__ offs,
                                                           void* __restrict__ out,
@@ -276,12 +314,20 @@ __global__ __launch_bounds__(256) void yuv420_clip_kernel(const uint8_t* __restr
   // the arithmetic below is nv12_clip_kernel's, expression for expression
   const float sx = a.g.crop_x + ((float)ox + 0.5f) * (a.g.crop_w / (float)a.g.out_w) - 0.5f;
   const float sy = a.g.crop_y + ((float)oy + 0.5f) * (a.g.crop_h / (float)a.g.out_h) - 0.5f;
-  const float yv = nv12_sample(fr + a.y_off, a.g.src_w, a.g.src_h, a.y_stride, 1, 0, sx, sy);
-  const float cx = (sx + 0.5f) * 0.5f - 0.5f, cy = (sy + 0.5f) * 0.5f - 0.5f;
-  const int cw = JFIF ? (a.g.src_w + 1) / 2 : a.g.src_w / 2;
-  const int ch = JFIF ? (a.g.src_h + 1) / 2 : a.g.src_h / 2;
-  const float u = nv12_sample(fr + a.u_off, cw, ch, a.u_stride, a.c_step, 0, cx, cy) - 128.f;
-  const float v = nv12_sample(fr + a.v_off, cw, ch, a.v_stride, a.c_step, 0, cx, cy) - 128.f;
+  float yv, u, v;
+  if constexpr (HS == 1 && VS == 1) {
+    const BilinearTaps t = bilinear_taps(a.g.src_w, a.g.src_h, sx, sy);
+    yv = bilinear_fetch(fr + a.y_off, a.y_stride, 1, t);
+    u = bilinear_fetch(fr + a.u_off, a.u_stride, a.c_step, t) - 128.f;
+    v = bilinear_fetch(fr + a.v_off, a.v_stride, a.c_step, t) - 128.f;
+  } else {
+    yv = nv12_sample(fr + a.y_off, a.g.src_w, a.g.src_h, a.y_stride, 1, 0, sx, sy);
+    const float cx = HS == 2 ? (sx + 0.5f) * 0.5f - 0.5f : sx;
+    const float cy = VS == 2 ? (sy + 0.5f) * 0.5f - 0.5f : sy;
+    const int cw = chroma_dim<HS>(a.g.src_w, JFIF), ch = chroma_dim<VS>(a.g.src_h, JFIF);
+    u = nv12_sample(fr + a.u_off, cw, ch, a.u_stride, a.c_step, 0, cx, cy) - 128.f;
+    v = nv12_sample(fr + a.v_off, cw, ch, a.v_stride, a.c_step, 0, cx, cy) - 128.f;
+  }
   const float yy = JFIF ? yv : 1.164f * (yv - 16.f);
   float r = yy + (JFIF ? 1.402f : 1.596f) * v;
   float g = yy - (JFIF ? 0.344136f : 0.392f) * u - (JFIF ? 0.714136f : 0.813f) * v;
@@ -403,7 +449,7 @@ static __device__ __forceinline__ void aa_plane(const uint8_t* __restrict__ plan
   for (int k = 0; k < AA_PX; ++k) res[k] = wsum[k] > 0.f ? acc[k] / wsum[k] : 0.f;
 }
 
-template <bool FROM_ARRAY, bool JFIF>
+template <bool FROM_ARRAY, bool JFIF, int HS = 2, int VS = 2>
 __global__ __launch_bounds__(256) void yuv420_clip_aa_kernel(const uint8_t* __restrict__ buf,
                                                              const long long* __restrict__ offs,
                                                              void* __restrict__ out,
@@ -426,14 +472,16 @@ __global__ __launch_bounds__(256) void yuv420_clip_aa_kernel(const uint8_t* __re
     cx[k] = p - r * tw;
     oy[k] = r < th ? oy0 + r : -1;
   }
-  const int cw = JFIF ? (a.g.src_w + 1) / 2 : a.g.src_w / 2;
-  const int ch = JFIF ? (a.g.src_h + 1) / 2 : a.g.src_h / 2;
+  const int cw = chroma_dim<HS>(a.g.src_w, JFIF), ch = chroma_dim<VS>(a.g.src_h, JFIF);
   float yv[AA_PX], u[AA_PX], v[AA_PX];
   aa_plane(fr + a.y_off, a.g.src_w, a.g.src_h, a.y_stride, 1, a.g.crop_x, a.g.crop_y,
            a.g.crop_w, a.g.crop_h, a.g.out_w, a.g.out_h, x0, tw, oy0, th, cx, oy, rows_lds, yv);
-  // chroma sample j sits at luma 2 j + 0.5: the chroma box is the luma box / 2
-  const float hx = a.g.crop_x * 0.5f, hy = a.g.crop_y * 0.5f;
-  const float hw = a.g.crop_w * 0.5f, hh = a.g.crop_h * 0.5f;
+  // chroma sample j sits at luma 2 j + 0.5 along a subsampled axis: the chroma
+  // box is the luma box / (HS, VS)
+  const float hx = HS == 2 ? a.g.crop_x * 0.5f : a.g.crop_x;
+  const float hy = VS == 2 ? a.g.crop_y * 0.5f : a.g.crop_y;
+  const float hw = HS == 2 ? a.g.crop_w * 0.5f : a.g.crop_w;
+  const float hh = VS == 2 ? a.g.crop_h * 0.5f : a.g.crop_h;
   aa_plane(fr + a.u_off, cw, ch, a.u_stride, a.c_step, hx, hy, hw, hh, a.g.out_w, a.g.out_h,
            x0, tw, oy0, th, cx, oy, rows_lds, u);
   aa_plane(fr + a.v_off, cw, ch, a.v_stride, a.c_step, hx, hy, hw, hh, a.g.out_w, a.g.out_h,
@@ -747,6 +795,27 @@ __global__ __launch_bounds__(256) void head_pool_f32_kernel(const float* __restr
   *(float4*)(pooled + (size_t)n * C + c) = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
 }
 
+// yuv420_to_clip_launch's choice among the instantiations of the two clip kernels
+template <bool FROM_ARRAY, bool JFIF, int HS, int VS>
+static void yuv_clip_run(bool aa, dim3 grid, hipStream_t stream, const uint8_t* buf,
+                         const long long* table, void* out, const Yuv420ClipArgs& a) {
+  if (aa)
+    hipLaunchKernelGGL((yuv420_clip_aa_kernel<FROM_ARRAY, JFIF, HS, VS>), grid, dim3(256), 0,
+                       stream, buf, table, out, a);
+  else
+    hipLaunchKernelGGL((yuv420_clip_kernel<FROM_ARRAY, JFIF, HS, VS>), grid, dim3(256), 0,
+                       stream, buf, table, out, a);
+}
+
+template <bool FROM_ARRAY, bool JFIF>
+static void yuv_clip_run_sampling(int sampling, bool aa, dim3 grid, hipStream_t stream,
+                                  const uint8_t* buf, const long long* table, void* out,
+                                  const Yuv420ClipArgs& a) {
+  if (sampling == 0) yuv_clip_run<FROM_ARRAY, JFIF, 2, 2>(aa, grid, stream, buf, table, out, a);
+  else if (sampling == 1) yuv_clip_run<FROM_ARRAY, JFIF, 2, 1>(aa, grid, stream, buf, table, out, a);
+  else yuv_clip_run<FROM_ARRAY, JFIF, 1, 1>(aa, grid, stream, buf, table, out, a);
+}
+
 extern "C" {
 
 int rnb_clipgen_u8(void* out, const int* vids, const int* starts, int nclips, int F, int H,
@@ -840,22 +909,28 @@ int rnb_nv12_to_clip(const void* nv12, void* out, long long frames, int src_w, i
 // chroma planes of ceil(w / 2) x ceil(h / 2)).
 // filter: 0 the two-tap bilinear kernel, 1 the antialiased triangle filter
 // (yuv420_clip_aa_kernel), which also needs the crop box inside the frame: -5.
+// sampling: 0 4:2:0 (luma factors 2x2), 1 4:2:2 (2x1), 2 4:4:4 (1x1); the chroma
+// planes are ceil(w / Hs) x ceil(h / Vs) under JFIF and w / Hs x h / Vs under
+// BT.601, which needs an even size only along an axis with factor 2.
 static int yuv420_to_clip_launch(const void* buf, long long buf_len, const long long* offs,
                                  const void* offs_dev, int nclips, int F, int src_w, int src_h,
                                  long long frame_stride, const long long* plane_off,
                                  const int* plane_stride, int c_step, void* out, int out_w,
                                  int out_h, const float* crop, const float* mean,
                                  const float* stdv, int bf16, int matrix, int filter,
-                                 hipStream_t stream) {
+                                 int sampling, hipStream_t stream) {
   if (nclips <= 0) return 0;
   if (matrix != 0 && matrix != 1) return -2;
+  if (sampling < 0 || sampling > 2) return -2;
+  const int hs = sampling == 2 ? 1 : 2, vs = sampling == 0 ? 2 : 1;
   if (F <= 0 || src_w < 1 || src_h < 1 || out_w <= 0 || out_h <= 0) return -2;
-  if (matrix == 0 && (src_w % 2 || src_h % 2)) return -2;
+  if (matrix == 0 && ((hs == 2 && src_w % 2) || (vs == 2 && src_h % 2))) return -2;
   if (((uintptr_t)out & 15u) != 0 || (c_step != 1 && c_step != 2)) return -2;
   if (nclips > YUV420_MAX_CLIPS && !offs_dev) return -3;
   // every byte nv12_sample can touch lies inside its frame (int indexing there)
   if (frame_stride <= 0 || frame_stride > 0x7FFFFFFFLL) return -4;
-  const int cw = (src_w + matrix) / 2, ch = (src_h + matrix) / 2;
+  const int cw = hs == 2 ? (src_w + matrix) / 2 : src_w;
+  const int ch = vs == 2 ? (src_h + matrix) / 2 : src_h;
   for (int p = 0; p < 3; ++p) {
     if (plane_off[p] < 0 || plane_stride[p] <= 0) return -4;
     const long long row = p == 0 ? src_w : (long long)(cw - 1) * c_step + 1;
@@ -883,19 +958,18 @@ static int yuv420_to_clip_launch(const void* buf, long long buf_len, const long 
   const bool in_args = nclips <= YUV420_MAX_CLIPS;
   for (int c = 0; c < YUV420_MAX_CLIPS; ++c) a.offs[c] = in_args && c < nclips ? offs[c] : 0;
   const long long* table = in_args ? (const long long*)nullptr : (const long long*)offs_dev;
-  if (filter) {
-    const long long tiles = (long long)((out_w + AA_TW - 1) / AA_TW) * ((out_h + AA_TH - 1) / AA_TH);
-    if (tiles > 0x7FFFFFFFLL) return -2;
-    const dim3 grid((unsigned)tiles, (unsigned)F, (unsigned)nclips);
-    auto kernel = in_args ? (matrix ? yuv420_clip_aa_kernel<false, true> : yuv420_clip_aa_kernel<false, false>)
-                          : (matrix ? yuv420_clip_aa_kernel<true, true> : yuv420_clip_aa_kernel<true, false>);
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (const uint8_t*)buf, table, out, a);
-    return (int)hipGetLastError();
+  const long long tiles = (long long)((out_w + AA_TW - 1) / AA_TW) * ((out_h + AA_TH - 1) / AA_TH);
+  if (filter && tiles > 0x7FFFFFFFLL) return -2;
+  const dim3 grid((unsigned)(filter ? tiles : (ohw + 255) / 256), (unsigned)F, (unsigned)nclips);
+  const uint8_t* src = (const uint8_t*)buf;
+  const bool aa = filter != 0;
+  if (in_args) {
+    if (matrix) yuv_clip_run_sampling<false, true>(sampling, aa, grid, stream, src, table, out, a);
+    else yuv_clip_run_sampling<false, false>(sampling, aa, grid, stream, src, table, out, a);
+  } else {
+    if (matrix) yuv_clip_run_sampling<true, true>(sampling, aa, grid, stream, src, table, out, a);
+    else yuv_clip_run_sampling<true, false>(sampling, aa, grid, stream, src, table, out, a);
   }
-  const dim3 grid((unsigned)((ohw + 255) / 256), (unsigned)F, (unsigned)nclips);
-  auto kernel = in_args ? (matrix ? yuv420_clip_kernel<false, true> : yuv420_clip_kernel<false, false>)
-                        : (matrix ? yuv420_clip_kernel<true, true> : yuv420_clip_kernel<true, false>);
-  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (const uint8_t*)buf, table, out, a);
   return (int)hipGetLastError();
 }
 
@@ -907,7 +981,7 @@ int rnb_yuv420_to_clip(const void* buf, long long buf_len, const long long* offs
                        int matrix, hipStream_t stream) {
   return yuv420_to_clip_launch(buf, buf_len, offs, offs_dev, nclips, F, src_w, src_h,
                                frame_stride, plane_off, plane_stride, c_step, out, out_w, out_h,
-                               crop, mean, stdv, bf16, matrix, 0, stream);
+                               crop, mean, stdv, bf16, matrix, 0, 0, stream);
 }
 
 // The same arguments and checks; the antialiased triangle filter. -5: the crop
@@ -920,7 +994,22 @@ int rnb_yuv420_to_clip_aa(const void* buf, long long buf_len, const long long* o
                           int matrix, hipStream_t stream) {
   return yuv420_to_clip_launch(buf, buf_len, offs, offs_dev, nclips, F, src_w, src_h,
                                frame_stride, plane_off, plane_stride, c_step, out, out_w, out_h,
-                               crop, mean, stdv, bf16, matrix, 1, stream);
+                               crop, mean, stdv, bf16, matrix, 1, 0, stream);
+}
+
+// rnb_yuv420_to_clip / rnb_yuv420_to_clip_aa for any of the three chroma
+// layouts. filter: 0 bilinear, 1 antialias; sampling: 0 4:2:0, 1 4:2:2, 2 4:4:4
+// (anything else: -2). With sampling 0 it is the entry points above.
+int rnb_yuv_to_clip(const void* buf, long long buf_len, const long long* offs,
+                    const void* offs_dev, int nclips, int F, int src_w, int src_h,
+                    long long frame_stride, const long long* plane_off, const int* plane_stride,
+                    int c_step, void* out, int out_w, int out_h, const float* crop,
+                    const float* mean, const float* stdv, int bf16, int matrix, int filter,
+                    int sampling, hipStream_t stream) {
+  if (filter != 0 && filter != 1) return -2;
+  return yuv420_to_clip_launch(buf, buf_len, offs, offs_dev, nclips, F, src_w, src_h,
+                               frame_stride, plane_off, plane_stride, c_step, out, out_w, out_h,
+                               crop, mean, stdv, bf16, matrix, filter, sampling, stream);
 }
 
 int rnb_preprocess(const void* in, void* out, long long npix, const float* mean,

@@ -258,8 +258,10 @@ class Y4mDecoder(_StagedFileDecoder):
     """Raw YUV4MPEG2 (``.y4m``) videos at their source resolution.
 
     ``probe`` memory-maps the file and parses its header (``utils/y4m.py``):
-    8-bit 4:2:0 only, i.e. no ``C`` field or ``C420`` / ``C420jpeg`` /
-    ``C420mpeg2`` / ``C420paldv``. These differ in chroma siting; all are
+    8-bit 4:2:0 (no ``C`` field or ``C420`` / ``C420jpeg`` / ``C420mpeg2`` /
+    ``C420paldv``), 4:2:2 (``C422``) and 4:4:4 (``C444``); the header's sampling
+    sizes the spans and goes down to the clip kernel, so one decoder serves
+    files of all three. The 4:2:0 tags differ in chroma siting; all are
     sampled with the kernel's centred siting (chroma sample centres at 2x + 0.5
     luma pixels, exact for ``C420jpeg``; the co-sited variants are read half a
     luma pixel off horizontally, as NVVL's scaler does not distinguish them
@@ -282,6 +284,8 @@ class Y4mDecoder(_StagedFileDecoder):
     ``"antialias"``, the triangle filter widened by the downscale factor that
     PIL's ``resize(BILINEAR)`` and torchvision's ``Resize(antialias=True)``
     apply (``yuv420_to_clip(filter=)``); both boxes lie inside the frame."""
+
+    _PLANES = {"420": vops.i420_planes, "422": vops.i422_planes, "444": vops.i444_planes}
 
     def probe(self, path):
         vid = self._ids.get(path)
@@ -332,7 +336,7 @@ class Y4mDecoder(_StagedFileDecoder):
             if s < 0 or s + self.F > hdr.num_frames:
                 raise ValueError("%s: clip at frame %d (+%d) is outside the %d frames"
                                  % (path, s, self.F, hdr.num_frames))
-        planes = vops.i420_planes(hdr.width, hdr.height, len(y4m.FRAME_MARKER))
+        planes = self._PLANES[hdr.sampling](hdr.width, hdr.height, len(y4m.FRAME_MARKER))
         offsets = [i * span for i in range(n)]
         cuda = self.device.type == "cuda"
         if cuda:
@@ -359,7 +363,7 @@ class Y4mDecoder(_StagedFileDecoder):
             vops.yuv420_to_clip(buf[:n * span], offsets, self.F, hdr.width, hdr.height,
                                 hdr.frame_stride, planes, self.W, self.H,
                                 crop=self._crop_box(hdr), dtype=self.dtype, out=out,
-                                filter=self.filter)
+                                filter=self.filter, sampling=hdr.sampling)
         finally:
             if cuda:     # also behind the uploads of a request that raised
                 entry.event.record(torch.cuda.current_stream(self.device))
@@ -373,10 +377,12 @@ class MjpegDecoder(_StagedFileDecoder):
     the serial entropy decode on the host, the per-sample arithmetic on the GPU.
 
     ``probe`` memory-maps the file and indexes it (``utils/mjpeg.py``,
-    ``rnb_mjpeg_index``): baseline sequential Huffman JPEG, 8-bit, 4:2:0, one
-    scan, all frames of one size; anything else raises ``ValueError`` naming
-    file, frame and field. AVI / MOV containers, progressive JPEG, 4:2:2, 4:4:4
-    and grayscale are not read.
+    ``rnb_mjpeg_index_s``): baseline sequential Huffman JPEG, 8-bit, 4:2:0,
+    4:2:2 or 4:4:4, one scan, all frames of one size and sampling; anything else
+    raises ``ValueError`` naming file, frame and field. AVI / MOV containers,
+    progressive JPEG, 4:4:0, 4:1:1 and grayscale are not read. The index's
+    sampling sizes every buffer of a request and goes down to each kernel, so
+    one decoder serves files of all three.
 
     ``decode`` entropy-decodes each clip's F frames (``librnb_jpeg.so``, on
     ``threads`` host threads with the GIL released) straight into a pinned
@@ -476,15 +482,15 @@ class MjpegDecoder(_StagedFileDecoder):
             self._surface = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._surface
 
-    def _to_clips(self, records, n, W, H, mw, mh, crop, out):
-        fbytes = 384 * mw * mh
+    def _to_clips(self, records, n, W, H, mw, mh, crop, out, sampling="420"):
+        fbytes = vops.jpeg_frame_bytes(mw, mh, sampling)[1]
         surf = vops.jpeg_idct(records, n * self.F, mw, mh,
                               out=self._planes(max(n, 15) * self.F, fbytes)
-                              if self.device.type == "cuda" else None)
+                              if self.device.type == "cuda" else None, sampling=sampling)
         return vops.yuv420_to_clip(surf, [i * self.F * fbytes for i in range(n)], self.F, W, H,
-                                   fbytes, vops.jpeg_surface_planes(mw, mh), self.W, self.H,
-                                   crop=crop, dtype=self.dtype, out=out, matrix="jfif",
-                                   filter=self.filter)
+                                   fbytes, vops.jpeg_surface_planes(mw, mh, sampling), self.W,
+                                   self.H, crop=crop, dtype=self.dtype, out=out, matrix="jfif",
+                                   filter=self.filter, sampling=sampling)
 
     def warmup(self, n: int) -> None:
         """Run both kernels on a zeroed record buffer (no file needed)."""
@@ -530,13 +536,13 @@ class MjpegDecoder(_StagedFileDecoder):
             for i, s in enumerate(starts):
                 mjpeg.entropy_decode(data, idx.offsets[s:s + self.F], idx.lengths[s:s + self.F],
                                      host[i * span:(i + 1) * span], idx.record_bytes,
-                                     self.threads, name=path)
+                                     self.threads, name=path, sampling=idx.sampling)
                 if cuda:     # this clip uploads while the next one decodes
                     buf[i * span:(i + 1) * span].copy_(
                         entry.pinned[i * span:(i + 1) * span], non_blocking=True)
             out = self._out(n, out)
             self._to_clips(buf[:n * span], n, idx.width, idx.height, idx.mw, idx.mh,
-                           self._crop_box(idx), out)
+                           self._crop_box(idx), out, idx.sampling)
         finally:
             if cuda:     # also behind the uploads of a request that raised
                 entry.event.record(torch.cuda.current_stream(self.device))
@@ -607,7 +613,7 @@ class MjpegDecoder(_StagedFileDecoder):
             for i, s in enumerate(starts):
                 got, rel = mjpeg.pack_scans(data, idx.offsets[s:s + F], idx.lengths[s:s + F],
                                             host[pos:stat_at], idx.width, idx.height,
-                                            name=path, frame0=s)
+                                            name=path, frame0=s, sampling=idx.sampling)
                 offs[i * F:(i + 1) * F] = rel[:F] + pos
                 if cuda:     # this clip uploads while the next one packs
                     buf[pos:pos + got].copy_(entry.pinned[pos:pos + got], non_blocking=True)
@@ -624,17 +630,18 @@ class MjpegDecoder(_StagedFileDecoder):
                     offs_dev=buf[:8 * (nfr + 1)].view(torch.int64),
                     subseq_bytes=self.subseq_bytes,
                     rounds=self._device_buffer("_rounds", cap, torch.int32)
-                    if self.subseq_bytes else None)
+                    if self.subseq_bytes else None, sampling=idx.sampling)
                 entry.pinned[stat_at:stat_at + 4 * nfr].view(torch.int32).copy_(
                     status, non_blocking=True)
                 entry.pending = (path, frames, stat_at)
             else:
                 records, status = vops.jpeg_huff(buf[:pos], offs, nfr, idx.mw, idx.mh,
-                                                 subseq_bytes=self.subseq_bytes)
+                                                 subseq_bytes=self.subseq_bytes,
+                                                 sampling=idx.sampling)
                 mjpeg.raise_for_status(status.numpy(), path, frames)
             out = self._out(n, out)
             self._to_clips(records, n, idx.width, idx.height, idx.mw, idx.mh,
-                           self._crop_box(idx), out)
+                           self._crop_box(idx), out, idx.sampling)
         finally:
             if cuda:     # also behind the uploads of a request that raised
                 entry.event.record(torch.cuda.current_stream(self.device))

@@ -220,6 +220,10 @@ class Kernels:
         lib.rnb_yuv420_to_clip.restype = ctypes.c_int
         lib.rnb_yuv420_to_clip_aa.argtypes = lib.rnb_yuv420_to_clip.argtypes
         lib.rnb_yuv420_to_clip_aa.restype = ctypes.c_int
+        # the same with trailing (matrix, filter, sampling) for 4:2:2 / 4:4:4 frames
+        lib.rnb_yuv_to_clip.argtypes = (lib.rnb_yuv420_to_clip.argtypes[:-1]
+                                        + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p])
+        lib.rnb_yuv_to_clip.restype = ctypes.c_int
         lib.rnb_jpeg_idct.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
@@ -235,6 +239,11 @@ class Kernels:
                                              ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_void_p, ctypes.c_void_p]
         lib.rnb_jpeg_huff_subseq.restype = ctypes.c_int
+        # the *_s forms: a sampling word (0 4:2:0, 1 4:2:2, 2 4:4:4) in front of the stream
+        for base in ("rnb_jpeg_idct", "rnb_jpeg_huff", "rnb_jpeg_huff_subseq"):
+            fn = getattr(lib, base + "_s")
+            fn.argtypes = getattr(lib, base).argtypes[:-1] + [ctypes.c_int, ctypes.c_void_p]
+            fn.restype = ctypes.c_int
         lib.rnb_preprocess.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
                                        ctypes.POINTER(ctypes.c_float),
                                        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
@@ -816,13 +825,16 @@ class Kernels:
 
     def yuv420_to_clip(self, buf_ptr, buf_len, offsets, offsets_dev_ptr, F, src_w, src_h,
                        frame_stride, plane_offsets, plane_strides, c_step, out_ptr, out_w,
-                       out_h, crop, mean, std, bf16, stream, matrix=0, antialias=False):
+                       out_h, crop, mean, std, bf16, stream, matrix=0, antialias=False,
+                       sampling=0):
         """``offsets``: the per-clip byte offsets on the host (checked against
         ``buf_len`` by the launcher); ``offsets_dev_ptr``: the same table in
         device memory, needed for more than 32 clips (else None). ``matrix``:
         0 BT.601 video range, 1 full-range JFIF. ``antialias``: the
         ``rnb_yuv420_to_clip_aa`` entry (triangle filter widened by the
-        downscale factor; the crop box must lie inside the frame)."""
+        downscale factor; the crop box must lie inside the frame).
+        ``sampling``: 0 4:2:0 (the two entry points above), 1 4:2:2, 2 4:4:4
+        (``rnb_yuv_to_clip``)."""
         n = len(offsets)
         offs = (ctypes.c_longlong * max(1, n))(*offsets)
         po = (ctypes.c_longlong * 3)(*plane_offsets)
@@ -830,6 +842,13 @@ class Kernels:
         c = (ctypes.c_float * 4)(*crop)
         m = (ctypes.c_float * 3)(*mean)
         s = (ctypes.c_float * 3)(*std)
+        if sampling:
+            _check(self.lib.rnb_yuv_to_clip(buf_ptr, buf_len, offs, offsets_dev_ptr, n, F, src_w,
+                                            src_h, frame_stride, po, ps, c_step, out_ptr, out_w,
+                                            out_h, c, m, s, 1 if bf16 else 0, int(matrix),
+                                            1 if antialias else 0, int(sampling), stream),
+                   "yuv_to_clip")
+            return
         fn = self.lib.rnb_yuv420_to_clip_aa if antialias else self.lib.rnb_yuv420_to_clip
         _check(fn(buf_ptr, buf_len, offs, offsets_dev_ptr, n, F, src_w, src_h, frame_stride,
                   po, ps, c_step, out_ptr, out_w, out_h, c, m, s, 1 if bf16 else 0,
@@ -837,29 +856,42 @@ class Kernels:
                "yuv420_to_clip_aa" if antialias else "yuv420_to_clip")
 
     def jpeg_idct(self, rec_ptr, rec_len, record_bytes, nframes, mw, mh, surf_ptr, surf_len,
-                  stream):
+                  stream, sampling=0):
         """Frame records -> padded I420 surface; the launcher checks both
-        lengths against (mw, mh, nframes) before it launches."""
+        lengths against (mw, mh, nframes) before it launches. ``sampling``: 0
+        4:2:0 (``rnb_jpeg_idct``), 1 4:2:2, 2 4:4:4 (``rnb_jpeg_idct_s``)."""
+        if sampling:
+            _check(self.lib.rnb_jpeg_idct_s(rec_ptr, rec_len, record_bytes, nframes, mw, mh,
+                                            surf_ptr, surf_len, int(sampling), stream),
+                   "jpeg_idct")
+            return
         _check(self.lib.rnb_jpeg_idct(rec_ptr, rec_len, record_bytes, nframes, mw, mh,
                                       surf_ptr, surf_len, stream), "jpeg_idct")
 
     def jpeg_huff(self, scans_ptr, scans_len, offs_host, offs_dev_ptr, nframes, mw, mh,
-                  rec_ptr, rec_len, record_bytes, status_ptr, stream):
+                  rec_ptr, rec_len, record_bytes, status_ptr, stream, sampling=0):
         """Scan records -> frame records + per-frame status. ``offs_host``:
         contiguous int64 numpy array of ``nframes + 1`` offsets, which the
         launcher checks against ``scans_len`` before it launches;
-        ``offs_dev_ptr``: the same table on the device."""
+        ``offs_dev_ptr``: the same table on the device. ``sampling`` as for
+        ``jpeg_idct`` (non-zero: ``rnb_jpeg_huff_s``)."""
         if offs_host.dtype.name != "int64" or not offs_host.flags.c_contiguous \
                 or offs_host.size < nframes + 1:
             raise ValueError("jpeg_huff: scan_offs must be %d contiguous int64 offsets"
                              % (nframes + 1))
+        if sampling:
+            _check(self.lib.rnb_jpeg_huff_s(scans_ptr, scans_len, offs_host.ctypes.data,
+                                            offs_dev_ptr, nframes, mw, mh, rec_ptr, rec_len,
+                                            record_bytes, status_ptr, int(sampling), stream),
+                   "jpeg_huff")
+            return
         _check(self.lib.rnb_jpeg_huff(scans_ptr, scans_len, offs_host.ctypes.data, offs_dev_ptr,
                                       nframes, mw, mh, rec_ptr, rec_len, record_bytes,
                                       status_ptr, stream), "jpeg_huff")
 
     def jpeg_huff_subseq(self, scans_ptr, scans_len, offs_host, offs_dev_ptr, nframes, mw, mh,
                          rec_ptr, rec_len, record_bytes, status_ptr, subseq_bytes, rounds_ptr,
-                         stream):
+                         stream, sampling=0):
         """As ``jpeg_huff`` through ``jpeg_huff_subseq_kernel``: one-interval
         frames by synchronised subsequences of ``subseq_bytes`` scan bytes;
         ``rounds_ptr``: ``nframes`` int32 on the device. The launcher also
@@ -868,6 +900,13 @@ class Kernels:
                 or offs_host.size < nframes + 1:
             raise ValueError("jpeg_huff: scan_offs must be %d contiguous int64 offsets"
                              % (nframes + 1))
+        if sampling:
+            _check(self.lib.rnb_jpeg_huff_subseq_s(scans_ptr, scans_len, offs_host.ctypes.data,
+                                                   offs_dev_ptr, nframes, mw, mh, rec_ptr,
+                                                   rec_len, record_bytes, status_ptr,
+                                                   int(subseq_bytes), rounds_ptr, int(sampling),
+                                                   stream), "jpeg_huff_subseq")
+            return
         _check(self.lib.rnb_jpeg_huff_subseq(scans_ptr, scans_len, offs_host.ctypes.data,
                                              offs_dev_ptr, nframes, mw, mh, rec_ptr, rec_len,
                                              record_bytes, status_ptr, int(subseq_bytes),
@@ -922,12 +961,23 @@ class Jpeg:
                                                           ctypes.c_int, vp, ll, ll, vp,
                                                           ctypes.c_int, vp]
         lib.rnb_jpeg_decode_scans_subseq_host.restype = ctypes.c_int
+        # the *_s forms carry the sampling (0 4:2:0, 1 4:2:2, 2 4:4:4) as a last argument;
+        # rnb_mjpeg_index_s reports it in a fifth info word
+        lib.rnb_mjpeg_index_s.argtypes = lib.rnb_mjpeg_index.argtypes
+        lib.rnb_mjpeg_index_s.restype = ll
+        for base in ("rnb_jpeg_decode_frames", "rnb_jpeg_pack_scans",
+                     "rnb_jpeg_decode_scans_host", "rnb_jpeg_decode_scans_subseq_host"):
+            fn = getattr(lib, base + "_s")
+            fn.argtypes = getattr(lib, base).argtypes + [ctypes.c_int]
+            fn.restype = getattr(lib, base).restype
 
-    def pack_scans(self, buf, offsets, lengths, out, width=0, height=0):
+    def pack_scans(self, buf, offsets, lengths, out, width=0, height=0, sampling=0):
         """Pack the scans of the frames at ``offsets`` / ``lengths`` of ``buf``
         into scan records in the flat uint8 array ``out`` (16-byte aligned).
         Returns (bytes written, int64 offsets [n + 1]) or, on a refusal,
-        (negative code, index of the frame it is in)."""
+        (negative code, index of the frame it is in). ``sampling``: the
+        stream's (0 4:2:0, 1 4:2:2, 2 4:4:4); non-zero goes through
+        ``rnb_jpeg_pack_scans_s``."""
         import numpy as np
         offs = np.ascontiguousarray(offsets, dtype=np.int64)
         lens = np.ascontiguousarray(lengths, dtype=np.int64)
@@ -937,21 +987,28 @@ class Jpeg:
             raise ValueError("jpeg pack_scans: table / output arrays do not fit")
         scan_offs = np.zeros(n + 1, dtype=np.int64)
         info = (ctypes.c_int * 3)()
-        rc = int(self.lib.rnb_jpeg_pack_scans(buf.ctypes.data, buf.size, offs.ctypes.data,
-                                              lens.ctypes.data, n, out.ctypes.data, out.size,
-                                              scan_offs.ctypes.data, int(width), int(height),
-                                              info))
+        if sampling:
+            rc = int(self.lib.rnb_jpeg_pack_scans_s(buf.ctypes.data, buf.size, offs.ctypes.data,
+                                                    lens.ctypes.data, n, out.ctypes.data,
+                                                    out.size, scan_offs.ctypes.data, int(width),
+                                                    int(height), info, int(sampling)))
+        else:
+            rc = int(self.lib.rnb_jpeg_pack_scans(buf.ctypes.data, buf.size, offs.ctypes.data,
+                                                  lens.ctypes.data, n, out.ctypes.data, out.size,
+                                                  scan_offs.ctypes.data, int(width), int(height),
+                                                  info))
         if rc < 0:
             return rc, int(info[2])
         return rc, scan_offs
 
     def decode_scans_host(self, scans, scan_offs, nframes, mw, mh, out, record_bytes, status,
-                          subseq_bytes=0, rounds=None):
+                          subseq_bytes=0, rounds=None, sampling=0):
         """The interval decoder on the CPU (what ``jpeg_huff_kernel`` computes):
         returns 0 or the negative buffer-level refusal; ``status`` (int32
         [nframes]) receives each frame's code. ``subseq_bytes`` > 0: the
         emulation of ``jpeg_huff_subseq_kernel``; ``rounds`` (int32 [nframes])
-        then receives each frame's synchronisation rounds."""
+        then receives each frame's synchronisation rounds. ``sampling``
+        non-zero: the ``*_s`` entry points with that geometry."""
         import numpy as np
         offs = np.ascontiguousarray(scan_offs, dtype=np.int64)
         if offs.size < nframes + 1 or status.dtype != np.int32 or status.size < nframes \
@@ -962,13 +1019,17 @@ class Jpeg:
             if rounds is None or rounds.dtype != np.int32 or rounds.size < nframes \
                     or not rounds.flags.c_contiguous:
                 raise ValueError("jpeg decode_scans_host: rounds must be int32 [nframes]")
-            return int(self.lib.rnb_jpeg_decode_scans_subseq_host(
-                scans.ctypes.data, scans.size, offs.ctypes.data, int(nframes), int(mw), int(mh),
-                out.ctypes.data, out.size, int(record_bytes), status.ctypes.data,
-                int(subseq_bytes), rounds.ctypes.data))
-        return int(self.lib.rnb_jpeg_decode_scans_host(
-            scans.ctypes.data, scans.size, offs.ctypes.data, int(nframes), int(mw), int(mh),
-            out.ctypes.data, out.size, int(record_bytes), status.ctypes.data))
+            args = (scans.ctypes.data, scans.size, offs.ctypes.data, int(nframes), int(mw),
+                    int(mh), out.ctypes.data, out.size, int(record_bytes), status.ctypes.data,
+                    int(subseq_bytes), rounds.ctypes.data)
+            if sampling:
+                return int(self.lib.rnb_jpeg_decode_scans_subseq_host_s(*args, int(sampling)))
+            return int(self.lib.rnb_jpeg_decode_scans_subseq_host(*args))
+        args = (scans.ctypes.data, scans.size, offs.ctypes.data, int(nframes), int(mw), int(mh),
+                out.ctypes.data, out.size, int(record_bytes), status.ctypes.data)
+        if sampling:
+            return int(self.lib.rnb_jpeg_decode_scans_host_s(*args, int(sampling)))
+        return int(self.lib.rnb_jpeg_decode_scans_host(*args))
 
     def error_name(self, code: int) -> str:
         return self.lib.rnb_jpeg_error_name(int(code)).decode()
@@ -987,7 +1048,23 @@ class Jpeg:
             return self.error_name(n), int(info[2])
         return int(info[0]), int(info[1]), int(info[3]), offs, lens
 
-    def decode_frames_rc(self, buf, offsets, lengths, out, record_bytes, threads=1) -> int:
+    def index_s(self, buf):
+        """``index`` for 4:2:0, 4:2:2 and 4:4:4 streams (``rnb_mjpeg_index_s``):
+        (width, height, restart interval, offsets, lengths, sampling 0 / 1 / 2),
+        or (field, frame) on a refusal."""
+        import numpy as np
+        info = (ctypes.c_int * 5)()
+        n = self.lib.rnb_mjpeg_index_s(buf.ctypes.data, buf.size, None, None, 0, info)
+        if n >= 0:
+            offs, lens = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+            n = self.lib.rnb_mjpeg_index_s(buf.ctypes.data, buf.size, offs.ctypes.data,
+                                           lens.ctypes.data, n, info)
+        if n < 0:
+            return self.error_name(n), int(info[2])
+        return int(info[0]), int(info[1]), int(info[3]), offs, lens, int(info[4])
+
+    def decode_frames_rc(self, buf, offsets, lengths, out, record_bytes, threads=1,
+                         sampling=0) -> int:
         """The launcher's return code: 0 or a negative refusal (ctypes releases
         the GIL for the call). ``out``: flat uint8 array of >= n * record_bytes."""
         import numpy as np
@@ -997,13 +1074,18 @@ class Jpeg:
         if lens.size != n or out.size < n * record_bytes or not out.flags.c_contiguous \
                 or not buf.flags.c_contiguous:
             raise ValueError("jpeg decode_frames: table / output sizes do not fit")
+        if sampling:
+            return int(self.lib.rnb_jpeg_decode_frames_s(buf.ctypes.data, buf.size,
+                                                         offs.ctypes.data, lens.ctypes.data, n,
+                                                         out.ctypes.data, int(record_bytes),
+                                                         int(threads), int(sampling)))
         return int(self.lib.rnb_jpeg_decode_frames(buf.ctypes.data, buf.size, offs.ctypes.data,
                                                    lens.ctypes.data, n, out.ctypes.data,
                                                    int(record_bytes), int(threads)))
 
-    def decode_frames(self, buf, offsets, lengths, out, record_bytes, threads=1):
+    def decode_frames(self, buf, offsets, lengths, out, record_bytes, threads=1, sampling=0):
         """None, or the field name of the refusal."""
-        rc = self.decode_frames_rc(buf, offsets, lengths, out, record_bytes, threads)
+        rc = self.decode_frames_rc(buf, offsets, lengths, out, record_bytes, threads, sampling)
         return None if rc == 0 else self.error_name(rc)
 
 

@@ -203,16 +203,19 @@ def _antialias_torch(plane: torch.Tensor, out_w: int, out_h: int, box) -> torch.
 
 
 def _planes_to_clip(y_plane, u_plane, v_plane, shape, crop, dtype, mean, std, out,
-                    matrix="bt601", filter="bilinear"):
+                    matrix="bt601", filter="bilinear", factors=(2, 2)):
     """CPU mirror shared by ``nv12_to_clip`` and ``yuv420_to_clip``: float Y
     [frames, h, w] and U, V [frames, h/2, w/2] planes -> ``shape`` =
     [..., out_h, out_w, C] normalised frames. ``matrix``: ``"bt601"`` (video
     range) or ``"jfif"`` (full-range JFIF YCbCr). ``filter``: ``"bilinear"``
     (two taps) or ``"antialias"`` (``_antialias_torch``; chroma from the chroma
-    box = luma box / 2 on the chroma plane)."""
+    box = luma box / 2 on the chroma plane). ``factors``: the luma sampling
+    factors (Hs, Vs); along an axis with factor 1 the chroma plane has the luma
+    size and the chroma coordinate is the luma coordinate."""
     out_h, out_w = shape[-3], shape[-2]
+    hs, vs = factors
     if filter == "antialias":
-        cbox = tuple(c / 2.0 for c in crop)
+        cbox = tuple(c / 2.0 if f == 2 else c for c, f in zip(crop, (hs, vs, hs, vs)))
         yv = _antialias_torch(y_plane, out_w, out_h, crop)
         u = _antialias_torch(u_plane, out_w, out_h, cbox) - 128.0
         v = _antialias_torch(v_plane, out_w, out_h, cbox) - 128.0
@@ -222,7 +225,8 @@ def _planes_to_clip(y_plane, u_plane, v_plane, shape, crop, dtype, mean, std, ou
         sx = crop[0] + (ox + 0.5) * (crop[2] / out_w) - 0.5
         sy = crop[1] + (oy + 0.5) * (crop[3] / out_h) - 0.5
         yv = _bilinear_torch(y_plane, sx, sy)
-        cx, cy = (sx + 0.5) * 0.5 - 0.5, (sy + 0.5) * 0.5 - 0.5
+        cx = (sx + 0.5) * 0.5 - 0.5 if hs == 2 else sx
+        cy = (sy + 0.5) * 0.5 - 0.5 if vs == 2 else sy
         u = _bilinear_torch(u_plane, cx, cy) - 128.0
         v = _bilinear_torch(v_plane, cx, cy) - 128.0
     if matrix == "jfif":
@@ -242,8 +246,20 @@ def _planes_to_clip(y_plane, u_plane, v_plane, shape, crop, dtype, mean, std, ou
     return res
 
 
+SAMPLINGS = ("420", "422", "444")
+# luma sampling factors (Hs, Vs) of each; both chroma planes are 1x1
+SAMPLING_FACTORS = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}
+
+
+def sampling_factors(sampling: str, who: str = "sampling_factors") -> Tuple[int, int]:
+    """(Hs, Vs) of ``sampling``; ``ValueError`` naming the argument otherwise."""
+    if sampling not in SAMPLING_FACTORS:
+        raise ValueError("%s: sampling must be one of %s, got %r" % (who, SAMPLINGS, sampling))
+    return SAMPLING_FACTORS[sampling]
+
+
 class YuvPlanes(NamedTuple):
-    """Where a frame's 4:2:0 samples lie, in bytes from the frame's start:
+    """Where a frame's planar YUV samples lie, in bytes from the frame's start:
     offsets and row strides of the Y, U and V planes, and the distance between
     chroma samples (1: planar, 2: interleaved UV with ``v = u + 1``)."""
     y: int
@@ -262,6 +278,17 @@ def i420_planes(W: int, H: int, header: int = 0) -> YuvPlanes:
                      W, W // 2, W // 2, 1)
 
 
+def i422_planes(W: int, H: int, header: int = 0) -> YuvPlanes:
+    """Planar 4:2:2 (Y, then U, then V of W/2 x H) behind ``header`` bytes."""
+    return YuvPlanes(header, header + W * H, header + W * H + (W // 2) * H,
+                     W, W // 2, W // 2, 1)
+
+
+def i444_planes(W: int, H: int, header: int = 0) -> YuvPlanes:
+    """Planar 4:4:4 (Y, then U, then V, all W x H) behind ``header`` bytes."""
+    return YuvPlanes(header, header + W * H, header + 2 * W * H, W, W, W, 1)
+
+
 def nv12_planes(W: int, H: int, header: int = 0) -> YuvPlanes:
     """NV12 (Y, then interleaved UV rows of W bytes) behind ``header`` bytes."""
     return YuvPlanes(header, header + W * H, header + W * H + 1, W, W, W, 2)
@@ -271,7 +298,7 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
                    frame_stride: int, planes: YuvPlanes, out_w: int = 112, out_h: int = 112,
                    crop=None, dtype=torch.float32, mean=KINETICS_MEAN, std=KINETICS_STD,
                    out: Optional[torch.Tensor] = None, matrix: str = "bt601",
-                   filter: str = "bilinear") -> torch.Tensor:
+                   filter: str = "bilinear", sampling: str = "420") -> torch.Tensor:
     """4:2:0 frames inside a byte buffer -> normalised NDHWC clips
     [n, F, out_h, out_w, C] (fp32 C=4 / bf16 C=8), with ``nv12_to_clip``'s
     arithmetic. ``buf`` is a flat uint8 tensor (uploaded file spans); clip ``c``
@@ -291,7 +318,13 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
     per axis ``scale = size / n_out``, ``fs = max(scale, 1)``, weights
     ``max(0, 1 - |j - s_o| / fs)`` over the plane's own samples, renormalised
     (``yuv420_clip_aa_kernel``; for ``scale <= 1`` the same as bilinear). It
-    needs ``crop`` inside the frame and raises ``ValueError`` otherwise."""
+    needs ``crop`` inside the frame and raises ``ValueError`` otherwise.
+
+    ``sampling``: ``"420"`` (default), ``"422"`` or ``"444"``, luma factors
+    (Hs, Vs) = (2, 2), (2, 1), (1, 1). The chroma planes are ceil(w / Hs) x
+    ceil(h / Vs) (JFIF) or w / Hs x h / Vs (BT.601, even size needed only along
+    an axis with factor 2); chroma sample j sits at luma Hs j + (Hs - 1) / 2."""
+    hs, vs = sampling_factors(sampling, "yuv420_to_clip")
     if matrix not in MATRICES:
         raise ValueError("yuv420_to_clip: matrix must be one of %s, got %r" % (MATRICES, matrix))
     if filter not in FILTERS:
@@ -332,13 +365,16 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
                                  out.data_ptr(), out_w, out_h, crop, mean, std,
                                  dtype == torch.bfloat16,
                                  torch.cuda.current_stream(buf.device).cuda_stream,
-                                 matrix=1 if jfif else 0, antialias=antialias)
+                                 matrix=1 if jfif else 0, antialias=antialias,
+                                 sampling=SAMPLINGS.index(sampling))
         return out
-    if (not jfif and (src_w % 2 or src_h % 2)) or planes.c_step not in (1, 2):
+    if (not jfif and ((hs == 2 and src_w % 2) or (vs == 2 and src_h % 2))) \
+            or planes.c_step not in (1, 2):
         raise ValueError("yuv420_to_clip: even frame sizes and a chroma step of 1 or 2")
     if any(o < 0 or o + F * frame_stride > buf.numel() for o in offsets):
         raise ValueError("yuv420_to_clip: a clip span lies outside the buffer")
-    cw, ch = (src_w + jfif) // 2, (src_h + jfif) // 2
+    cw = (src_w + jfif) // 2 if hs == 2 else src_w
+    ch = (src_h + jfif) // 2 if vs == 2 else src_h
     base = (torch.tensor(offsets, dtype=torch.int64).view(n, 1)
             + torch.arange(F, dtype=torch.int64).view(1, F) * frame_stride).view(-1, 1, 1)
 
@@ -349,21 +385,31 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
     return _planes_to_clip(gather(planes.y, planes.y_stride, src_h, src_w, 1),
                            gather(planes.u, planes.u_stride, ch, cw, planes.c_step),
                            gather(planes.v, planes.v_stride, ch, cw, planes.c_step),
-                           shape, crop, dtype, mean, std, out, matrix, filter)
+                           shape, crop, dtype, mean, std, out, matrix, filter, (hs, vs))
 
 
 # ---------------------------------------------------------------------------
 # MJPEG frame records (utils/mjpeg.py) -> padded I420 surfaces
 # ---------------------------------------------------------------------------
-def jpeg_surface_planes(mw: int, mh: int) -> YuvPlanes:
-    """Where ``jpeg_idct`` puts a frame's planes (frame stride ``384 mw mh``)."""
-    n = mw * mh
-    return YuvPlanes(0, 256 * n, 320 * n, 16 * mw, 8 * mw, 8 * mw, 1)
+def jpeg_surface_planes(mw: int, mh: int, sampling: str = "420") -> YuvPlanes:
+    """Where ``jpeg_idct`` puts a frame's planes: Y [8 Vs mh, 8 Hs mw], then Cb
+    and Cr [8 mh, 8 mw]; frame stride ``64 B mw mh``, B = Hs Vs + 2 (4:2:0:
+    ``384 mw mh``)."""
+    hs, vs = sampling_factors(sampling, "jpeg_surface_planes")
+    n, ny = mw * mh, hs * vs
+    return YuvPlanes(0, 64 * ny * n, 64 * (ny + 1) * n, 8 * hs * mw, 8 * mw, 8 * mw, 1)
+
+
+def jpeg_frame_bytes(mw: int, mh: int, sampling: str = "420") -> Tuple[int, int]:
+    """(frame record bytes, surface frame bytes) of an ``mw`` x ``mh`` MCU grid."""
+    hs, vs = sampling_factors(sampling, "jpeg_frame_bytes")
+    nb = hs * vs + 2
+    return 384 + 128 * nb * mw * mh, 64 * nb * mw * mh
 
 
 def jpeg_idct(records: torch.Tensor, nframes: int, mw: int, mh: int,
               out: Optional[torch.Tensor] = None,
-              record_bytes: Optional[int] = None) -> torch.Tensor:
+              record_bytes: Optional[int] = None, sampling: str = "420") -> torch.Tensor:
     """Dequantise + 8x8 inverse DCT of ``nframes`` frame records (flat uint8
     tensor, ``record_bytes`` apart, default ``384 + 768 mw mh``; layout in
     ``utils/mjpeg.py``) into 8-bit planar frames at the padded size: per frame
@@ -371,10 +417,17 @@ def jpeg_idct(records: torch.Tensor, nframes: int, mw: int, mh: int,
     a flat uint8 surface to write into (the result is its leading part). fp32
     arithmetic, + 128, round to nearest, clamp. On the GPU one
     ``jpeg_idct_kernel`` launch, after the launcher checked both buffers
-    against the geometry; on the CPU a torch mirror."""
-    n = mw * mh
-    rb = 384 + 768 * n if record_bytes is None else int(record_bytes)
-    need = nframes * 384 * n
+    against the geometry; on the CPU a torch mirror.
+
+    ``sampling`` ``"422"`` / ``"444"``: records of ``384 + 128 B mw mh`` bytes
+    (B = 4 / 3 blocks per MCU, the Y blocks over the ``Vs mh x Hs mw`` grid)
+    into frames of Y [8 Vs mh, 8 Hs mw], Cb, Cr [8 mh, 8 mw], ``64 B mw mh``
+    bytes."""
+    hs, vs = sampling_factors(sampling, "jpeg_idct")
+    n, ny = mw * mh, hs * vs
+    rb_min, fbytes = jpeg_frame_bytes(mw, mh, sampling)
+    rb = rb_min if record_bytes is None else int(record_bytes)
+    need = nframes * fbytes
     if records.dtype != torch.uint8 or records.dim() != 1 or not records.is_contiguous():
         raise ValueError("jpeg_idct: records must be a flat contiguous uint8 tensor")
     if out is not None and (out.dtype != torch.uint8 or out.dim() != 1
@@ -387,21 +440,23 @@ def jpeg_idct(records: torch.Tensor, nframes: int, mw: int, mh: int,
             out = torch.empty(need, dtype=torch.uint8, device=records.device)
         kernels().jpeg_idct(records.data_ptr(), records.numel(), rb, nframes, mw, mh,
                             out.data_ptr(), out.numel(),
-                            torch.cuda.current_stream(records.device).cuda_stream)
+                            torch.cuda.current_stream(records.device).cuda_stream,
+                            sampling=SAMPLINGS.index(sampling))
         return out[:need]
-    if mw < 1 or mh < 1 or rb < 384 + 768 * n or nframes * rb > records.numel() \
+    if mw < 1 or mh < 1 or rb < rb_min or nframes * rb > records.numel() \
             or (out is not None and out.numel() < need):
         raise ValueError("jpeg_idct: a record or a frame lies outside its buffer")
     rec = records[:nframes * rb].view(nframes, rb)
     qt = rec[:, :384].contiguous().view(torch.int16).view(nframes, 3, 1, 64).float()
-    co = rec[:, 384:384 + 768 * n].contiguous().view(torch.int16).view(nframes, 6 * n, 64).float()
+    co = rec[:, 384:rb_min].contiguous().view(torch.int16).view(nframes, (ny + 2) * n, 64).float()
     u = torch.arange(8, dtype=torch.float64)
     basis = 0.5 * torch.cos((2.0 * u.view(8, 1) + 1.0) * u.view(1, 8) * math.pi / 16.0)
     basis[:, 0] *= math.sqrt(0.5)
     basis = basis.float()                                   # [x][u], as the kernel's table
     planes = []
-    for c, (lo, hi, rows, cols) in enumerate(((0, 4 * n, 2 * mh, 2 * mw),
-                                              (4 * n, 5 * n, mh, mw), (5 * n, 6 * n, mh, mw))):
+    for c, (lo, hi, rows, cols) in enumerate(((0, ny * n, vs * mh, hs * mw),
+                                              (ny * n, (ny + 1) * n, mh, mw),
+                                              ((ny + 1) * n, (ny + 2) * n, mh, mw))):
         f = (co[:, lo:hi] * qt[:, c]).view(nframes, -1, 8, 8)           # [frame, block, u, v]
         s = torch.einsum("xu,fbuv,yv->fbxy", basis, f, basis) + 128.0
         s = s.round().clamp(0, 255).to(torch.uint8)
@@ -418,7 +473,8 @@ def jpeg_huff(scans: torch.Tensor, scan_offs, nframes: int, mw: int, mh: int,
               out: Optional[torch.Tensor] = None, record_bytes: Optional[int] = None,
               status: Optional[torch.Tensor] = None,
               offs_dev: Optional[torch.Tensor] = None, subseq_bytes: int = 0,
-              rounds: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+              rounds: Optional[torch.Tensor] = None,
+              sampling: str = "420") -> Tuple[torch.Tensor, torch.Tensor]:
     """Huffman-decode ``nframes`` packed scan records (``utils/mjpeg.py:
     pack_scans``; flat uint8 tensor ``scans``, record ``i`` at
     ``scan_offs[i] : scan_offs[i + 1]``, ``scan_offs`` a host table of
@@ -446,12 +502,17 @@ def jpeg_huff(scans: torch.Tensor, scan_offs, nframes: int, mw: int, mh: int,
     byte for byte. ``rounds``: an int32 tensor of >= ``nframes`` on the
     device of ``scans`` that receives each frame's synchronisation rounds
     (allocated and dropped when not given). On the CPU the kernel's host
-    emulation, ``rnb_jpeg_decode_scans_subseq_host``."""
+    emulation, ``rnb_jpeg_decode_scans_subseq_host``.
+
+    ``sampling``: the geometry ``mw`` / ``mh`` count MCUs of (records default to
+    ``384 + 128 B mw mh`` bytes). The kernels take it from here, never from the
+    scan record; a record whose sampling word differs gets the status
+    'scan record'."""
     import numpy as np
     from ..utils import mjpeg
     subseq_bytes = mjpeg.check_subseq_bytes(subseq_bytes, "jpeg_huff")
-    n = mw * mh
-    rb = 384 + 768 * n if record_bytes is None else int(record_bytes)
+    sampling_factors(sampling, "jpeg_huff")
+    rb = jpeg_frame_bytes(mw, mh, sampling)[0] if record_bytes is None else int(record_bytes)
     offs = np.ascontiguousarray(scan_offs.numpy() if isinstance(scan_offs, torch.Tensor)
                                 else scan_offs, dtype=np.int64)
     if offs.ndim != 1 or offs.size != nframes + 1:
@@ -490,16 +551,17 @@ def jpeg_huff(scans: torch.Tensor, scan_offs, nframes: int, mw: int, mh: int,
         if subseq_bytes:
             kernels().jpeg_huff_subseq(scans.data_ptr(), scans.numel(), offs, offs_dev.data_ptr(),
                                        nframes, mw, mh, out.data_ptr(), out.numel(), rb,
-                                       status.data_ptr(), subseq_bytes, rounds.data_ptr(), stream)
+                                       status.data_ptr(), subseq_bytes, rounds.data_ptr(), stream,
+                                       sampling=SAMPLINGS.index(sampling))
         else:
             kernels().jpeg_huff(scans.data_ptr(), scans.numel(), offs, offs_dev.data_ptr(),
                                 nframes, mw, mh, out.data_ptr(), out.numel(), rb,
-                                status.data_ptr(), stream)
+                                status.data_ptr(), stream, sampling=SAMPLINGS.index(sampling))
         return out[:nframes * rb], status[:nframes]
     try:
         got = mjpeg.decode_scans_host(scans.numpy(), offs, nframes, mw, mh, out.numpy(), rb,
                                       status.numpy(), subseq_bytes=subseq_bytes,
-                                      return_rounds=True)
+                                      return_rounds=True, sampling=sampling)
     except mjpeg.JpegError:
         raise ValueError("jpeg_huff: a scan record or a frame record lies outside its buffer, "
                          "or is misaligned")

@@ -4,22 +4,28 @@ encoder, and a numpy reference decoder.
 A stream is JPEG frames back to back (SOI ... EOI, SOI ... EOI, ...), what
 ``ffmpeg -c:v mjpeg -f mjpeg`` writes. Only what ``csrc/jpeg_entropy.cpp``
 reads is accepted: baseline sequential Huffman (SOF0), 8-bit, three components
-sampled 2x2 / 1x1 / 1x1 (4:2:0), one interleaved scan, every frame of the
-first frame's size. Containers (AVI / MOV), progressive JPEG, 4:2:2, 4:4:4 and
-grayscale are not read.
+sampled 2x2 / 1x1 / 1x1 (4:2:0), 2x1 / 1x1 / 1x1 (4:2:2) or 1x1 / 1x1 / 1x1
+(4:4:4), one interleaved scan, every frame of the first frame's size and
+sampling. Containers (AVI / MOV), progressive JPEG, 4:4:0, 4:1:1 and grayscale
+are not read.
 
-``read_index`` finds the frames (native ``rnb_mjpeg_index`` when
+The *sampling* (``"420"``, ``"422"``, ``"444"``; luma factors (Hs, Vs) = (2, 2),
+(2, 1), (1, 1)) sets the MCU: ``8 Hs x 8 Vs`` luma pixels in ``B = Hs Vs + 2``
+blocks, the Y blocks row-major, then Cb, then Cr; ``mw = ceil(W / (8 Hs))``,
+``mh = ceil(H / (8 Vs))``. ``"420"`` is the default everywhere.
+
+``read_index`` finds the frames (native ``rnb_mjpeg_index_s`` when
 ``librnb_jpeg.so`` is there, else the parser below); ``write_mjpeg`` encodes
-planar 4:2:0 frames with the Annex K Huffman tables and returns the quantised
+planar frames with the Annex K Huffman tables and returns the quantised
 coefficients it wrote; ``decode_reference`` is a slow, independent decoder of
 one frame (the tests' oracle, and the fallback entropy decoder).
 
 The *frame record* both decoders produce is the upload format of
 ``MjpegDecoder``: ``uint16 qt[3][64]`` (the quantisation table of each
 component, natural order), then ``int16`` quantised coefficients, 64 per block
-in natural order: the Y blocks row-major over the padded ``2 mh x 2 mw`` grid,
-then the ``mh x mw`` Cb blocks, then Cr (``mw = ceil(W / 16)``, ``mh =
-ceil(H / 16)``): ``384 + 768 mw mh`` bytes.
+in natural order: the Y blocks row-major over the padded ``Vs mh x Hs mw`` grid,
+then the ``mh x mw`` Cb blocks, then Cr: ``384 + 128 B mw mh`` bytes
+(4:2:0: ``mw = ceil(W / 16)``, ``mh = ceil(H / 16)``, ``384 + 768 mw mh``).
 
 ``pack_scans`` / ``decode_scans_host`` serve ``MjpegDecoder(entropy="gpu")``:
 the first packs frames' entropy-coded scans into *scan records* (tables, the
@@ -86,7 +92,8 @@ _REASONS = {
     "precision": "sample precision is not 8 bits",
     "DQT precision": "16-bit quantisation table; only 8-bit tables are read",
     "components": "not three components (grayscale / CMYK are not read)",
-    "sampling": "sampling factors are not 2x2, 1x1, 1x1 (only 4:2:0 is read)",
+    "sampling": "sampling factors are not 2x2 / 2x1 / 1x1 luma with 1x1 chroma "
+                "(only 4:2:0, 4:2:2 and 4:4:4 are read)",
     "scans": "more than one scan, or a scan that does not hold all three components",
     "size": "the frame's size differs from the first frame's",
     "huffman": "a Huffman code that matches no table entry, or an invalid table",
@@ -98,25 +105,52 @@ _REASONS = {
     "record": "the record is too small for the frame",
     "dc_range": "DC value outside the 16-bit range",
     "dimensions": "zero width or height",
-    "scan record": "malformed scan record (header, span table or extent)",
+    "scan record": "malformed scan record (header, span table, extent or sampling word)",
+    "sampling change": "the frame's sampling differs from the first frame's",
 }
 
+SAMPLINGS = ("420", "422", "444")        # index: the native sampling word
+SAMPLING_FACTORS = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}
+# SOF0 luma sampling byte -> sampling
+_SOF_SAMPLING = {0x22: "420", 0x21: "422", 0x11: "444"}
 
-def geometry(width: int, height: int) -> Tuple[int, int, int]:
-    """(mw, mh, record bytes) of a ``width`` x ``height`` 4:2:0 frame."""
-    mw, mh = (width + 15) // 16, (height + 15) // 16
-    return mw, mh, 384 + 768 * mw * mh
+
+def sampling_factors(sampling: str, who: str = "mjpeg") -> Tuple[int, int]:
+    """Luma factors (Hs, Vs); ``ValueError`` naming the argument otherwise."""
+    if sampling not in SAMPLING_FACTORS:
+        raise ValueError("%s: sampling must be one of %s, got %r" % (who, SAMPLINGS, sampling))
+    return SAMPLING_FACTORS[sampling]
+
+
+def mcu_blocks(sampling: str = "420") -> int:
+    """Blocks per MCU: 6, 4 or 3."""
+    hs, vs = sampling_factors(sampling, "mcu_blocks")
+    return hs * vs + 2
+
+
+def geometry(width: int, height: int, sampling: str = "420") -> Tuple[int, int, int]:
+    """(mw, mh, record bytes) of a ``width`` x ``height`` frame."""
+    hs, vs = sampling_factors(sampling, "geometry")
+    mw, mh = -(-width // (8 * hs)), -(-height // (8 * vs))
+    return mw, mh, 384 + 128 * (hs * vs + 2) * mw * mh
+
+
+def chroma_size(width: int, height: int, sampling: str = "420") -> Tuple[int, int]:
+    """(cw, ch): ceil(width / Hs), ceil(height / Vs)."""
+    hs, vs = sampling_factors(sampling, "chroma_size")
+    return -(-width // hs), -(-height // vs)
 
 
 class MjpegIndex(NamedTuple):
     width: int
     height: int
-    mw: int                   # MCUs (16 x 16 luma samples) per row
+    mw: int                   # MCUs (8 Hs x 8 Vs luma samples) per row
     mh: int                   # MCU rows
-    record_bytes: int         # 384 + 768 * mw * mh
+    record_bytes: int         # 384 + 128 * B * mw * mh
     restart_interval: int     # of the first frame (informational)
     offsets: np.ndarray       # int64 [frames]: byte offset of each frame's SOI
     lengths: np.ndarray       # int64 [frames]: bytes up to and including its EOI
+    sampling: str = "420"     # "420", "422" or "444": every frame's
 
     @property
     def num_frames(self) -> int:
@@ -135,7 +169,10 @@ def _as_u8(data) -> np.ndarray:
 def read_index(path: str, data=None) -> MjpegIndex:
     """Frame table of the stream at ``path``; ``data`` may pass its contents
     (bytes, a memory map or a uint8 array). Every frame's header is parsed;
-    raises ``ValueError`` naming file, frame and field for anything not read."""
+    raises ``ValueError`` naming file, frame and field for anything not read.
+    The first frame is also decoded once: a header that announces another of
+    the three samplings than its scan was written for is refused (field
+    'sampling'; ``_check_announced_sampling``)."""
     if data is None:
         with open(path, "rb") as fp:
             data = fp.read()
@@ -144,37 +181,97 @@ def read_index(path: str, data=None) -> MjpegIndex:
         raise ValueError("%s: empty file (field 'SOI')" % path)
     lib = _native()
     if lib is not None:
-        got = lib.index(buf)
+        got = lib.index_s(buf)
         if isinstance(got, tuple) and len(got) == 2:          # (field, frame)
             raise ValueError("%s: frame %d is not read (field '%s': %s)"
                              % (path, got[1], got[0], _REASONS.get(got[0], got[0])))
-        w, h, ri, offs, lens = got
+        w, h, ri, offs, lens, sampling = got
+        sampling = SAMPLINGS[sampling]
     else:
-        offs, lens, pos, w, h, ri = [], [], 0, 0, 0, 0
+        offs, lens, pos, w, h, ri, sampling = [], [], 0, 0, 0, 0, "420"
         raw = buf.tobytes()
         while pos < len(raw):
             try:
                 hdr = _parse_frame(raw[pos:])
+                if offs and hdr["sampling"] != sampling:
+                    raise JpegError("sampling change", _REASONS["sampling change"])
                 if offs and (hdr["width"], hdr["height"]) != (w, h):
                     raise JpegError("size", _REASONS["size"])
             except JpegError as e:
                 raise ValueError("%s: frame %d is not read (field '%s': %s)"
                                  % (path, len(offs), e.field, e))
             if not offs:
-                w, h, ri = hdr["width"], hdr["height"], hdr["restart"]
+                w, h, ri, sampling = hdr["width"], hdr["height"], hdr["restart"], hdr["sampling"]
             offs.append(pos)
             lens.append(hdr["end"])
             pos += hdr["end"]
         offs, lens = np.array(offs, dtype=np.int64), np.array(lens, dtype=np.int64)
-    mw, mh, rec = geometry(w, h)
-    return MjpegIndex(w, h, mw, mh, rec, ri, offs, lens)
+    if len(offs):
+        a0 = int(offs[0])
+        _check_announced_sampling(path, buf[a0:a0 + int(lens[0])], w, h, sampling)
+    mw, mh, rec = geometry(w, h, sampling)
+    return MjpegIndex(w, h, mw, mh, rec, ri, offs, lens, sampling)
+
+
+def _sof_offset(frame: np.ndarray) -> int:
+    """Offset of the frame's SOF0 marker (walking the segments), or -1."""
+    pos, n = 2, int(frame.size)
+    while pos + 4 <= n and frame[pos] == 0xFF:
+        m = int(frame[pos + 1])
+        if m == 0xFF:
+            pos += 1
+            continue
+        if m == 0xC0:
+            return pos
+        if m in (0xD9, 0xDA):
+            break
+        pos += 2 + (int(frame[pos + 2]) << 8 | int(frame[pos + 3]))
+    return -1
+
+
+def _frame_decodes(frame: np.ndarray, w: int, h: int, sampling: str) -> bool:
+    lib = _native()
+    if lib is not None:
+        rec = np.empty(geometry(w, h, sampling)[2], dtype=np.uint8)
+        return lib.decode_frames_rc(frame, [0], [frame.size], rec, rec.size, 1,
+                                    SAMPLINGS.index(sampling)) == 0
+    try:
+        return decode_reference(frame.tobytes(), planes=False)["sampling"] == sampling
+    except JpegError:
+        return False
+
+
+def _check_announced_sampling(path: str, frame: np.ndarray, w: int, h: int,
+                              sampling: str) -> None:
+    """The three samplings share every header byte but one, so a header can
+    announce a layout its scan was not written for; the blocks then land in the
+    wrong planes or the decode fails far from the cause. The stream's first frame
+    is therefore decoded once: if it does not decode as announced but does with
+    another luma sampling byte, the index refuses it, naming 'sampling'. A frame
+    that decodes under none is left to ``decode``'s own refusals, as before."""
+    frame = np.ascontiguousarray(frame)
+    if _frame_decodes(frame, w, h, sampling):
+        return
+    sof = _sof_offset(frame)
+    if sof < 0 or sof + 11 >= frame.size:
+        return
+    for byte, other in _SOF_SAMPLING.items():
+        if other != sampling:
+            trial = frame.copy()
+            trial[sof + 11] = byte
+            if _frame_decodes(trial, w, h, other):
+                raise ValueError("%s: frame 0 is not read (field 'sampling': the header announces "
+                                 "%s but the scan decodes only as %s)"
+                                 % (path, ":".join(sampling), ":".join(other)))
 
 
 def entropy_decode(data, offsets, lengths, out: np.ndarray, record_bytes: int,
-                   threads: int = 1, name: str = "<mjpeg>") -> None:
+                   threads: int = 1, name: str = "<mjpeg>", sampling: str = "420") -> None:
     """Entropy-decode the frames at ``offsets`` / ``lengths`` of ``data`` into
     records laid ``record_bytes`` apart in the uint8 array ``out`` (native
-    decoder, or ``decode_reference`` when the library is absent)."""
+    decoder, or ``decode_reference`` when the library is absent). ``sampling``:
+    the stream's (``MjpegIndex.sampling``); a frame of another is refused."""
+    sampling_factors(sampling, "entropy_decode")
     buf = _as_u8(data)
     n = len(offsets)
     if out.dtype != np.uint8 or out.ndim != 1 or out.size < n * record_bytes:
@@ -182,7 +279,8 @@ def entropy_decode(data, offsets, lengths, out: np.ndarray, record_bytes: int,
                          % (n * record_bytes))
     lib = _native()
     if lib is not None:
-        field = lib.decode_frames(buf, offsets, lengths, out, record_bytes, threads)
+        field = lib.decode_frames(buf, offsets, lengths, out, record_bytes, threads,
+                                  SAMPLINGS.index(sampling))
         if field is not None:
             raise ValueError("%s: a sampled frame is not read (field '%s': %s)"
                              % (name, field, _REASONS.get(field, field)))
@@ -191,6 +289,8 @@ def entropy_decode(data, offsets, lengths, out: np.ndarray, record_bytes: int,
         try:
             ref = decode_reference(buf[int(offsets[i]):int(offsets[i] + lengths[i])].tobytes(),
                                    planes=False)
+            if ref["sampling"] != sampling:
+                raise JpegError("sampling change", _REASONS["sampling change"])
         except JpegError as e:
             raise ValueError("%s: a sampled frame is not read (field '%s': %s)"
                              % (name, e.field, e))
@@ -220,16 +320,21 @@ def _need_native(what: str):
 
 
 def pack_scans(data, offsets, lengths, out: np.ndarray, width: int = 0, height: int = 0,
-               name: str = "<mjpeg>", frame0: int = 0) -> Tuple[int, np.ndarray]:
+               name: str = "<mjpeg>", frame0: int = 0,
+               sampling: str = "420") -> Tuple[int, np.ndarray]:
     """Pack the scans of the frames at ``offsets`` / ``lengths`` of ``data``
     into scan records in the flat, 16-byte aligned uint8 array ``out``
     (``rnb_jpeg_pack_scans``: header parse, restart markers located, counted and
     checked, no Huffman work). ``width`` / ``height``: the size every frame must
     have (0: the first frame's). Returns (bytes written, int64 offsets
     [n + 1] of the records in ``out``). A refusal raises ``JpegError`` naming
-    ``name``, the frame (``frame0`` + its index) and the field."""
+    ``name``, the frame (``frame0`` + its index) and the field. ``sampling``:
+    the stream's; it goes into the record's fourth header word, and a frame of
+    another sampling is refused."""
+    sampling_factors(sampling, "pack_scans")
     lib = _need_native("pack_scans")
-    got, extra = lib.pack_scans(_as_u8(data), offsets, lengths, out, width, height)
+    got, extra = lib.pack_scans(_as_u8(data), offsets, lengths, out, width, height,
+                                SAMPLINGS.index(sampling))
     if got < 0:
         field = lib.error_name(got)
         raise JpegError(field, "%s: frame %d is not read (field '%s': %s)"
@@ -250,7 +355,7 @@ def check_subseq_bytes(subseq_bytes, what: str) -> int:
 def decode_scans_host(scans: np.ndarray, scan_offs, nframes: int, mw: int, mh: int,
                       out: Optional[np.ndarray] = None, record_bytes: Optional[int] = None,
                       status: Optional[np.ndarray] = None, subseq_bytes: int = 0,
-                      return_rounds: bool = False):
+                      return_rounds: bool = False, sampling: str = "420"):
     """The GPU interval decoder's host mirror (``rnb_jpeg_decode_scans_host``):
     ``nframes`` scan records -> (frame records ``record_bytes`` apart in a flat
     uint8 array, int32 status per frame: 0 or the code of the frame's
@@ -262,17 +367,21 @@ def decode_scans_host(scans: np.ndarray, scan_offs, nframes: int, mw: int, mh: i
     (``rnb_jpeg_decode_scans_subseq_host``): frames without restart markers are
     decoded by synchronised subsequences of that many scan bytes, to the same
     records and status. ``return_rounds`` appends the int32 synchronisation
-    rounds per frame (zeros at ``subseq_bytes=0``) to the result."""
+    rounds per frame (zeros at ``subseq_bytes=0``) to the result.
+
+    ``sampling``: the geometry ``mw`` / ``mh`` count MCUs of; a scan record
+    whose sampling word is another one gets the status 'scan record'."""
     check_subseq_bytes(subseq_bytes, "decode_scans_host")
+    nb = mcu_blocks(sampling)
     lib = _need_native("decode_scans_host")
-    rb = 384 + 768 * mw * mh if record_bytes is None else int(record_bytes)
+    rb = 384 + 128 * nb * mw * mh if record_bytes is None else int(record_bytes)
     if out is None:
         out = np.empty(nframes * rb, dtype=np.uint8)
     if status is None:
         status = np.zeros(nframes, dtype=np.int32)
     rounds = np.zeros(nframes, dtype=np.int32)
     rc = lib.decode_scans_host(scans, scan_offs, nframes, mw, mh, out, rb, status,
-                               subseq_bytes, rounds)
+                               subseq_bytes, rounds, SAMPLINGS.index(sampling))
     if rc:
         field = lib.error_name(rc)
         raise JpegError(field, "decode_scans_host: %s (field '%s')"
@@ -297,27 +406,32 @@ def raise_for_status(status, name: str, frames) -> None:
 
 
 def pack_record(coefs: np.ndarray, qt: np.ndarray) -> np.ndarray:
-    """Frame record bytes from ``coefs`` int16 [6 mw mh, 64] and ``qt`` [3, 64]."""
+    """Frame record bytes from ``coefs`` int16 [B mw mh, 64] and ``qt`` [3, 64]."""
     return np.concatenate([np.ascontiguousarray(qt, dtype=np.uint16).reshape(-1).view(np.uint8),
                            np.ascontiguousarray(coefs, dtype=np.int16).reshape(-1).view(np.uint8)])
 
 
-def unpack_record(rec: np.ndarray, mw: int, mh: int) -> Tuple[np.ndarray, np.ndarray]:
-    """(coefs int16 [6 mw mh, 64], qt uint16 [3, 64]) views of a record."""
-    rec = np.ascontiguousarray(rec[:384 + 768 * mw * mh])
+def unpack_record(rec: np.ndarray, mw: int, mh: int,
+                  sampling: str = "420") -> Tuple[np.ndarray, np.ndarray]:
+    """(coefs int16 [B mw mh, 64], qt uint16 [3, 64]) views of a record."""
+    rec = np.ascontiguousarray(rec[:384 + 128 * mcu_blocks(sampling) * mw * mh])
     return rec[384:].view(np.int16).reshape(-1, 64), rec[:384].view(np.uint16).reshape(3, 64)
 
 
 # ---------------------------------------------------------------------------
 # fp64 reference IDCT
 # ---------------------------------------------------------------------------
-def idct_planes_f64(coefs: np.ndarray, qt: np.ndarray, mw: int, mh: int):
-    """Ideal IDCT of a frame's blocks: fp64 (Y [16 mh, 16 mw], Cb, Cr
+def idct_planes_f64(coefs: np.ndarray, qt: np.ndarray, mw: int, mh: int,
+                    sampling: str = "420"):
+    """Ideal IDCT of a frame's blocks: fp64 (Y [8 Vs mh, 8 Hs mw], Cb, Cr
     [8 mh, 8 mw]) sample values + 128, before rounding and clamping."""
     n = mw * mh
+    hs, vs = sampling_factors(sampling, "idct_planes_f64")
+    ny = hs * vs
     out = []
-    for c, (lo, hi, rows, cols) in enumerate(((0, 4 * n, 2 * mh, 2 * mw),
-                                              (4 * n, 5 * n, mh, mw), (5 * n, 6 * n, mh, mw))):
+    for c, (lo, hi, rows, cols) in enumerate(((0, ny * n, vs * mh, hs * mw),
+                                              (ny * n, (ny + 1) * n, mh, mw),
+                                              ((ny + 1) * n, (ny + 2) * n, mh, mw))):
         f = (coefs[lo:hi].astype(np.float64) * qt[c].astype(np.float64)).reshape(-1, 8, 8)
         s = np.einsum("ux,buv,vy->bxy", BASIS, f, BASIS) + 128.0
         out.append(s.reshape(rows, cols, 8, 8).transpose(0, 2, 1, 3).reshape(rows * 8, cols * 8))
@@ -412,30 +526,33 @@ def _fdct_quant(plane: np.ndarray, q: np.ndarray, coef_max: int = 1023) -> np.nd
 
 
 def encode_frame(y, u, v, qt: np.ndarray, restart_interval: int = 0,
-                 coefs: Optional[np.ndarray] = None) -> Tuple[bytes, np.ndarray]:
-    """One baseline 4:2:0 JPEG frame from uint8 planes Y [H, W] and U, V
-    [ceil(H/2), ceil(W/2)] with quantisation tables ``qt`` [2, 64] (luma,
+                 coefs: Optional[np.ndarray] = None,
+                 sampling: str = "420") -> Tuple[bytes, np.ndarray]:
+    """One baseline JPEG frame of ``sampling`` from uint8 planes Y [H, W] and U, V
+    [ceil(H/Vs), ceil(W/Hs)] with quantisation tables ``qt`` [2, 64] (luma,
     chroma; natural order). Returns (bytes, quantised coefficients int16
-    [6 mw mh, 64] in record order). ``coefs`` (same layout) replaces the
+    [B mw mh, 64] in record order). ``coefs`` (same layout) replaces the
     transform of the planes, for hand-made blocks."""
     y = np.asarray(y)
     H, W = y.shape
-    mw, mh, _ = geometry(W, H)
+    hs, vs = sampling_factors(sampling, "encode_frame")
+    ny = hs * vs
+    mw, mh, _ = geometry(W, H, sampling)
     qt = np.asarray(qt, dtype=np.uint16).reshape(2, 64)
     if coefs is None:
-        ch, cw = (H + 1) // 2, (W + 1) // 2
+        cw, ch = chroma_size(W, H, sampling)
         if np.asarray(u).shape != (ch, cw) or np.asarray(v).shape != (ch, cw):
             raise ValueError("encode_frame: chroma planes must be %dx%d for a %dx%d frame"
                              % (cw, ch, W, H))
-        coefs = np.concatenate([_fdct_quant(_pad_plane(y, 16 * mh, 16 * mw), qt[0]),
+        coefs = np.concatenate([_fdct_quant(_pad_plane(y, 8 * vs * mh, 8 * hs * mw), qt[0]),
                                 _fdct_quant(_pad_plane(np.asarray(u), 8 * mh, 8 * mw), qt[1]),
                                 _fdct_quant(_pad_plane(np.asarray(v), 8 * mh, 8 * mw), qt[1])])
-    coefs = np.ascontiguousarray(coefs, dtype=np.int16).reshape(6 * mw * mh, 64)
+    coefs = np.ascontiguousarray(coefs, dtype=np.int16).reshape((ny + 2) * mw * mh, 64)
     head = b"\xff\xd8" + _segment(0xE0, b"JFIF\0\x01\x01\0\0\x01\0\x01\0\0")
     head += _segment(0xDB, b"".join(bytes([i]) + bytes(qt[i][ZIGZAG].astype(np.uint8))
                                     for i in range(2)))
     head += _segment(0xC0, bytes([8]) + H.to_bytes(2, "big") + W.to_bytes(2, "big")
-                     + bytes([3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1]))
+                     + bytes([3, 1, (hs << 4) | vs, 0, 2, 0x11, 1, 3, 0x11, 1]))
     tables = ((0x00, HUFF_DC_LUMA), (0x10, HUFF_AC_LUMA), (0x01, HUFF_DC_CHROMA),
               (0x11, HUFF_AC_CHROMA))
     head += _segment(0xC4, b"".join(bytes([i]) + bytes(t[0]) + t[1] for i, t in tables))
@@ -455,24 +572,26 @@ def encode_frame(y, u, v, qt: np.ndarray, restart_interval: int = 0,
             body += bw.out + bytes([0xFF, 0xD0 + (m // restart_interval - 1) % 8])
             bw, pred = _BitWriter(), [0, 0, 0]
         my, mx = divmod(m, mw)
-        for dy in range(2):
-            for dx in range(2):
-                pred[0] = _put_block(bw, zz[(2 * my + dy) * 2 * mw + 2 * mx + dx], pred[0],
+        for dy in range(vs):
+            for dx in range(hs):
+                pred[0] = _put_block(bw, zz[(vs * my + dy) * hs * mw + hs * mx + dx], pred[0],
                                      dcl, acl)
-        pred[1] = _put_block(bw, zz[4 * n + m], pred[1], dcc, acc)
-        pred[2] = _put_block(bw, zz[5 * n + m], pred[2], dcc, acc)
+        pred[1] = _put_block(bw, zz[ny * n + m], pred[1], dcc, acc)
+        pred[2] = _put_block(bw, zz[(ny + 1) * n + m], pred[2], dcc, acc)
     bw.flush()
     return head + bytes(body + bw.out) + b"\xff\xd9", coefs
 
 
 def write_mjpeg(path: str, frames_yuv420, quality: int = 75, restart_interval: int = 0,
-                qtables=None) -> List[Tuple[np.ndarray, np.ndarray]]:
-    """Write planar 4:2:0 frames ``(Y [H, W], U, V [ceil(H/2), ceil(W/2)])`` as
+                qtables=None, sampling: str = "420") -> List[Tuple[np.ndarray, np.ndarray]]:
+    """Write planar frames ``(Y [H, W], U, V [ceil(H/Vs), ceil(W/Hs)])`` of
+    ``sampling`` (``"420"``, ``"422"``, ``"444"``) as
     a baseline MJPEG stream with the Annex K Huffman tables; ``restart_interval``
     in MCUs (0: none). ``qtables``: one ``[2, 64]`` (luma, chroma; natural order)
     array for all frames or a sequence of one per frame; default the Annex K
     tables at ``quality``. Returns, per frame, the quantised coefficients written
-    (int16 [6 mw mh, 64], record order) and the record's tables (uint16 [3, 64])."""
+    (int16 [B mw mh, 64], record order) and the record's tables (uint16 [3, 64])."""
+    sampling_factors(sampling, "write_mjpeg")
     frames = list(frames_yuv420)
     if not frames:
         raise ValueError("write_mjpeg: no frames")
@@ -487,7 +606,7 @@ def write_mjpeg(path: str, frames_yuv420, quality: int = 75, restart_interval: i
                 raise ValueError("write_mjpeg: frame %d is %s, the first is %s"
                                  % (i, np.asarray(y).shape, shape))
             qt = np.asarray(qtables[i] if per_frame else qtables, dtype=np.uint16).reshape(2, 64)
-            data, coefs = encode_frame(y, u, v, qt, restart_interval)
+            data, coefs = encode_frame(y, u, v, qt, restart_interval, sampling=sampling)
             fp.write(data)
             truth.append((coefs, qt[[0, 1, 1]].copy()))
     return truth
@@ -525,9 +644,10 @@ def _parse_frame(buf: bytes) -> dict:
                 raise JpegError("precision", _REASONS["precision"])
             if s[5] != 3:
                 raise JpegError("components", _REASONS["components"])
-            if [s[7], s[10], s[13]] != [0x22, 0x11, 0x11]:
+            if s[7] not in _SOF_SAMPLING or [s[10], s[13]] != [0x11, 0x11]:
                 raise JpegError("sampling", _REASONS["sampling"])
-            hdr.update(height=int.from_bytes(s[1:3], "big"), width=int.from_bytes(s[3:5], "big"),
+            hdr.update(sampling=_SOF_SAMPLING[s[7]], height=int.from_bytes(s[1:3], "big"),
+                       width=int.from_bytes(s[3:5], "big"),
                        tq=[s[8], s[11], s[14]])
             if not hdr["width"] or not hdr["height"]:
                 raise JpegError("dimensions", _REASONS["dimensions"])
@@ -573,21 +693,24 @@ def _parse_frame(buf: bytes) -> dict:
 
 
 def decode_reference(frame_bytes: bytes, planes: bool = True) -> dict:
-    """Decode one baseline 4:2:0 frame in numpy: ``coefs`` (int16 [6 mw mh, 64],
-    record order), ``qt`` (uint16 [3, 64]), ``width``, ``height``, ``mw``, ``mh``
-    and, with ``planes``, ``planes_f64`` (ideal IDCT + 128 at the padded size,
+    """Decode one baseline 4:2:0 / 4:2:2 / 4:4:4 frame in numpy: ``coefs`` (int16
+    [B mw mh, 64], record order), ``qt`` (uint16 [3, 64]), ``width``, ``height``,
+    ``mw``, ``mh``, ``sampling`` and, with ``planes``, ``planes_f64`` (ideal IDCT + 128 at the padded size,
     before rounding) and ``planes_u8`` (rounded, clamped). Raises ``JpegError``."""
     buf = bytes(frame_bytes)
     hdr = _parse_frame(buf)
     W, H = hdr["width"], hdr["height"]
-    mw, mh, _ = geometry(W, H)
+    sampling = hdr["sampling"]
+    hs, vs = SAMPLING_FACTORS[sampling]
+    ny = hs * vs
+    mw, mh, _ = geometry(W, H, sampling)
     n = mw * mh
     try:
         qt = np.stack([hdr["qt"][t] for t in hdr["tq"]])
         tabs = [(hdr["huff"][d], hdr["huff"][0x10 | a]) for d, a in hdr["tables"]]
     except KeyError:
         raise JpegError("table", _REASONS["table"])
-    coefs = np.zeros((6 * n, 64), dtype=np.int16)
+    coefs = np.zeros(((ny + 2) * n, 64), dtype=np.int16)
     a, b = hdr["scan"]
     chunks, start = [], a
     for q in range(a, b - 1):                      # split at RSTn
@@ -624,8 +747,9 @@ def decode_reference(frame_bytes: bytes, planes: bool = True) -> dict:
 
         for m in range(ci * ri, min(n, (ci + 1) * ri)):
             my, mx = divmod(m, mw)
-            blocks = [(0, (2 * my + dy) * 2 * mw + 2 * mx + dx) for dy in (0, 1) for dx in (0, 1)]
-            for c, blk in blocks + [(1, 4 * n + m), (2, 5 * n + m)]:
+            blocks = [(0, (vs * my + dy) * hs * mw + hs * mx + dx)
+                      for dy in range(vs) for dx in range(hs)]
+            for c, blk in blocks + [(1, ny * n + m), (2, (ny + 1) * n + m)]:
                 dc, ac = tabs[c]
                 s = symbol(dc)
                 if s > 11:
@@ -652,8 +776,8 @@ def decode_reference(frame_bytes: bytes, planes: bool = True) -> dict:
                     k += 1
                 if pos > real:
                     raise JpegError("truncated", _REASONS["truncated"])
-    out = dict(coefs=coefs, qt=qt, width=W, height=H, mw=mw, mh=mh)
+    out = dict(coefs=coefs, qt=qt, width=W, height=H, mw=mw, mh=mh, sampling=sampling)
     if planes:
-        out["planes_f64"] = idct_planes_f64(coefs, qt, mw, mh)
+        out["planes_f64"] = idct_planes_f64(coefs, qt, mw, mh, sampling)
         out["planes_u8"] = round_planes(out["planes_f64"])
     return out

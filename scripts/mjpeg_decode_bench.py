@@ -23,6 +23,9 @@
     the host decoder's, prints the synchronisation rounds and subsequences
     per frame, and repeats the ``MjpegDecoder(entropy="gpu")`` rows per size.
 
+    ``--sampling 422`` / ``444`` encodes, decodes and reports that chroma layout
+    (default 420) on every row.
+
     python scripts/mjpeg_decode_bench.py --out profiles/mjpeg_decode.txt
     python scripts/mjpeg_decode_bench.py --entropy gpu --restart-interval 22
     python scripts/mjpeg_decode_bench.py --entropy gpu --subseq-bytes 0,64,128,256,512
@@ -46,6 +49,7 @@ from rnb_amd.utils import mjpeg  # noqa: E402
 
 W, H, F, CLIPS = vops.SOURCE_W, vops.SOURCE_H, 8, 15
 DISTINCT = 24          # frames encoded; the stream repeats them
+SAMPLING = "420"       # --sampling: the chroma layout of everything below
 
 
 def event_ms(fn, reps):
@@ -60,44 +64,47 @@ def event_ms(fn, reps):
 
 def encode(quality, restart=0):
     q = mjpeg.quality_tables(quality)
-    return [mjpeg.encode_frame(*f, q, restart) for f in synthetic_frames(3, DISTINCT, W, H)]
+    return [mjpeg.encode_frame(*f, q, restart, sampling=SAMPLING)
+            for f in synthetic_frames(3, DISTINCT, W, H, sampling=SAMPLING)]
 
 
 def huff_kernel(dev, encoded, reps, rounds, lines, subseq=()):
     """jpeg_huff_kernel on one request's scan records, alternating with the
     IDCT kernel it feeds and with jpeg_huff_subseq_kernel at every size in
     ``subseq``."""
-    mw, mh, rb = mjpeg.geometry(W, H)
+    mw, mh, rb = mjpeg.geometry(W, H, SAMPLING)
     n = CLIPS * F
     frames = [encoded[i % DISTINCT][0] for i in range(n)]
     lens = np.array([len(f) for f in frames], dtype=np.int64)
     offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
     data = np.frombuffer(b"".join(frames), dtype=np.uint8)
     buf = np.zeros(sum(mjpeg.scan_record_bound(mw, mh, x) for x in lens), dtype=np.uint8)
-    size, scan_offs = mjpeg.pack_scans(data, offs, lens, buf)
+    size, scan_offs = mjpeg.pack_scans(data, offs, lens, buf, sampling=SAMPLING)
     scans = torch.from_numpy(buf[:size]).to(dev)
     offs_dev = torch.from_numpy(scan_offs).to(dev)
     rec = torch.empty(n * rb, dtype=torch.uint8, device=dev)
     status = torch.zeros(n, dtype=torch.int32, device=dev)
-    surf = torch.empty(n * 384 * mw * mh, dtype=torch.uint8, device=dev)
+    surf = torch.empty(n * vops.jpeg_frame_bytes(mw, mh, SAMPLING)[1], dtype=torch.uint8,
+                       device=dev)
 
     def huff():
-        vops.jpeg_huff(scans, scan_offs, n, mw, mh, out=rec, status=status, offs_dev=offs_dev)
+        vops.jpeg_huff(scans, scan_offs, n, mw, mh, out=rec, status=status, offs_dev=offs_dev,
+                       sampling=SAMPLING)
 
     def idct():
-        vops.jpeg_idct(rec, n, mw, mh, out=surf)
+        vops.jpeg_idct(rec, n, mw, mh, out=surf, sampling=SAMPLING)
     sync_rounds = torch.zeros(n, dtype=torch.int32, device=dev)
 
     def huff_subseq(size):
         def run():
             vops.jpeg_huff(scans, scan_offs, n, mw, mh, out=rec, status=status, offs_dev=offs_dev,
-                           subseq_bytes=size, rounds=sync_rounds)
+                           subseq_bytes=size, rounds=sync_rounds, sampling=SAMPLING)
         return run
     reps = max(10, reps // 10)                            # a millisecond-scale kernel
     fns = (("jpeg_huff_kernel", huff), ("jpeg_idct_kernel", idct)) + tuple(
         ("jpeg_huff_subseq S=%d" % sub, huff_subseq(sub)) for sub in subseq if sub)
     want = np.empty(n * rb, dtype=np.uint8)
-    mjpeg.entropy_decode(data, offs, lens, want, rb, 4)
+    mjpeg.entropy_decode(data, offs, lens, want, rb, 4, sampling=SAMPLING)
     shape = {}
     for name, fn in fns:
         if fn is not idct:
@@ -132,45 +139,47 @@ def huff_kernel(dev, encoded, reps, rounds, lines, subseq=()):
     t = []
     for _ in range(20):
         t0 = time.perf_counter()
-        mjpeg.pack_scans(data, offs, lens, buf)
+        mjpeg.pack_scans(data, offs, lens, buf, sampling=SAMPLING)
         t.append((time.perf_counter() - t0) * 1e3)
     lines.append("scan packer alone: median %.3f ms per %d frames (min %.3f), one thread"
                  % (statistics.median(t), n, min(t)))
 
 
 def kernels(dev, dtype, encoded, reps, rounds, lines, filter="bilinear"):
-    mw, mh, rb = mjpeg.geometry(W, H)
+    mw, mh, rb = mjpeg.geometry(W, H, SAMPLING)
     n = CLIPS * F
     qt = mjpeg.quality_tables(75)[[0, 1, 1]]
     rec = torch.from_numpy(np.concatenate(
         [mjpeg.pack_record(encoded[i % DISTINCT][1], qt) for i in range(n)])).to(dev)
-    fb = 384 * mw * mh
+    fb = vops.jpeg_frame_bytes(mw, mh, SAMPLING)[1]
     surf = torch.empty(n * fb, dtype=torch.uint8, device=dev)
     C = 4 if dtype == torch.float32 else 8
     out = torch.empty((CLIPS, F, 112, 112, C), dtype=dtype, device=dev)
     offs = [c * F * fb for c in range(CLIPS)]
-    planes = vops.jpeg_surface_planes(mw, mh)
+    planes = vops.jpeg_surface_planes(mw, mh, SAMPLING)
     moved = rec.numel() + surf.numel()
     src, dst = (torch.empty(moved // 2, dtype=torch.uint8, device=dev) for _ in range(2))
 
     def idct():
-        vops.jpeg_idct(rec, n, mw, mh, out=surf)
+        vops.jpeg_idct(rec, n, mw, mh, out=surf, sampling=SAMPLING)
 
     def copy():
         dst.copy_(src)
 
     def jfif():
-        vops.yuv420_to_clip(surf, offs, F, W, H, fb, planes, dtype=dtype, out=out, matrix="jfif")
+        vops.yuv420_to_clip(surf, offs, F, W, H, fb, planes, dtype=dtype, out=out, matrix="jfif",
+                            sampling=SAMPLING)
 
     def bt601():
-        vops.yuv420_to_clip(surf, offs, F, W, H, fb, planes, dtype=dtype, out=out)
+        vops.yuv420_to_clip(surf, offs, F, W, H, fb, planes, dtype=dtype, out=out,
+                            sampling=SAMPLING)
     fns = (("jpeg_idct_kernel", idct, moved), ("device copy, same bytes", copy, moved),
            ("yuv420_clip_kernel jfif", jfif, n * fb + out.numel() * out.element_size()),
            ("yuv420_clip_kernel bt601", bt601, n * fb + out.numel() * out.element_size()))
     if filter == "antialias":
         def jfif_aa():
             vops.yuv420_to_clip(surf, offs, F, W, H, fb, planes, dtype=dtype, out=out,
-                                matrix="jfif", filter="antialias")
+                                matrix="jfif", filter="antialias", sampling=SAMPLING)
         fns += (("yuv420_clip_aa_kernel jfif", jfif_aa,
                  n * fb + out.numel() * out.element_size()),)
     for _, fn, _ in fns:
@@ -253,7 +262,7 @@ def host(dev, dtype, encoded, reqs, lines, sustained=60, entropy="host", restart
             for _ in range(max(3, reqs // 4)):
                 t0 = time.perf_counter()
                 mjpeg.entropy_decode(data, idx.offsets[sel], idx.lengths[sel], rec,
-                                     idx.record_bytes, threads)
+                                     idx.record_bytes, threads, sampling=idx.sampling)
                 t.append((time.perf_counter() - t0) * 1e3)
             lines.append("entropy decode alone, %2d threads: median %.2f ms per %d frames "
                          "(min %.2f)" % (threads, statistics.median(t), len(sel), min(t)))
@@ -282,13 +291,17 @@ def main():
     ap.add_argument("--filter", choices=vops.FILTERS, default="bilinear",
                     help="antialias: also time yuv420_clip_aa_kernel, and decode with "
                          "MjpegDecoder(filter='antialias')")
+    ap.add_argument("--sampling", choices=mjpeg.SAMPLINGS, default="420")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    global SAMPLING
+    SAMPLING = args.sampling
     if not torch.cuda.is_available():
         raise SystemExit("mjpeg_decode_bench: needs a GPU")
     dev = torch.device("cuda:0")
-    lines = ["mjpeg decode path, per 15-clip request at %dx%d -> 112x112%s (%s)"
-             % (W, H, ", filter antialias" if args.filter == "antialias" else "",
+    lines = ["mjpeg decode path, sampling %s, per 15-clip request at %dx%d -> 112x112%s (%s)"
+             % (":".join(SAMPLING), W, H,
+                ", filter antialias" if args.filter == "antialias" else "",
                 torch.cuda.get_device_name(0))]
     subseq = tuple(mjpeg.check_subseq_bytes(int(x), "--subseq-bytes")
                    for x in args.subseq_bytes.split(",") if x.strip())

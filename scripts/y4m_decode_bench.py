@@ -34,6 +34,15 @@ from rnb_amd.utils import y4m  # noqa: E402
 W, H, F, CLIPS = vops.SOURCE_W, vops.SOURCE_H, 8, 15
 
 
+SAMPLING = "420"       # --sampling: the chroma layout of the frames timed
+PLANES = {"420": vops.i420_planes, "422": vops.i422_planes, "444": vops.i444_planes}
+
+
+def chroma_shape(w, h):
+    hs, vs = y4m.SAMPLING_FACTORS[SAMPLING]
+    return h // vs, w // hs
+
+
 def event_ms(fn, reps):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -86,21 +95,22 @@ def kernels(dev, dtype, reps, rounds, lines):
 
 def kernels_antialias(dev, dtype, reps, rounds, lines, w, h, clips):
     """``yuv420_clip_aa_kernel`` next to ``yuv420_clip_kernel`` on ``clips``
-    clips of random ``w`` x ``h`` I420 frames behind FRAME markers."""
+    clips of random ``w`` x ``h`` planar frames of ``SAMPLING`` behind FRAME markers."""
     rng = np.random.default_rng(0)
-    stride = 6 + vops.nv12_frame_bytes(w, h)
+    stride = 6 + y4m.payload_bytes(w, h, SAMPLING)
     buf = torch.from_numpy(rng.integers(0, 256, clips * F * stride, dtype=np.uint8)).to(dev)
     offs = [c * F * stride for c in range(clips)]
     C = 4 if dtype == torch.float32 else 8
     out = torch.empty((clips, F, 112, 112, C), dtype=dtype, device=dev)
-    planes = vops.i420_planes(w, h, 6)
+    planes = PLANES[SAMPLING](w, h, 6)
 
     def antialias():
         vops.yuv420_to_clip(buf, offs, F, w, h, stride, planes, dtype=dtype, out=out,
-                            filter="antialias")
+                            filter="antialias", sampling=SAMPLING)
 
     def bilinear():
-        vops.yuv420_to_clip(buf, offs, F, w, h, stride, planes, dtype=dtype, out=out)
+        vops.yuv420_to_clip(buf, offs, F, w, h, stride, planes, dtype=dtype, out=out,
+                            sampling=SAMPLING)
     for fn in (antialias, bilinear):
         event_ms(fn, reps)                                # warm
     t_aa, t_bil = [], []
@@ -129,9 +139,9 @@ def host_antialias(dev, dtype, reqs, lines, w, h, clips):
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "v.y4m")
         y4m.write_y4m(path, [(rng.integers(0, 256, (h, w), dtype=np.uint8),
-                              rng.integers(0, 256, (h // 2, w // 2), dtype=np.uint8),
-                              rng.integers(0, 256, (h // 2, w // 2), dtype=np.uint8))
-                             for _ in range(frames)])
+                              rng.integers(0, 256, chroma_shape(w, h), dtype=np.uint8),
+                              rng.integers(0, 256, chroma_shape(w, h), dtype=np.uint8))
+                             for _ in range(frames)], sampling=SAMPLING)
         with open(path, "rb") as fp:                       # warm the page cache
             while fp.read(1 << 24):
                 pass
@@ -164,9 +174,9 @@ def host(dev, dtype, reqs, lines):
     with tempfile.TemporaryDirectory() as d:
         py, pn = os.path.join(d, "v.y4m"), os.path.join(d, "v.npy")
         y4m.write_y4m(py, [(rng.integers(0, 256, (H, W), dtype=np.uint8),
-                            rng.integers(0, 256, (H // 2, W // 2), dtype=np.uint8),
-                            rng.integers(0, 256, (H // 2, W // 2), dtype=np.uint8))
-                           for _ in range(frames)])
+                            rng.integers(0, 256, chroma_shape(W, H), dtype=np.uint8),
+                            rng.integers(0, 256, chroma_shape(W, H), dtype=np.uint8))
+                           for _ in range(frames)], sampling=SAMPLING)
         np.save(pn, rng.integers(0, 256, (frames, 112, 112, 3), dtype=np.uint8))
         for p in (py, pn):
             with open(p, "rb") as fp:                      # warm the page cache
@@ -204,23 +214,32 @@ def main():
     ap.add_argument("--size", default="%dx%d" % (W, H),
                     help="with --filter antialias: source WxH (even)")
     ap.add_argument("--clips", type=int, default=CLIPS, help="with --filter antialias")
+    ap.add_argument("--sampling", choices=tuple(PLANES), default="420",
+                    help="422 / 444: the clip kernels (both filters) and Y4mDecoder on C422 / "
+                         "C444 frames")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    global SAMPLING
+    SAMPLING = args.sampling
     if not torch.cuda.is_available():
         raise SystemExit("y4m_decode_bench: needs a GPU")
     dev = torch.device("cuda:0")
     if args.filter == "antialias":
         w, h = (int(x) for x in args.size.lower().split("x"))
-        lines = ["y4m decode path, filter antialias, per %d-clip request at %dx%d -> 112x112 (%s)"
-                 % (args.clips, w, h, torch.cuda.get_device_name(0))]
+        lines = ["y4m decode path, sampling %s, filter antialias, per %d-clip request at %dx%d -> "
+                 "112x112 (%s)" % (":".join(SAMPLING), args.clips, w, h,
+                                   torch.cuda.get_device_name(0))]
         for dtype in (torch.float32, torch.bfloat16):
             kernels_antialias(dev, dtype, args.reps, args.rounds, lines, w, h, args.clips)
         host_antialias(dev, torch.float32, args.requests, lines, w, h, args.clips)
     else:
-        lines = ["y4m decode path, per 15-clip request at %dx%d -> 112x112 (%s)"
-                 % (W, H, torch.cuda.get_device_name(0))]
+        lines = ["y4m decode path, sampling %s, per 15-clip request at %dx%d -> 112x112 (%s)"
+                 % (":".join(SAMPLING), W, H, torch.cuda.get_device_name(0))]
         for dtype in (torch.float32, torch.bfloat16):
-            kernels(dev, dtype, args.reps, args.rounds, lines)
+            if SAMPLING == "420":
+                kernels(dev, dtype, args.reps, args.rounds, lines)
+            else:                       # no NV12 twin to compare with: both filters' kernels
+                kernels_antialias(dev, dtype, args.reps, args.rounds, lines, W, H, CLIPS)
         host(dev, torch.float32, args.requests, lines)
     text = "\n".join(lines) + "\n"
     print(text, end="")
