@@ -13,6 +13,9 @@
 //  * rnb_yuv420_to_clip_aa
 //                        the same with the antialiased triangle filter
 //                        (separable through LDS) for downscaled real frames.
+//  * rnb_yuv_to_clip_boxes
+//                        both filters with a crop box per row, so that several
+//                        views of one clip read one uploaded span.
 //  * rnb_stem_pack       NDHWC8 -> zero-bordered pixel-pair-packed layout of
 //                        the stem conv (ops/conv.StemConv).
 //  * rnb_preprocess_packed  rnb_preprocess + rnb_stem_pack in one pass: uint8
@@ -256,6 +259,43 @@ struct Yuv420ClipArgs {
   long long offs[YUV420_MAX_CLIPS];        // per-clip base (FROM_ARRAY: unused)
 };
 
+// The boxed form (PER_CLIP_BOX) of the two clip kernels: row c of the launch
+// reads the frames at offs[c] through its own crop box, so several views of one
+// clip share one uploaded span (rows may repeat an offset). Up to
+// YUV_BOX_MAX_ROWS rows travel in the kernel arguments, offset (8 B) next to box
+// (16 B, one s_load_dwordx4): 1536 B of tables, 1664 B in all, under the 4 KB
+// of a dispatch packet's argument segment. 64, not 32, because a 15-clip request
+// with three views is 45 rows. More rows read both tables from device memory
+// (offs, boxes_dev). g.crop_* are unused.
+#define YUV_BOX_MAX_ROWS 64
+struct __attribute__((aligned(16))) YuvBox {
+  float x, y, w, h;                        // luma pixels, as Nv12ClipArgs.crop_*
+};
+struct Yuv420BoxArgs {
+  Nv12ClipArgs g;
+  int F, y_stride, u_stride, v_stride, c_step;
+  long long frame_stride, y_off, u_off, v_off;
+  const YuvBox* boxes_dev;                 // FROM_ARRAY: per-row boxes (else unused)
+  long long offs[YUV_BOX_MAX_ROWS];        // per-row base (FROM_ARRAY: unused)
+  YuvBox boxes[YUV_BOX_MAX_ROWS];          // per-row box (FROM_ARRAY: unused)
+};
+static_assert(sizeof(Yuv420BoxArgs) <= 2048, "boxed clip arguments outgrew their budget");
+
+template <bool PER_CLIP_BOX>
+struct YuvClipArgsOf { typedef Yuv420ClipArgs type; };
+template <>
+struct YuvClipArgsOf<true> { typedef Yuv420BoxArgs type; };
+
+// the crop box of block row `clip`: the launch's one box, or the row's own (a
+// uniform address either way: scalar loads). `a` is the kernel's own argument.
+#define YUV_CLIP_BOX(box, a, clip)                                              \
+  YuvBox box;                                                                   \
+  if constexpr (PER_CLIP_BOX) {                                                 \
+    box = FROM_ARRAY ? a.boxes_dev[clip] : a.boxes[clip];                       \
+  } else {                                                                      \
+    box.x = a.g.crop_x; box.y = a.g.crop_y; box.w = a.g.crop_w; box.h = a.g.crop_h; \
+  }
+
 // JFIF: full-range JFIF YCbCr (what JPEG frames hold) instead of the video-range
 // BT.601 matrix; the chroma planes of an odd-sized frame then round up.
 // HS, VS: the luma sampling factors per axis, 2x2 (4:2:0), 2x1 (4:2:2) or 1x1
@@ -296,11 +336,10 @@ static __device__ __forceinline__ float bilinear_fetch(const uint8_t* __restrict
   return top + (bot - top) * t.fy;
 }
 
-template <bool FROM_ARRAY, bool JFIF, int HS = 2, int VS = 2>
-__global__ __launch_bounds__(256) void yuv420_clip_kernel(const uint8_t* __restrict__ buf,
-                                                          const long long* __restrict__ offs,
-                                                          void* __restrict__ out,
-                                                          Yuv420ClipArgs a) {
+template <bool FROM_ARRAY, bool JFIF, int HS = 2, int VS = 2, bool PER_CLIP_BOX = false>
+__global__ __launch_bounds__(256) void yuv420_clip_kernel(
+    const uint8_t* __restrict__ buf, const long long* __restrict__ offs, void* __restrict__ out,
+    typename YuvClipArgsOf<PER_CLIP_BOX>::type a) {
   // grid = (pixel blocks of one frame, F, nclips): frame and clip are uniform
   // per block, so the base offset is one scalar load and no thread divides a
   // 64-bit pixel index (the cost of a flat grid: two such divisions per pixel)
@@ -311,9 +350,10 @@ __global__ __launch_bounds__(256) void yuv420_clip_kernel(const uint8_t* __restr
   const long long i = ((long long)clip * a.F + f) * ohw + p;
   const int oy = p / a.g.out_w, ox = p - oy * a.g.out_w;
   const uint8_t* fr = buf + (FROM_ARRAY ? offs[clip] : a.offs[clip]) + f * a.frame_stride;
+  YUV_CLIP_BOX(box, a, clip)
   // the arithmetic below is nv12_clip_kernel's, expression for expression
-  const float sx = a.g.crop_x + ((float)ox + 0.5f) * (a.g.crop_w / (float)a.g.out_w) - 0.5f;
-  const float sy = a.g.crop_y + ((float)oy + 0.5f) * (a.g.crop_h / (float)a.g.out_h) - 0.5f;
+  const float sx = box.x + ((float)ox + 0.5f) * (box.w / (float)a.g.out_w) - 0.5f;
+  const float sy = box.y + ((float)oy + 0.5f) * (box.h / (float)a.g.out_h) - 0.5f;
   float yv, u, v;
   if constexpr (HS == 1 && VS == 1) {
     const BilinearTaps t = bilinear_taps(a.g.src_w, a.g.src_h, sx, sy);
@@ -449,11 +489,10 @@ static __device__ __forceinline__ void aa_plane(const uint8_t* __restrict__ plan
   for (int k = 0; k < AA_PX; ++k) res[k] = wsum[k] > 0.f ? acc[k] / wsum[k] : 0.f;
 }
 
-template <bool FROM_ARRAY, bool JFIF, int HS = 2, int VS = 2>
-__global__ __launch_bounds__(256) void yuv420_clip_aa_kernel(const uint8_t* __restrict__ buf,
-                                                             const long long* __restrict__ offs,
-                                                             void* __restrict__ out,
-                                                             Yuv420ClipArgs a) {
+template <bool FROM_ARRAY, bool JFIF, int HS = 2, int VS = 2, bool PER_CLIP_BOX = false>
+__global__ __launch_bounds__(256) void yuv420_clip_aa_kernel(
+    const uint8_t* __restrict__ buf, const long long* __restrict__ offs, void* __restrict__ out,
+    typename YuvClipArgsOf<PER_CLIP_BOX>::type a) {
   // grid = (column tiles x row bands of one frame, F, nclips): frame and clip are
   // uniform per block, as in yuv420_clip_kernel
   __shared__ float rows_lds[AA_CH * AA_TW];
@@ -473,15 +512,16 @@ __global__ __launch_bounds__(256) void yuv420_clip_aa_kernel(const uint8_t* __re
     oy[k] = r < th ? oy0 + r : -1;
   }
   const int cw = chroma_dim<HS>(a.g.src_w, JFIF), ch = chroma_dim<VS>(a.g.src_h, JFIF);
+  YUV_CLIP_BOX(box, a, clip)
   float yv[AA_PX], u[AA_PX], v[AA_PX];
-  aa_plane(fr + a.y_off, a.g.src_w, a.g.src_h, a.y_stride, 1, a.g.crop_x, a.g.crop_y,
-           a.g.crop_w, a.g.crop_h, a.g.out_w, a.g.out_h, x0, tw, oy0, th, cx, oy, rows_lds, yv);
+  aa_plane(fr + a.y_off, a.g.src_w, a.g.src_h, a.y_stride, 1, box.x, box.y,
+           box.w, box.h, a.g.out_w, a.g.out_h, x0, tw, oy0, th, cx, oy, rows_lds, yv);
   // chroma sample j sits at luma 2 j + 0.5 along a subsampled axis: the chroma
   // box is the luma box / (HS, VS)
-  const float hx = HS == 2 ? a.g.crop_x * 0.5f : a.g.crop_x;
-  const float hy = VS == 2 ? a.g.crop_y * 0.5f : a.g.crop_y;
-  const float hw = HS == 2 ? a.g.crop_w * 0.5f : a.g.crop_w;
-  const float hh = VS == 2 ? a.g.crop_h * 0.5f : a.g.crop_h;
+  const float hx = HS == 2 ? box.x * 0.5f : box.x;
+  const float hy = VS == 2 ? box.y * 0.5f : box.y;
+  const float hw = HS == 2 ? box.w * 0.5f : box.w;
+  const float hh = VS == 2 ? box.h * 0.5f : box.h;
   aa_plane(fr + a.u_off, cw, ch, a.u_stride, a.c_step, hx, hy, hw, hh, a.g.out_w, a.g.out_h,
            x0, tw, oy0, th, cx, oy, rows_lds, u);
   aa_plane(fr + a.v_off, cw, ch, a.v_stride, a.c_step, hx, hy, hw, hh, a.g.out_w, a.g.out_h,
@@ -816,6 +856,43 @@ static void yuv_clip_run_sampling(int sampling, bool aa, dim3 grid, hipStream_t 
   else yuv_clip_run<FROM_ARRAY, JFIF, 1, 1>(aa, grid, stream, buf, table, out, a);
 }
 
+// the same choice among the boxed (PER_CLIP_BOX) instantiations
+template <bool FROM_ARRAY, bool JFIF, int HS, int VS>
+static void yuv_box_run(bool aa, dim3 grid, hipStream_t stream, const uint8_t* buf,
+                        const long long* table, void* out, const Yuv420BoxArgs& a) {
+  if (aa)
+    hipLaunchKernelGGL((yuv420_clip_aa_kernel<FROM_ARRAY, JFIF, HS, VS, true>), grid, dim3(256),
+                       0, stream, buf, table, out, a);
+  else
+    hipLaunchKernelGGL((yuv420_clip_kernel<FROM_ARRAY, JFIF, HS, VS, true>), grid, dim3(256), 0,
+                       stream, buf, table, out, a);
+}
+
+template <bool FROM_ARRAY, bool JFIF>
+static void yuv_box_run_sampling(int sampling, bool aa, dim3 grid, hipStream_t stream,
+                                 const uint8_t* buf, const long long* table, void* out,
+                                 const Yuv420BoxArgs& a) {
+  if (sampling == 0) yuv_box_run<FROM_ARRAY, JFIF, 2, 2>(aa, grid, stream, buf, table, out, a);
+  else if (sampling == 1) yuv_box_run<FROM_ARRAY, JFIF, 2, 1>(aa, grid, stream, buf, table, out, a);
+  else yuv_box_run<FROM_ARRAY, JFIF, 1, 1>(aa, grid, stream, buf, table, out, a);
+}
+
+// the fields Yuv420ClipArgs and Yuv420BoxArgs share
+template <typename Args>
+static void yuv_clip_fill(Args& a, int F, int src_w, int src_h, long long frame_stride,
+                          const long long* plane_off, const int* plane_stride, int c_step,
+                          int out_w, int out_h, const float* mean, const float* stdv, int bf16) {
+  a.g.src_w = src_w; a.g.src_h = src_h; a.g.out_w = out_w; a.g.out_h = out_h;
+  for (int c = 0; c < 3; ++c) {
+    a.g.scale[c] = 1.0f / (255.0f * stdv[c]);
+    a.g.shift[c] = -mean[c] / stdv[c];
+  }
+  a.g.bf16 = bf16;
+  a.F = F; a.c_step = c_step; a.frame_stride = frame_stride;
+  a.y_off = plane_off[0]; a.u_off = plane_off[1]; a.v_off = plane_off[2];
+  a.y_stride = plane_stride[0]; a.u_stride = plane_stride[1]; a.v_stride = plane_stride[2];
+}
+
 extern "C" {
 
 int rnb_clipgen_u8(void* out, const int* vids, const int* starts, int nclips, int F, int H,
@@ -898,6 +975,52 @@ int rnb_nv12_to_clip(const void* nv12, void* out, long long frames, int src_w, i
   return (int)hipGetLastError();
 }
 
+// everything the clip launchers check but the crop boxes (0: fine). tables_ok:
+// the rows fit the kernel arguments, or their tables are in device memory.
+static int yuv_clip_check(long long buf_len, const long long* offs, int nclips, bool tables_ok,
+                          int F, int src_w, int src_h, long long frame_stride,
+                          const long long* plane_off, const int* plane_stride, int c_step,
+                          const void* out, int out_w, int out_h, int matrix, int filter,
+                          int sampling) {
+  if (matrix != 0 && matrix != 1) return -2;
+  if (sampling < 0 || sampling > 2) return -2;
+  const int hs = sampling == 2 ? 1 : 2, vs = sampling == 0 ? 2 : 1;
+  if (F <= 0 || src_w < 1 || src_h < 1 || out_w <= 0 || out_h <= 0) return -2;
+  if (matrix == 0 && ((hs == 2 && src_w % 2) || (vs == 2 && src_h % 2))) return -2;
+  if (((uintptr_t)out & 15u) != 0 || (c_step != 1 && c_step != 2)) return -2;
+  if (!tables_ok) return -3;
+  // every byte nv12_sample can touch lies inside its frame (int indexing there)
+  if (frame_stride <= 0 || frame_stride > 0x7FFFFFFFLL) return -4;
+  const int cw = hs == 2 ? (src_w + matrix) / 2 : src_w;
+  const int ch = vs == 2 ? (src_h + matrix) / 2 : src_h;
+  for (int p = 0; p < 3; ++p) {
+    if (plane_off[p] < 0 || plane_stride[p] <= 0) return -4;
+    const long long row = p == 0 ? src_w : (long long)(cw - 1) * c_step + 1;
+    const long long rows = p == 0 ? src_h : ch;
+    if (plane_off[p] + (rows - 1) * plane_stride[p] + row > frame_stride) return -4;
+  }
+  for (int c = 0; c < nclips; ++c)
+    if (offs[c] < 0 || offs[c] + (long long)F * frame_stride > buf_len) return -4;
+  const long long ohw = (long long)out_w * out_h;
+  if (ohw > 0x7FFFFF00LL || F > 65535 || nclips > 65535) return -2;    // grid limits
+  const long long tiles = (long long)((out_w + AA_TW - 1) / AA_TW) * ((out_h + AA_TH - 1) / AA_TH);
+  if (filter && tiles > 0x7FFFFFFFLL) return -2;
+  return 0;
+}
+
+// the antialias kernel's condition on a crop box: inside [0, src_w] x [0, src_h],
+// summed in double (no row of weights can then be empty)
+static bool yuv_clip_box_inside(const float* b, int src_w, int src_h) {
+  return b[0] >= 0.f && b[1] >= 0.f && b[2] > 0.f && b[3] > 0.f &&
+         (double)b[0] + b[2] <= src_w && (double)b[1] + b[3] <= src_h;
+}
+
+static dim3 yuv_clip_grid(int filter, int out_w, int out_h, int F, int nclips) {
+  const long long ohw = (long long)out_w * out_h;
+  const long long tiles = (long long)((out_w + AA_TW - 1) / AA_TW) * ((out_h + AA_TH - 1) / AA_TH);
+  return dim3((unsigned)(filter ? tiles : (ohw + 255) / 256), (unsigned)F, (unsigned)nclips);
+}
+
 // buf: buf_len uploaded bytes; clip c's F frames start at offs[c] (host copy,
 // checked here) and are frame_stride bytes apart; plane_off / plane_stride:
 // byte offset within a frame and row stride of Y, U, V; c_step: bytes between
@@ -920,47 +1043,19 @@ static int yuv420_to_clip_launch(const void* buf, long long buf_len, const long 
                                  const float* stdv, int bf16, int matrix, int filter,
                                  int sampling, hipStream_t stream) {
   if (nclips <= 0) return 0;
-  if (matrix != 0 && matrix != 1) return -2;
-  if (sampling < 0 || sampling > 2) return -2;
-  const int hs = sampling == 2 ? 1 : 2, vs = sampling == 0 ? 2 : 1;
-  if (F <= 0 || src_w < 1 || src_h < 1 || out_w <= 0 || out_h <= 0) return -2;
-  if (matrix == 0 && ((hs == 2 && src_w % 2) || (vs == 2 && src_h % 2))) return -2;
-  if (((uintptr_t)out & 15u) != 0 || (c_step != 1 && c_step != 2)) return -2;
-  if (nclips > YUV420_MAX_CLIPS && !offs_dev) return -3;
-  // every byte nv12_sample can touch lies inside its frame (int indexing there)
-  if (frame_stride <= 0 || frame_stride > 0x7FFFFFFFLL) return -4;
-  const int cw = hs == 2 ? (src_w + matrix) / 2 : src_w;
-  const int ch = vs == 2 ? (src_h + matrix) / 2 : src_h;
-  for (int p = 0; p < 3; ++p) {
-    if (plane_off[p] < 0 || plane_stride[p] <= 0) return -4;
-    const long long row = p == 0 ? src_w : (long long)(cw - 1) * c_step + 1;
-    const long long rows = p == 0 ? src_h : ch;
-    if (plane_off[p] + (rows - 1) * plane_stride[p] + row > frame_stride) return -4;
-  }
-  for (int c = 0; c < nclips; ++c)
-    if (offs[c] < 0 || offs[c] + (long long)F * frame_stride > buf_len) return -4;
-  const long long ohw = (long long)out_w * out_h;
-  if (ohw > 0x7FFFFF00LL || F > 65535 || nclips > 65535) return -2;    // grid limits
-  if (filter && !(crop[0] >= 0.f && crop[1] >= 0.f && crop[2] > 0.f && crop[3] > 0.f &&
-                   (double)crop[0] + crop[2] <= src_w && (double)crop[1] + crop[3] <= src_h))
-    return -5;
+  const int rc = yuv_clip_check(buf_len, offs, nclips, nclips <= YUV420_MAX_CLIPS || offs_dev, F,
+                                src_w, src_h, frame_stride, plane_off, plane_stride, c_step, out,
+                                out_w, out_h, matrix, filter, sampling);
+  if (rc) return rc;
+  if (filter && !yuv_clip_box_inside(crop, src_w, src_h)) return -5;
   Yuv420ClipArgs a;
-  a.g.src_w = src_w; a.g.src_h = src_h; a.g.out_w = out_w; a.g.out_h = out_h;
+  yuv_clip_fill(a, F, src_w, src_h, frame_stride, plane_off, plane_stride, c_step, out_w, out_h,
+                mean, stdv, bf16);
   a.g.crop_x = crop[0]; a.g.crop_y = crop[1]; a.g.crop_w = crop[2]; a.g.crop_h = crop[3];
-  for (int c = 0; c < 3; ++c) {
-    a.g.scale[c] = 1.0f / (255.0f * stdv[c]);
-    a.g.shift[c] = -mean[c] / stdv[c];
-  }
-  a.g.bf16 = bf16;
-  a.F = F; a.c_step = c_step; a.frame_stride = frame_stride;
-  a.y_off = plane_off[0]; a.u_off = plane_off[1]; a.v_off = plane_off[2];
-  a.y_stride = plane_stride[0]; a.u_stride = plane_stride[1]; a.v_stride = plane_stride[2];
   const bool in_args = nclips <= YUV420_MAX_CLIPS;
   for (int c = 0; c < YUV420_MAX_CLIPS; ++c) a.offs[c] = in_args && c < nclips ? offs[c] : 0;
   const long long* table = in_args ? (const long long*)nullptr : (const long long*)offs_dev;
-  const long long tiles = (long long)((out_w + AA_TW - 1) / AA_TW) * ((out_h + AA_TH - 1) / AA_TH);
-  if (filter && tiles > 0x7FFFFFFFLL) return -2;
-  const dim3 grid((unsigned)(filter ? tiles : (ohw + 255) / 256), (unsigned)F, (unsigned)nclips);
+  const dim3 grid = yuv_clip_grid(filter, out_w, out_h, F, nclips);
   const uint8_t* src = (const uint8_t*)buf;
   const bool aa = filter != 0;
   if (in_args) {
@@ -1010,6 +1105,58 @@ int rnb_yuv_to_clip(const void* buf, long long buf_len, const long long* offs,
   return yuv420_to_clip_launch(buf, buf_len, offs, offs_dev, nclips, F, src_w, src_h,
                                frame_stride, plane_off, plane_stride, c_step, out, out_w, out_h,
                                crop, mean, stdv, bf16, matrix, filter, sampling, stream);
+}
+
+// rnb_yuv_to_clip with a crop box per row: row c reads the F frames at offs[c]
+// through boxes[c] = (x, y, w, h), so the views of one clip share its uploaded
+// span (rows may repeat an offset, in any order). The checks are
+// yuv420_to_clip_launch's, per row. Up to YUV_BOX_MAX_ROWS rows travel in the
+// kernel arguments; more need offs_dev AND boxes_dev, both tables in device
+// memory (-3 otherwise). filter 1: every box inside [0, src_w] x [0, src_h], else
+// -5 and nothing is launched; the bilinear filter takes any box.
+int rnb_yuv_to_clip_boxes(const void* buf, long long buf_len, const long long* offs,
+                          const void* offs_dev, int nclips, int F, int src_w, int src_h,
+                          long long frame_stride, const long long* plane_off,
+                          const int* plane_stride, int c_step, void* out, int out_w, int out_h,
+                          const float* boxes, const void* boxes_dev, const float* mean,
+                          const float* stdv, int bf16, int matrix, int filter, int sampling,
+                          hipStream_t stream) {
+  if (nclips <= 0) return 0;
+  if (filter != 0 && filter != 1) return -2;
+  const bool in_args = nclips <= YUV_BOX_MAX_ROWS;
+  const int rc = yuv_clip_check(buf_len, offs, nclips, in_args || (offs_dev && boxes_dev), F,
+                                src_w, src_h, frame_stride, plane_off, plane_stride, c_step, out,
+                                out_w, out_h, matrix, filter, sampling);
+  if (rc) return rc;
+  if (((uintptr_t)boxes_dev & 15u) != 0) return -2;         // 16-byte box loads
+  if (filter)
+    for (int c = 0; c < nclips; ++c)
+      if (!yuv_clip_box_inside(boxes + 4 * c, src_w, src_h)) return -5;
+  Yuv420BoxArgs a;
+  yuv_clip_fill(a, F, src_w, src_h, frame_stride, plane_off, plane_stride, c_step, out_w, out_h,
+                mean, stdv, bf16);
+  a.g.crop_x = a.g.crop_y = a.g.crop_w = a.g.crop_h = 0.f;
+  a.boxes_dev = in_args ? (const YuvBox*)nullptr : (const YuvBox*)boxes_dev;
+  for (int c = 0; c < YUV_BOX_MAX_ROWS; ++c) {
+    const bool live = in_args && c < nclips;
+    a.offs[c] = live ? offs[c] : 0;
+    a.boxes[c].x = live ? boxes[4 * c] : 0.f;
+    a.boxes[c].y = live ? boxes[4 * c + 1] : 0.f;
+    a.boxes[c].w = live ? boxes[4 * c + 2] : 0.f;
+    a.boxes[c].h = live ? boxes[4 * c + 3] : 0.f;
+  }
+  const long long* table = in_args ? (const long long*)nullptr : (const long long*)offs_dev;
+  const dim3 grid = yuv_clip_grid(filter, out_w, out_h, F, nclips);
+  const uint8_t* src = (const uint8_t*)buf;
+  const bool aa = filter != 0;
+  if (in_args) {
+    if (matrix) yuv_box_run_sampling<false, true>(sampling, aa, grid, stream, src, table, out, a);
+    else yuv_box_run_sampling<false, false>(sampling, aa, grid, stream, src, table, out, a);
+  } else {
+    if (matrix) yuv_box_run_sampling<true, true>(sampling, aa, grid, stream, src, table, out, a);
+    else yuv_box_run_sampling<true, false>(sampling, aa, grid, stream, src, table, out, a);
+  }
+  return (int)hipGetLastError();
 }
 
 int rnb_preprocess(const void* in, void* out, long long npix, const float* mean,

@@ -25,7 +25,9 @@ Every decoder returns NDHWC clips normalised with the Kinetics mean/std:
 """
 from __future__ import annotations
 
+import math
 import mmap
+import numbers
 import os
 from collections import OrderedDict
 from typing import List, Optional, Sequence, Tuple
@@ -40,6 +42,7 @@ from ...video_path_provider import parse_synthetic_path
 
 class Decoder:
     dtype = torch.bfloat16
+    views = 1                # output rows per clip (file-backed decoders: crop={"views": 3})
 
     def probe(self, path: str) -> Tuple[int, int]:
         """(video id, number of frames)."""
@@ -181,10 +184,65 @@ class _UploadEntry:
             self.in_flight = False
 
 
+def _f32_towards(x: float, up: bool) -> float:
+    """The nearest fp32 value that is >= ``x`` (``up``) or <= ``x``."""
+    f = np.float32(x)
+    if (float(f) < x) if up else (float(f) > x):
+        f = np.nextafter(f, np.float32(np.inf if up else -np.inf))
+    return float(f)
+
+
+def view_boxes(W: int, H: int, out_w: int, out_h: int, short_side: float, views: int):
+    """The crop boxes (x, y, w, h) of ``views`` windows of a ``W`` x ``H`` frame
+    resized so that its short side is ``short_side``, each ``out_w`` x ``out_h``
+    after the resize; ``None`` if such a window is larger than the frame.
+
+    In source pixels a window is ``out * min(W, H) / short_side`` per axis. One
+    view is centred. Three lie along the axis with the larger free length (a tie
+    goes to x) at 0, 1/2 and 1 of it -- left / centre / right or top / centre /
+    bottom -- and are centred along the other. Every number is rounded to fp32
+    towards the interior of the box, so that the box the kernel gets (fp32) lies
+    inside the frame by the antialias launcher's own test (``x + w`` summed in
+    double against ``W``) whenever the exact box does."""
+    m = min(W, H)
+    bw, bh = out_w * m / short_side, out_h * m / short_side
+    if bw > W or bh > H:
+        return None
+    fx, fy = W - bw, H - bh
+    if views == 1:
+        at = [(fx / 2.0, fy / 2.0)]
+    elif fx >= fy:
+        at = [(t * fx, fy / 2.0) for t in (0.0, 0.5, 1.0)]
+    else:
+        at = [(fx / 2.0, t * fy) for t in (0.0, 0.5, 1.0)]
+
+    def axis(lo, size, n):
+        lo32 = _f32_towards(max(lo, 0.0), True)
+        size32 = _f32_towards(min(lo + size, float(n)) - lo32, False)
+        while lo32 + size32 > n:              # two fp32 values: their double sum is exact
+            size32 = float(np.nextafter(np.float32(size32), np.float32(-np.inf)))
+        return lo32, size32
+    boxes = []
+    for x, y in at:
+        (x32, w32), (y32, h32) = axis(x, bw, W), axis(y, bh, H)
+        boxes.append((x32, y32, w32, h32))
+    return boxes
+
+
 class _StagedFileDecoder(Decoder):
     """What the file-backed decoders that upload bytes share: an LRU of memory
-    maps, and a ring of ``depth`` pinned staging / device upload buffers
-    (``_UploadEntry``) ordered by HIP events."""
+    maps, a ring of ``depth`` pinned staging / device upload buffers
+    (``_UploadEntry``) ordered by HIP events, and the crop geometry.
+
+    ``crop``: ``"full"`` scales the whole frame to the output, ``"center"`` the
+    centred square of the short side. ``{"short_side": S, "views": V}`` is the
+    evaluation protocol of the R(2+1)D family: the frame is resized, aspect
+    kept, so that its short side is ``S`` (a positive number) and ``V`` windows
+    of the output size are taken from it, 1 (default; centred) or 3 (along the
+    long side: ``view_boxes``). ``decode`` then returns ``views`` = ``V`` rows
+    per clip, the views of a clip adjacent. All views of a clip read one staged
+    and uploaded span, in one launch (``yuv420_to_clip`` with a box per row). A
+    file whose frames are smaller than the window is refused at ``probe``."""
 
     WARMUP_W, WARMUP_H = vops.SOURCE_W, vops.SOURCE_H
     MAX_OPEN = 64            # memory maps kept open (least recently used first out)
@@ -193,8 +251,24 @@ class _StagedFileDecoder(Decoder):
                  width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full",
                  filter: str = "bilinear"):
         name = type(self).__name__
-        if crop not in ("full", "center"):
-            raise ValueError("%s: crop must be 'full' or 'center', got %r" % (name, crop))
+        self.views, self.short_side = 1, None
+        if isinstance(crop, dict):
+            unknown = sorted(set(crop) - {"short_side", "views"})
+            if unknown or "short_side" not in crop:
+                raise ValueError("%s: crop takes the keys 'short_side' and 'views', got %r"
+                                 % (name, sorted(crop)))
+            side, views = crop["short_side"], crop.get("views", 1)
+            if isinstance(side, bool) or not isinstance(side, numbers.Real) \
+                    or not (side > 0 and math.isfinite(side)):
+                raise ValueError("%s: crop 'short_side' must be a positive number, got %r"
+                                 % (name, side))
+            if isinstance(views, bool) or views not in (1, 3):
+                raise ValueError("%s: crop 'views' must be 1 or 3, got %r" % (name, views))
+            self.views, self.short_side = int(views), float(side)
+            crop = {"short_side": side, "views": int(views)}
+        elif crop not in ("full", "center"):
+            raise ValueError("%s: crop must be 'full', 'center' or {'short_side': S, "
+                             "'views': 1 or 3}, got %r" % (name, crop))
         if filter not in vops.FILTERS:
             raise ValueError("%s: filter must be one of %s, got %r"
                              % (name, vops.FILTERS, filter))
@@ -208,6 +282,7 @@ class _StagedFileDecoder(Decoder):
         self.filter = filter
         self._ids = {}
         self._videos = {}          # video id -> (path, header / index)
+        self._boxes = {}           # video id -> view boxes (crop={"short_side": ...})
         self._maps = OrderedDict()  # video id -> (mmap, uint8 view), LRU
         self._ring: List[_UploadEntry] = []
         self._ring_bytes = 0
@@ -232,6 +307,59 @@ class _StagedFileDecoder(Decoder):
             return None
         side = min(hdr.width, hdr.height)
         return ((hdr.width - side) / 2.0, (hdr.height - side) / 2.0, float(side), float(side))
+
+    def _probe_boxes(self, path: str, hdr):
+        """The view boxes of a file just probed (``None`` for the string crops);
+        ``ValueError`` naming file and field if the window does not fit."""
+        if self.short_side is None:
+            return None
+        boxes = view_boxes(hdr.width, hdr.height, self.W, self.H, self.short_side, self.views)
+        if boxes is None:
+            m = min(hdr.width, hdr.height)
+            raise ValueError("%s: a %d x %d frame resized to short side %g is smaller than the "
+                             "%d x %d window (field 'crop': short_side must be >= %g)"
+                             % (path, hdr.width, hdr.height, self.short_side, self.W, self.H,
+                                max(self.W * m / hdr.width, self.H * m / hdr.height)))
+        return boxes
+
+    def _rows(self, starts, views):
+        """``(clips, rows)`` of a request: the start frames to stage, each once,
+        and per output row (index into ``clips``, view). ``views=None``: every
+        view of every entry of ``starts``, clip-major. Else one view index per
+        entry of ``starts``: exactly those rows, equal starts sharing a clip."""
+        if views is None:
+            return list(starts), [(i, v) for i in range(len(starts)) for v in range(self.views)]
+        views = [int(v) for v in views]
+        if len(views) != len(starts):
+            raise ValueError("%s: %d view indices for %d clip starts"
+                             % (type(self).__name__, len(views), len(starts)))
+        if any(not 0 <= v < self.views for v in views):
+            raise ValueError("%s: view indices must be in 0..%d, got %r"
+                             % (type(self).__name__, self.views - 1, views))
+        clips, index, rows = [], {}, []
+        for s, v in zip(starts, views):
+            if s not in index:
+                index[s] = len(clips)
+                clips.append(s)
+            rows.append((index[s], v))
+        return clips, rows
+
+    def _clip_args(self, vid, hdr, rows, span: int):
+        """``yuv420_to_clip``'s (offsets, crop) for the output rows, clip ``c``
+        staged at byte ``c * span``: one box for every row, or a box per row."""
+        offsets = [c * span for c, _ in rows]
+        boxes = self._boxes.get(vid)
+        if boxes is None:
+            return offsets, self._crop_box(hdr)
+        if self.views == 1:
+            return offsets, boxes[0]
+        return offsets, [boxes[v] for _, v in rows]
+
+    def _warm_crop(self, W: int, H: int):
+        """(offsets, crop) of a warm-up launch: the kernel form a request runs."""
+        if self.views == 1:
+            return [0], None
+        return [0] * self.views, [(0.0, 0.0, float(W), float(H))] * self.views
 
     # -- ring ---------------------------------------------------------------
     def _entry(self, nbytes: int) -> _UploadEntry:
@@ -280,7 +408,11 @@ class Y4mDecoder(_StagedFileDecoder):
 
     ``crop``: ``"full"`` scales the whole frame to the output (what the
     synthetic NV12 path does), ``"center"`` the centred square of the short
-    side. ``filter``: ``"bilinear"`` (two taps per axis, the default) or
+    side, ``{"short_side": S, "views": V}`` one or three windows of the frame
+    resized to short side ``S`` (``_StagedFileDecoder``); ``decode`` then
+    returns ``V`` rows per clip, or with ``views=[...]`` (one view index per
+    entry of ``starts``) exactly those rows, every distinct clip staged and
+    uploaded once. ``filter``: ``"bilinear"`` (two taps per axis, the default) or
     ``"antialias"``, the triangle filter widened by the downscale factor that
     PIL's ``resize(BILINEAR)`` and torchvision's ``Resize(antialias=True)``
     apply (``yuv420_to_clip(filter=)``); both boxes lie inside the frame."""
@@ -300,8 +432,14 @@ class Y4mDecoder(_StagedFileDecoder):
         except ValueError:
             del self._maps[vid]
             raise
+        try:
+            boxes = self._probe_boxes(path, hdr)
+        except ValueError:
+            del self._maps[vid]
+            raise
         self._ids[path] = vid
         self._videos[vid] = (path, hdr)
+        self._boxes[vid] = boxes
         return vid, hdr.num_frames
 
     def warmup(self, n: int) -> None:
@@ -313,21 +451,23 @@ class Y4mDecoder(_StagedFileDecoder):
         for i in range(n):
             e = self._entry(15 * self.F * stride)
             e.dev[:self.F * stride].zero_()
-            vops.yuv420_to_clip(e.dev, [0], self.F, W, H, stride,
+            offsets, crop = self._warm_crop(W, H)
+            vops.yuv420_to_clip(e.dev, offsets, self.F, W, H, stride,
                                 vops.i420_planes(W, H, len(y4m.FRAME_MARKER)), self.W,
-                                self.H, dtype=self.dtype, out=self._out(1, None),
-                                filter=self.filter)
+                                self.H, crop=crop, dtype=self.dtype,
+                                out=self._out(len(offsets), None), filter=self.filter)
             e.event.record(torch.cuda.current_stream(self.device))
             e.in_flight = True
 
     # -- decode ---------------------------------------------------------------
-    def decode(self, vid, starts, out=None):
-        n = len(starts)
-        if n == 0:
+    def decode(self, vid, starts, out=None, views=None):
+        if len(starts) == 0:
             return self.empty()
         got = self._videos.get(vid)
         if got is None:
             raise KeyError("video id %r was not probed" % (vid,))
+        starts, rows = self._rows(starts, views)
+        n = len(starts)
         path, hdr = got
         _, data = self._map(vid, path)
         span = self.F * hdr.frame_stride
@@ -337,7 +477,7 @@ class Y4mDecoder(_StagedFileDecoder):
                 raise ValueError("%s: clip at frame %d (+%d) is outside the %d frames"
                                  % (path, s, self.F, hdr.num_frames))
         planes = self._PLANES[hdr.sampling](hdr.width, hdr.height, len(y4m.FRAME_MARKER))
-        offsets = [i * span for i in range(n)]
+        offsets, crop = self._clip_args(vid, hdr, rows, span)
         cuda = self.device.type == "cuda"
         if cuda:
             entry = self._entry(max(n, 15) * span)
@@ -359,10 +499,10 @@ class Y4mDecoder(_StagedFileDecoder):
                 if cuda:     # this clip uploads while the next one is staged
                     buf[i * span:(i + 1) * span].copy_(
                         entry.pinned[i * span:(i + 1) * span], non_blocking=True)
-            out = self._out(n, out)
+            out = self._out(len(rows), out)
             vops.yuv420_to_clip(buf[:n * span], offsets, self.F, hdr.width, hdr.height,
                                 hdr.frame_stride, planes, self.W, self.H,
-                                crop=self._crop_box(hdr), dtype=self.dtype, out=out,
+                                crop=crop, dtype=self.dtype, out=out,
                                 filter=self.filter, sampling=hdr.sampling)
         finally:
             if cuda:     # also behind the uploads of a request that raised
@@ -395,7 +535,8 @@ class MjpegDecoder(_StagedFileDecoder):
     its event discipline are ``Y4mDecoder``'s. On a CPU device the records go
     to the ops' CPU mirrors.
 
-    ``crop`` and ``filter`` as for ``Y4mDecoder``; ``threads``: 1-16 entropy-decode
+    ``crop`` and ``filter`` as for ``Y4mDecoder`` (with views, every frame is
+    entropy-decoded and IDCT'd once per request); ``threads``: 1-16 entropy-decode
     threads.
 
     ``entropy="gpu"`` (opt-in; ``"host"`` is the path above) moves the Huffman
@@ -471,8 +612,14 @@ class MjpegDecoder(_StagedFileDecoder):
         except ValueError:
             del self._maps[vid]
             raise
+        try:
+            boxes = self._probe_boxes(path, idx)
+        except ValueError:
+            del self._maps[vid]
+            raise
         self._ids[path] = vid
         self._videos[vid] = (path, idx)
+        self._boxes[vid] = boxes
         return vid, idx.num_frames
 
     def _planes(self, nframes: int, frame_bytes: int) -> torch.Tensor:
@@ -482,12 +629,16 @@ class MjpegDecoder(_StagedFileDecoder):
             self._surface = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._surface
 
-    def _to_clips(self, records, n, W, H, mw, mh, crop, out, sampling="420"):
+    def _to_clips(self, records, n, W, H, mw, mh, clip_args, out, sampling="420"):
+        """``n`` clips of frame records -> one IDCT over all of them, then one clip
+        launch over the output rows; ``clip_args(span)``: (offsets, crop) of the
+        rows for clips ``span`` surface bytes apart."""
         fbytes = vops.jpeg_frame_bytes(mw, mh, sampling)[1]
         surf = vops.jpeg_idct(records, n * self.F, mw, mh,
                               out=self._planes(max(n, 15) * self.F, fbytes)
                               if self.device.type == "cuda" else None, sampling=sampling)
-        return vops.yuv420_to_clip(surf, [i * self.F * fbytes for i in range(n)], self.F, W, H,
+        offsets, crop = clip_args(self.F * fbytes)
+        return vops.yuv420_to_clip(surf, offsets, self.F, W, H,
                                    fbytes, vops.jpeg_surface_planes(mw, mh, sampling), self.W,
                                    self.H, crop=crop, dtype=self.dtype, out=out, matrix="jfif",
                                    filter=self.filter, sampling=sampling)
@@ -502,18 +653,21 @@ class MjpegDecoder(_StagedFileDecoder):
             e = self._entry(15 * self.F * rb)
             e.dev[:self.F * rb].zero_()
             try:
-                self._to_clips(e.dev[:self.F * rb], 1, W, H, mw, mh, None, self._out(1, None))
+                self._to_clips(e.dev[:self.F * rb], 1, W, H, mw, mh,
+                               lambda span: self._warm_crop(W, H),
+                               self._out(max(1, self.views), None))
             finally:
                 e.event.record(torch.cuda.current_stream(self.device))
                 e.in_flight = True
 
-    def decode(self, vid, starts, out=None):
-        n = len(starts)
-        if n == 0:
+    def decode(self, vid, starts, out=None, views=None):
+        if len(starts) == 0:
             return self.empty()
         got = self._videos.get(vid)
         if got is None:
             raise KeyError("video id %r was not probed" % (vid,))
+        starts, rows = self._rows(starts, views)
+        n = len(starts)
         path, idx = got
         _, data = self._map(vid, path)
         for s in starts:
@@ -522,7 +676,7 @@ class MjpegDecoder(_StagedFileDecoder):
                                  % (path, s, self.F, idx.num_frames))
         self.stats["requests"] += 1
         if self.entropy == "gpu":
-            return self._decode_gpu_entropy(vid, path, idx, data, starts, out)
+            return self._decode_gpu_entropy(vid, path, idx, data, starts, out, rows)
         span = self.F * idx.record_bytes
         self.stats["uploaded_bytes"] += n * span
         cuda = self.device.type == "cuda"
@@ -540,9 +694,9 @@ class MjpegDecoder(_StagedFileDecoder):
                 if cuda:     # this clip uploads while the next one decodes
                     buf[i * span:(i + 1) * span].copy_(
                         entry.pinned[i * span:(i + 1) * span], non_blocking=True)
-            out = self._out(n, out)
+            out = self._out(len(rows), out)
             self._to_clips(buf[:n * span], n, idx.width, idx.height, idx.mw, idx.mh,
-                           self._crop_box(idx), out, idx.sampling)
+                           lambda sp: self._clip_args(vid, idx, rows, sp), out, idx.sampling)
         finally:
             if cuda:     # also behind the uploads of a request that raised
                 entry.event.record(torch.cuda.current_stream(self.device))
@@ -589,7 +743,7 @@ class MjpegDecoder(_StagedFileDecoder):
             setattr(self, name, buf)
         return buf
 
-    def _decode_gpu_entropy(self, vid, path, idx, data, starts, out):
+    def _decode_gpu_entropy(self, vid, path, idx, data, starts, out, rows):
         n, F = len(starts), self.F
         nfr = n * F
         longest = self._max_len.get(vid)
@@ -639,9 +793,9 @@ class MjpegDecoder(_StagedFileDecoder):
                                                  subseq_bytes=self.subseq_bytes,
                                                  sampling=idx.sampling)
                 mjpeg.raise_for_status(status.numpy(), path, frames)
-            out = self._out(n, out)
+            out = self._out(len(rows), out)
             self._to_clips(records, n, idx.width, idx.height, idx.mw, idx.mh,
-                           self._crop_box(idx), out, idx.sampling)
+                           lambda sp: self._clip_args(vid, idx, rows, sp), out, idx.sampling)
         finally:
             if cuda:     # also behind the uploads of a request that raised
                 entry.event.record(torch.cuda.current_stream(self.device))
@@ -654,7 +808,9 @@ def make_decoder(backend: str, device: torch.device, clip_length=8, height=112, 
     """``decoder_args``: backend-specific constructor arguments (``y4m``:
     ``depth``, ``crop``, ``filter``; ``mjpeg``: ``depth``, ``crop``, ``filter``,
     ``threads``, ``entropy``, ``subseq_bytes``); the other
-    backends take none and ignore it."""
+    backends take none and ignore it. ``crop`` is ``"full"``, ``"center"`` or
+    ``{"short_side": S, "views": 1 or 3}``; with three views the decoder returns
+    three rows per clip (``Decoder.views``; 1 for every other decoder)."""
     if backend == "y4m":
         return Y4mDecoder(device, clip_length, height, width, dtype, **(decoder_args or {}))
     if backend == "mjpeg":

@@ -494,9 +494,34 @@ class R2P1DVideoPathIterator(VideoPathIterator):
         return iter(self._it)
 
 
+def _decoder_args(decoder_args, crop, filter):
+    """``decoder_args`` with the step-level ``crop`` / ``filter`` kwargs (what a
+    config's ``defaults`` or ``--set`` reach) laid over it."""
+    args = dict(decoder_args or {})
+    if crop is not None:
+        args["crop"] = crop
+    if filter is not None:
+        args["filter"] = filter
+    return args or None
+
+
+def expand_views(starts, views: int):
+    """Clip starts -> (start, view) of every output row, the views of a clip
+    adjacent: the row order of ``decode`` with ``views`` views per clip."""
+    return [s for s in starts for _ in range(views)], [v for _ in starts for v in range(views)]
+
+
 class R2P1DLoader(RunnerModel):
     """Video path -> sampled clips, NDHWC [n, clip_length, 112, 112, C] (fp32 C=4,
-    bf16 C=8; clip_length 8, 16 or 32 frames, default 8)."""
+    bf16 C=8; clip_length 8, 16 or 32 frames, default 8).
+
+    A decoder with ``views`` > 1 (``decoder_args`` / ``crop`` of
+    ``{"short_side": S, "views": 3}``) returns that many rows per temporal
+    clip: the loader keeps ``min(len(starts), max_clips // views)`` clips, emits
+    ``views`` rows for each and counts rows in ``time_card.num_clips``, so
+    slots, buckets and the aggregator (which sums every row of a video) are
+    sized by ``max_clips`` as before. ``crop`` and ``filter`` are shorthands
+    for the same keys of ``decoder_args``."""
 
     # decode kernels are tiny and gate the consumers: run them on a
     # high-priority HIP stream so they do not queue behind the conv kernels
@@ -505,7 +530,7 @@ class R2P1DLoader(RunnerModel):
     def __init__(self, device, num_clips_population=(1, 15), num_clips_weights=(10, 1),
                  decoder="synthetic", seed=None, max_clips=DEFAULT_MAX_CLIPS,
                  warmup=3, dtype=None, decoder_args=None,
-                 clip_length=DEFAULT_CLIP_LENGTH, **unused):
+                 clip_length=DEFAULT_CLIP_LENGTH, crop=None, filter=None, **unused):
         super().__init__(device)
         self.clip_length = check_clip_length(clip_length)
         self.sampler = R2P1DSampler(clip_length=self.clip_length,
@@ -514,8 +539,13 @@ class R2P1DLoader(RunnerModel):
         self.dtype = _dtype(dtype)
         self.decoder = make_decoder(decoder, device, *clip_shape(self.clip_length),
                                     dtype=self.dtype,
-                                    decoder_args=decoder_args)
+                                    decoder_args=_decoder_args(decoder_args, crop, filter))
         self.max_clips = max_clips
+        self.views = int(getattr(self.decoder, "views", 1))
+        if int(max_clips) < self.views:
+            raise ValueError("R2P1DLoader: max_clips = %r holds no clip of %d views (the "
+                             "decoder's crop 'views'); max_clips must be >= views"
+                             % (max_clips, self.views))
         self.decoder.warmup(warmup)
         if device.type == "cuda":
             torch.cuda.current_stream(device).synchronize()
@@ -524,16 +554,19 @@ class R2P1DLoader(RunnerModel):
         """(video id, clip start frames) of ``path``; tags sampled requests
         with what a numerics check needs to decode the same clips again."""
         vid, length = self.decoder.probe(path)
-        starts = (self.sampler.sample(length) or [])[:self.max_clips]
+        starts = (self.sampler.sample(length) or [])[:self.max_clips // self.views]
         if time_card is not None and (time_card.id % CHECK_EVERY == 0 or (
                 len(starts) >= 15 and time_card.id % CHECK_EVERY_LARGE == 0)):
-            time_card.extra["clip_src"] = (int(vid), [int(s) for s in starts])
+            # one start per output row, so that the sample files keep
+            # len(starts) == logits rows
+            time_card.extra["clip_src"] = (int(vid), [int(s) for s in
+                                                      expand_views(starts, self.views)[0]])
         return vid, starts
 
     def load(self, path: str, out: Optional[torch.Tensor] = None, time_card=None):
         vid, starts = self._sample(path, time_card)
         return self.decoder.decode(vid, starts, out=None if out is None else
-                                   out[:len(starts)])
+                                   out[:len(starts) * self.views])
 
     def __call__(self, tensors, non_tensors, time_card):
         frames = self.load(non_tensors, time_card=time_card)
@@ -556,13 +589,18 @@ class R2P1DLoader(RunnerModel):
         start frame) only, so the segments equal the split of one decode."""
         from ...control import segment_bounds
         vid, starts = self._sample(non_tensors, time_card)
+        if self.views > 1:      # the rows are split, not the clips: a segment names its views
+            row_starts, row_views = expand_views(starts, self.views)
         rows = []
         for k, out in enumerate(outs):
-            a, b = segment_bounds(len(starts), len(outs), k)
-            if b > a:
+            a, b = segment_bounds(len(starts) * self.views, len(outs), k)
+            if b > a and self.views > 1:
+                self.decoder.decode(vid, row_starts[a:b], out=out[0][:b - a],
+                                    views=row_views[a:b])
+            elif b > a:
                 self.decoder.decode(vid, starts[a:b], out=out[0][:b - a])
             rows.append(b - a)
-        time_card.num_clips = len(starts)
+        time_card.num_clips = len(starts) * self.views
         return rows, None, time_card
 
     def input_shape(self):
@@ -590,13 +628,13 @@ class R2P1DSingleStep(RunnerModel):
                  decoder="synthetic", seed=None, model_seed=0, backend="auto",
                  bn_mode=None, ckpt_path=None, max_clips=DEFAULT_MAX_CLIPS, warmup=3,
                  use_graphs=True, autotune=True, dtype=None, decoder_args=None,
-                 clip_length=DEFAULT_CLIP_LENGTH, **unused):
+                 clip_length=DEFAULT_CLIP_LENGTH, crop=None, filter=None, **unused):
         super().__init__(device)
         clip_length = check_clip_length(clip_length)
         self.loader = R2P1DLoader(device, num_clips_population, num_clips_weights,
                                   decoder=decoder, seed=seed, max_clips=max_clips,
                                   warmup=warmup, dtype=dtype, decoder_args=decoder_args,
-                                  clip_length=clip_length)
+                                  clip_length=clip_length, crop=crop, filter=filter)
         self.runner = R2P1DRunner(device, 1, 5, num_classes,
                                   layer_sizes=layer_sizes, depth=depth, backend=backend,
                                   bn_mode=bn_mode, seed=model_seed, ckpt_path=ckpt_path,
@@ -619,12 +657,14 @@ class R2P1DSingleStep(RunnerModel):
         if isinstance(eng, GraphedEngine) and self.runner.device.type == "cuda":
             # decode straight into the bucket graph's input buffer
             vid, length = self.loader.decoder.probe(non_tensors)
-            starts = (self.loader.sampler.sample(length) or [])[:self.loader.max_clips]
-            time_card.num_clips = len(starts)
+            views = self.loader.views
+            starts = (self.loader.sampler.sample(length) or [])[:self.loader.max_clips // views]
+            nrows = len(starts) * views
+            time_card.num_clips = nrows
             if starts:
-                static_in, _ = eng.input_buffer(len(starts))
-                self.loader.decoder.decode(vid, starts, out=static_in[:len(starts)])
-                y = eng.replay(len(starts))
+                static_in, _ = eng.input_buffer(nrows)
+                self.loader.decoder.decode(vid, starts, out=static_in[:nrows])
+                y = eng.replay(nrows)
                 if eng.range_guard is not None:
                     self.runner._guard_calls.append((eng, y))
                 return (y,), None, time_card

@@ -224,6 +224,11 @@ class Kernels:
         lib.rnb_yuv_to_clip.argtypes = (lib.rnb_yuv420_to_clip.argtypes[:-1]
                                         + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p])
         lib.rnb_yuv_to_clip.restype = ctypes.c_int
+        # rnb_yuv_to_clip with (boxes [n][4], boxes_dev) in place of crop
+        at = lib.rnb_yuv_to_clip.argtypes
+        lib.rnb_yuv_to_clip_boxes.argtypes = at[:15] + [ctypes.POINTER(ctypes.c_float),
+                                                        ctypes.c_void_p] + at[16:]
+        lib.rnb_yuv_to_clip_boxes.restype = ctypes.c_int
         lib.rnb_jpeg_idct.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
@@ -854,6 +859,33 @@ class Kernels:
                   po, ps, c_step, out_ptr, out_w, out_h, c, m, s, 1 if bf16 else 0,
                   int(matrix), stream),
                "yuv420_to_clip_aa" if antialias else "yuv420_to_clip")
+
+    def yuv_to_clip_boxes(self, buf_ptr, buf_len, offsets, offsets_dev_ptr, F, src_w, src_h,
+                          frame_stride, plane_offsets, plane_strides, c_step, out_ptr, out_w,
+                          out_h, boxes, boxes_dev_ptr, mean, std, bf16, stream, matrix=0,
+                          antialias=False, sampling=0):
+        """``yuv420_to_clip`` with one crop box per row (``rnb_yuv_to_clip_boxes``):
+        ``boxes`` holds ``len(offsets)`` boxes (x, y, w, h); rows may repeat an
+        offset. Past 64 rows both tables must also be in device memory
+        (``offsets_dev_ptr`` int64, ``boxes_dev_ptr`` fp32 ``[n][4]``)."""
+        n = len(offsets)
+        offs = (ctypes.c_longlong * max(1, n))(*offsets)
+        po = (ctypes.c_longlong * 3)(*plane_offsets)
+        ps = (ctypes.c_int * 3)(*plane_strides)
+        import numpy as np
+        table = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1)     # alive to the call
+        if table.size != 4 * n:
+            raise ValueError("yuv_to_clip_boxes: %d offsets need %d box numbers, got %d"
+                             % (n, 4 * n, table.size))
+        b = table.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        m = (ctypes.c_float * 3)(*mean)
+        s = (ctypes.c_float * 3)(*std)
+        _check(self.lib.rnb_yuv_to_clip_boxes(buf_ptr, buf_len, offs, offsets_dev_ptr, n, F,
+                                              src_w, src_h, frame_stride, po, ps, c_step,
+                                              out_ptr, out_w, out_h, b, boxes_dev_ptr, m, s,
+                                              1 if bf16 else 0, int(matrix),
+                                              1 if antialias else 0, int(sampling), stream),
+               "yuv_to_clip_boxes")
 
     def jpeg_idct(self, rec_ptr, rec_len, record_bytes, nframes, mw, mh, surf_ptr, surf_len,
                   stream, sampling=0):

@@ -6,8 +6,10 @@ mirror (the mirrors are what the numerics tests compare the kernels with).
 from __future__ import annotations
 
 import math
+import numbers
 from typing import NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 # Kinetics-400 normalisation used by R(2+1)D
@@ -294,6 +296,35 @@ def nv12_planes(W: int, H: int, header: int = 0) -> YuvPlanes:
     return YuvPlanes(header, header + W * H, header + W * H + 1, W, W, W, 2)
 
 
+BOX_ROWS_IN_ARGS = 64      # rows whose offset and box travel in the kernel arguments
+
+
+def _crop_boxes(crop, n: int):
+    """``None`` for no crop or one box (x, y, w, h); a list of ``n`` float
+    4-tuples for a sequence of boxes, one per clip (``ValueError`` otherwise)."""
+    if crop is None:
+        return None
+    if isinstance(crop, (torch.Tensor, np.ndarray)):
+        crop = crop.tolist()
+    crop = list(crop)
+    if crop and all(isinstance(c, numbers.Real) for c in crop):
+        return None
+    boxes = [tuple(float(c) for c in box) for box in crop]
+    if len(boxes) != n or any(len(b) != 4 for b in boxes):
+        raise ValueError("yuv420_to_clip: crop must be one box (x, y, w, h) or one box per "
+                         "clip: %d boxes for %d clips" % (len(boxes), n))
+    return boxes
+
+
+def _first_box_outside(boxes, src_w: int, src_h: int):
+    """The first box that does not lie inside the frame, or ``None``: the boxes as
+    the kernel gets them (fp32), summed in double, the launcher's own check."""
+    b = np.asarray(boxes, dtype=np.float32).astype(np.float64).reshape(-1, 4)
+    ok = ((b[:, 0] >= 0) & (b[:, 1] >= 0) & (b[:, 2] > 0) & (b[:, 3] > 0)
+          & (b[:, 0] + b[:, 2] <= src_w) & (b[:, 1] + b[:, 3] <= src_h))
+    return None if ok.all() else tuple(boxes[int(np.argmin(ok))])
+
+
 def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: int,
                    frame_stride: int, planes: YuvPlanes, out_w: int = 112, out_h: int = 112,
                    crop=None, dtype=torch.float32, mean=KINETICS_MEAN, std=KINETICS_STD,
@@ -323,7 +354,14 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
     ``sampling``: ``"420"`` (default), ``"422"`` or ``"444"``, luma factors
     (Hs, Vs) = (2, 2), (2, 1), (1, 1). The chroma planes are ceil(w / Hs) x
     ceil(h / Vs) (JFIF) or w / Hs x h / Vs (BT.601, even size needed only along
-    an axis with factor 2); chroma sample j sits at luma Hs j + (Hs - 1) / 2."""
+    an axis with factor 2); chroma sample j sits at luma Hs j + (Hs - 1) / 2.
+
+    ``crop``: ``None`` (the whole frame), one box ``(x, y, w, h)`` for every
+    clip, or a sequence of ``n`` boxes, one per entry of ``clip_offsets``. With
+    a sequence, entries may repeat an offset: several views of one clip read
+    one uploaded span, in one launch of the boxed form of the kernels
+    (``rnb_yuv_to_clip_boxes``; up to 64 rows travel in the kernel arguments,
+    more through device tables). ``filter="antialias"`` checks every box."""
     hs, vs = sampling_factors(sampling, "yuv420_to_clip")
     if matrix not in MATRICES:
         raise ValueError("yuv420_to_clip: matrix must be one of %s, got %r" % (MATRICES, matrix))
@@ -334,7 +372,9 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
                                 else clip_offsets)]
     n = len(offsets)
     planes = YuvPlanes(*planes)
-    crop = tuple(float(c) for c in (crop or (0, 0, src_w, src_h)))
+    boxes = _crop_boxes(crop, n)
+    if boxes is None:
+        crop = tuple(float(c) for c in (crop if crop is not None else (0, 0, src_w, src_h)))
     C = IN_CHANNELS_P_F32 if dtype == torch.float32 else IN_CHANNELS_P
     shape = (n, F, out_h, out_w, C)
     if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
@@ -344,12 +384,28 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
         raise ValueError("yuv420_to_clip: out must be contiguous %s %s" % (dtype, shape))
     antialias = filter == "antialias"
     if antialias:
-        # the box as the kernel gets it (fp32), summed in double: the launcher's own check
-        bx, by, bw, bh = torch.tensor(crop, dtype=torch.float32).double().tolist()
-        if not (bx >= 0 and by >= 0 and bw > 0 and bh > 0
-                and bx + bw <= src_w and by + bh <= src_h):
+        bad = _first_box_outside([crop] if boxes is None else boxes, src_w, src_h)
+        if bad is not None:
             raise ValueError("yuv420_to_clip: filter='antialias' needs the crop box inside "
-                             "the %d x %d frame, got %r" % (src_w, src_h, crop))
+                             "the %d x %d frame, got %r" % (src_w, src_h, bad))
+    if buf.is_cuda and boxes is not None:
+        from .native import kernels
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=buf.device)
+        table = box_table = None
+        if n > BOX_ROWS_IN_ARGS:       # past the kernel-argument tables: both in device memory
+            table = torch.tensor(offsets, dtype=torch.int64).to(buf.device)
+            box_table = torch.tensor(boxes, dtype=torch.float32).to(buf.device)
+        kernels().yuv_to_clip_boxes(buf.data_ptr(), buf.numel(), offsets,
+                                    None if table is None else table.data_ptr(), F, src_w,
+                                    src_h, frame_stride, planes[:3], planes[3:6], planes.c_step,
+                                    out.data_ptr(), out_w, out_h, boxes,
+                                    None if box_table is None else box_table.data_ptr(), mean,
+                                    std, dtype == torch.bfloat16,
+                                    torch.cuda.current_stream(buf.device).cuda_stream,
+                                    matrix=1 if jfif else 0, antialias=antialias,
+                                    sampling=SAMPLINGS.index(sampling))
+        return out
     if buf.is_cuda:
         from .native import kernels
         if out is None:
@@ -382,10 +438,20 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
         idx = base + off + torch.arange(rows).view(1, rows, 1) * stride \
             + torch.arange(cols).view(1, 1, cols) * step
         return buf[idx].float()
-    return _planes_to_clip(gather(planes.y, planes.y_stride, src_h, src_w, 1),
-                           gather(planes.u, planes.u_stride, ch, cw, planes.c_step),
-                           gather(planes.v, planes.v_stride, ch, cw, planes.c_step),
-                           shape, crop, dtype, mean, std, out, matrix, filter, (hs, vs))
+    yp = gather(planes.y, planes.y_stride, src_h, src_w, 1)
+    up = gather(planes.u, planes.u_stride, ch, cw, planes.c_step)
+    vp = gather(planes.v, planes.v_stride, ch, cw, planes.c_step)
+    if boxes is None:
+        return _planes_to_clip(yp, up, vp, shape, crop, dtype, mean, std, out, matrix, filter,
+                               (hs, vs))
+    res = torch.stack([_planes_to_clip(yp[c * F:(c + 1) * F], up[c * F:(c + 1) * F],
+                                       vp[c * F:(c + 1) * F], shape[1:], boxes[c], dtype, mean,
+                                       std, None, matrix, filter, (hs, vs))
+                       for c in range(n)]) if n else torch.zeros(shape, dtype=dtype)
+    if out is not None:
+        out.copy_(res.view(out.shape))
+        return out
+    return res
 
 
 # ---------------------------------------------------------------------------

@@ -26,6 +26,12 @@
     ``--sampling 422`` / ``444`` encodes, decodes and reports that chroma layout
     (default 420) on every row.
 
+    ``--short-side S [--views V]`` reports the short-side resize + window
+    protocol instead (``crop={"short_side": S, "views": V}``): the host and
+    sustained rows of ``MjpegDecoder`` with ``threads=4`` and with
+    ``entropy="gpu"``, both filters, for 1 view and for ``V``; the bytes
+    uploaded per request do not depend on the views.
+
     python scripts/mjpeg_decode_bench.py --out profiles/mjpeg_decode.txt
     python scripts/mjpeg_decode_bench.py --entropy gpu --restart-interval 22
     python scripts/mjpeg_decode_bench.py --entropy gpu --subseq-bytes 0,64,128,256,512
@@ -275,6 +281,24 @@ def host(dev, dtype, encoded, reqs, lines, sustained=60, entropy="host", restart
                              entropy="gpu", subseq_bytes=sub, filter=filter)
 
 
+def views_host(dev, dtype, encoded, reqs, lines, sustained, short_side, nviews):
+    frames = 300
+    starts = [20 * c for c in range(CLIPS)]
+    C = 4 if dtype == torch.float32 else 8
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "v.mjpeg")
+        with open(path, "wb") as fp:
+            for i in range(frames):
+                fp.write(encoded[i % DISTINCT][0])
+        for filt in vops.FILTERS:
+            for v in sorted({1, nviews}):
+                out = torch.empty((CLIPS * v, F, 112, 112, C), dtype=dtype, device=dev)
+                crop = {"short_side": short_side, "views": v}
+                for label, kw in (("threads=4", dict(threads=4)), ("entropy=gpu", dict(entropy="gpu"))):
+                    decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines,
+                                 "%s %s v=%d" % (label, filt[:4], v), filter=filt, crop=crop, **kw)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
@@ -292,6 +316,9 @@ def main():
                     help="antialias: also time yuv420_clip_aa_kernel, and decode with "
                          "MjpegDecoder(filter='antialias')")
     ap.add_argument("--sampling", choices=mjpeg.SAMPLINGS, default="420")
+    ap.add_argument("--short-side", type=float, default=None,
+                    help="report MjpegDecoder with crop={'short_side': S, 'views': V} instead")
+    ap.add_argument("--views", type=int, choices=(1, 3), default=1, help="with --short-side")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     global SAMPLING
@@ -306,6 +333,19 @@ def main():
     subseq = tuple(mjpeg.check_subseq_bytes(int(x), "--subseq-bytes")
                    for x in args.subseq_bytes.split(",") if x.strip())
     encoded = encode(75, args.restart_interval)
+    if args.short_side is not None:
+        lines[0] = ("mjpeg decode path, sampling %s, short side %g, %d view(s), per 15-clip "
+                    "request at %dx%d -> 112x112 (%s)"
+                    % (":".join(SAMPLING), args.short_side, args.views, W, H,
+                       torch.cuda.get_device_name(0)))
+        views_host(dev, torch.float32, encoded, args.requests, lines, args.sustained,
+                   args.short_side, args.views)
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        if args.out:
+            with open(args.out, "w") as fp:
+                fp.write(text)
+        return
     for dtype in (torch.float32, torch.bfloat16):
         kernels(dev, dtype, encoded, args.reps, args.rounds, lines, args.filter)
     if args.entropy == "gpu":

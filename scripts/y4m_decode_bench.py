@@ -15,6 +15,13 @@ process; the ratio is reported) and ``Y4mDecoder(filter="antialias")`` on the
 host side. ``--size WxH`` and ``--clips N`` change that request, e.g.
 ``--size 1920x1080 --clips 1``. Without ``--filter antialias`` the script runs
 and prints what it always did.
+
+``--short-side S [--views V]`` times the short-side resize + window protocol
+instead (``crop={"short_side": S, "views": V}``), for both filters: the clip
+kernels through the one-box entry points at ``--clips`` rows next to the boxed
+entry point at the same rows with that box repeated and at ``clips * V`` rows
+with the views' boxes, then ``Y4mDecoder.decode`` (host call, call + sync,
+sustained requests/s, uploaded bytes per request) for 1 view and for ``V``.
 """
 import argparse
 import os
@@ -167,6 +174,90 @@ def host_antialias(dev, dtype, reqs, lines, w, h, clips):
                         max(call), statistics.median(total), reqs, clips))
 
 
+def views_kernels(dev, dtype, reps, rounds, lines, w, h, clips, short_side, nviews):
+    """The one-box kernels at ``clips`` rows, the boxed kernels at ``clips`` rows
+    (the centre box repeated) and at ``clips * nviews`` rows (each clip through
+    every view's box, one uploaded span per clip), both filters, alternating."""
+    from rnb_amd.models.r2p1d.decoder import view_boxes
+    rng = np.random.default_rng(0)
+    stride = 6 + y4m.payload_bytes(w, h, SAMPLING)
+    buf = torch.from_numpy(rng.integers(0, 256, clips * F * stride, dtype=np.uint8)).to(dev)
+    offs = [c * F * stride for c in range(clips)]
+    C = 4 if dtype == torch.float32 else 8
+    out = torch.empty((clips * nviews, F, 112, 112, C), dtype=dtype, device=dev)
+    planes = PLANES[SAMPLING](w, h, 6)
+    centre = view_boxes(w, h, 112, 112, short_side, 1)[0]
+    vb = view_boxes(w, h, 112, 112, short_side, nviews)
+    name = str(dtype).split(".")[1]
+    for filt in vops.FILTERS:
+        def run(offsets, crop):
+            return lambda: vops.yuv420_to_clip(buf, offsets, F, w, h, stride, planes, dtype=dtype,
+                                               out=out[:len(offsets)], crop=crop, filter=filt,
+                                               sampling=SAMPLING)
+        cases = [("one box, %d rows" % clips, run(offs, centre)),
+                 ("boxed, %d rows, one box repeated" % clips, run(offs, [centre] * clips)),
+                 ("boxed, %d rows, %d views" % (clips * nviews, nviews),
+                  run([o for o in offs for _ in range(nviews)], vb * clips))]
+        times = [[] for _ in cases]
+        for _, fn in cases:
+            event_ms(fn, reps)                            # warm
+        for _ in range(rounds):
+            for t, (_, fn) in zip(times, cases):
+                t.append(event_ms(fn, reps))
+        for (what, _), t in zip(cases, times):
+            lines.append("clip kernel %s %s, %s: median %.2f us/launch (min %.2f, max %.2f over %d "
+                         "rounds of %d)" % (filt, name, what, statistics.median(t) * 1e3,
+                                            min(t) * 1e3, max(t) * 1e3, rounds, reps))
+
+
+def views_host(dev, dtype, reqs, lines, w, h, clips, short_side, nviews):
+    """``Y4mDecoder.decode`` with 1 view and with ``nviews``: host call, call +
+    sync, sustained requests/s of one loader, staged bytes per request."""
+    rng = np.random.default_rng(1)
+    starts = [20 * c for c in range(clips)]
+    frames = starts[-1] + F + 4
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "v.y4m")
+        y4m.write_y4m(path, [(rng.integers(0, 256, (h, w), dtype=np.uint8),
+                              rng.integers(0, 256, chroma_shape(w, h), dtype=np.uint8),
+                              rng.integers(0, 256, chroma_shape(w, h), dtype=np.uint8))
+                             for _ in range(frames)], sampling=SAMPLING)
+        with open(path, "rb") as fp:                       # warm the page cache
+            while fp.read(1 << 24):
+                pass
+        C = 4 if dtype == torch.float32 else 8
+        for filt in vops.FILTERS:
+            for v in sorted({1, nviews}):
+                out = torch.empty((clips * v, F, 112, 112, C), dtype=dtype, device=dev)
+                dec = Y4mDecoder(dev, dtype=dtype, filter=filt,
+                                 crop={"short_side": short_side, "views": v})
+                vid, _ = dec.probe(path)
+                for _ in range(5):
+                    dec.decode(vid, starts, out=out)
+                torch.cuda.synchronize()
+                call, total = [], []
+                for _ in range(reqs):
+                    t0 = time.perf_counter()
+                    dec.decode(vid, starts, out=out)
+                    t1 = time.perf_counter()
+                    torch.cuda.synchronize()
+                    t2 = time.perf_counter()
+                    call.append((t1 - t0) * 1e3)
+                    total.append((t2 - t0) * 1e3)
+                t0 = time.perf_counter()
+                for _ in range(reqs):
+                    dec.decode(vid, starts, out=out)
+                torch.cuda.synchronize()
+                rate = reqs / (time.perf_counter() - t0)
+                hdr = dec._videos[vid][1]
+                lines.append("Y4mDecoder.decode %s, %d view(s), %d rows %s: host call median %.3f ms "
+                             "(min %.3f, max %.3f), call + sync median %.3f ms, sustained %.0f "
+                             "requests/s, %d bytes uploaded per request"
+                             % (filt, v, clips * v, str(dtype).split(".")[1],
+                                statistics.median(call), min(call), max(call),
+                                statistics.median(total), rate, clips * F * hdr.frame_stride))
+
+
 def host(dev, dtype, reqs, lines):
     rng = np.random.default_rng(1)
     frames = 300
@@ -217,6 +308,9 @@ def main():
     ap.add_argument("--sampling", choices=tuple(PLANES), default="420",
                     help="422 / 444: the clip kernels (both filters) and Y4mDecoder on C422 / "
                          "C444 frames")
+    ap.add_argument("--short-side", type=float, default=None,
+                    help="time crop={'short_side': S, 'views': V} (both filters) instead")
+    ap.add_argument("--views", type=int, choices=(1, 3), default=1, help="with --short-side")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     global SAMPLING
@@ -224,7 +318,17 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("y4m_decode_bench: needs a GPU")
     dev = torch.device("cuda:0")
-    if args.filter == "antialias":
+    if args.short_side is not None:
+        w, h = (int(x) for x in args.size.lower().split("x"))
+        lines = ["y4m decode path, sampling %s, short side %g, %d view(s), per %d-clip request at "
+                 "%dx%d -> 112x112 (%s)" % (":".join(SAMPLING), args.short_side, args.views,
+                                            args.clips, w, h, torch.cuda.get_device_name(0))]
+        for dtype in (torch.float32, torch.bfloat16):
+            views_kernels(dev, dtype, args.reps, args.rounds, lines, w, h, args.clips,
+                          args.short_side, args.views)
+        views_host(dev, torch.float32, args.requests, lines, w, h, args.clips, args.short_side,
+                   args.views)
+    elif args.filter == "antialias":
         w, h = (int(x) for x in args.size.lower().split("x"))
         lines = ["y4m decode path, sampling %s, filter antialias, per %d-clip request at %dx%d -> "
                  "112x112 (%s)" % (":".join(SAMPLING), args.clips, w, h,

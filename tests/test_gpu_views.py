@@ -1,0 +1,255 @@
+"""Short-side resize and three-crop views on the GPU: the boxed form of the two
+clip kernels (``rnb_yuv_to_clip_boxes``) against one launch of the existing
+kernels per row, bit for bit, in the kernel arguments and through the device
+tables; the launcher's refusals; the decoders with three views against the CPU
+device and the fp64 oracle; the shipped 3-crop config end to end. Inputs and
+bounds are tests/test_views_cpu.py's."""
+import ctypes
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import decode_oracle as orc
+import decode_oracle_chroma as occ
+import decode_oracle_views as ov
+from rnb_amd.models.r2p1d.decoder import view_boxes
+from rnb_amd.ops import video as vops
+from rnb_amd.utils import mjpeg
+from test_gpu_chroma import MIRROR_TOL
+from test_pipeline_e2e import ROOT, run_cfg
+from test_views_cpu import (DECODERS, ORACLE_CASES, check_views_against_oracle, make_decoder,
+                            make_files, write_y4m_file)
+from test_y4m_cpu import planes, raw_y4m
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+CPU = torch.device("cpu")
+OUTSIDE = (-2.5, 1.0, 50.0, 30.5)          # bilinear only: leaves the frame on three sides
+INSIDE = (3.5, 1.25, 40.0, 30.0)
+
+
+def channels(dtype):
+    return 4 if dtype == torch.float32 else 8
+
+
+def boxed(t, offsets, F, W, H, stride, pl, ow, oh, boxes, dtype, **kw):
+    """The new entry point into a buffer with one clip of sentinel behind the rows."""
+    n = len(offsets)
+    full = torch.full((n + 1, F, oh, ow, channels(dtype)), 3.0, dtype=dtype, device=DEV)
+    got = vops.yuv420_to_clip(t, offsets, F, W, H, stride, pl, ow, oh, crop=boxes, dtype=dtype,
+                              out=full[:n], **kw)
+    torch.cuda.synchronize()
+    assert got.data_ptr() == full.data_ptr() and torch.all(full[n] == 3.0)
+    return got
+
+
+def per_row(t, offsets, F, W, H, stride, pl, ow, oh, boxes, dtype, **kw):
+    """One launch of the existing kernels per row, each with its own box."""
+    return torch.cat([vops.yuv420_to_clip(t, [o], F, W, H, stride, pl, ow, oh, crop=b, dtype=dtype,
+                                          **kw) for o, b in zip(offsets, boxes)])
+
+
+def source(matrix, sampling, clips, F, header):
+    """``clips`` clips of noise: BT.601 planar frames behind ``header`` bytes, or
+    JFIF planes of an odd-sized frame inside a JPEG surface with MCU padding."""
+    if matrix == "jfif":
+        W, H = 45, 33
+        y, u, v = occ.noise_planes(W, H, clips * F, 300 + header, matrix, sampling)
+        mw, mh, _ = mjpeg.geometry(W, H, sampling)
+        buf, stride, pl = occ.pack_jpeg_surface(y, u, v, mw, mh, sampling, 0xEE)
+    else:
+        W, H = (45 if sampling == "444" else 46), (34 if sampling == "420" else 33)
+        y, u, v = occ.noise_planes(W, H, clips * F, 200 + header, matrix, sampling)
+        buf, stride, pl = occ.pack_planar(y, u, v, header)
+    return torch.from_numpy(buf).to(DEV), stride, pl, W, H
+
+
+# -- 1. the boxed kernels against the existing ones, bit for bit --------------------------------------
+@pytest.mark.parametrize("filt", vops.FILTERS)
+@pytest.mark.parametrize("sampling", vops.SAMPLINGS)
+@pytest.mark.parametrize("matrix", vops.MATRICES)
+def test_boxed_entry_point_equals_a_launch_per_row(matrix, sampling, filt):
+    F = 2 if matrix == "jfif" else 3
+    t, stride, pl, W, H = source(matrix, sampling, 3, F, 6 if sampling == "422" else 7)
+    vb = view_boxes(W, H, 16, 12, 13.7, 3)
+    rows = [(2, 0), (0, 2), (2, 1), (1, 1), (0, 0), (2, 2), (0, 1)]      # repeated, non-monotonic
+    offsets = [c * F * stride for c, _ in rows]
+    boxes = [vb[k] for _, k in rows[:-1]] + [INSIDE if filt == "antialias" else OUTSIDE]
+    kw = dict(matrix=matrix, filter=filt, sampling=sampling)
+    for dtype in (torch.float32, torch.bfloat16):
+        got = boxed(t, offsets, F, W, H, stride, pl, 16, 12, boxes, dtype, **kw)
+        want = per_row(t, offsets, F, W, H, stride, pl, 16, 12, boxes, dtype, **kw)
+        assert torch.equal(got, want), (matrix, sampling, filt, dtype)
+        assert not torch.equal(got[0], got[5])               # clip 2 through boxes 0 and 2
+
+
+def test_boxed_antialias_wider_than_one_column_tile():
+    """130 x 4 from 300 x 8: two column tiles, the second of two columns."""
+    y, u, v = orc.noise_planes(300, 8, 4, 17)
+    buf, stride, pl = orc.pack_i420(y, u, v, 7)
+    t = torch.from_numpy(buf).to(DEV)
+    offsets = [2 * stride, 0, 2 * stride]
+    boxes = [(0.0, 0.0, 260.0, 8.0), (20.25, 0.5, 260.0, 7.5), (40.0, 0.0, 260.0, 8.0)]
+    for dtype in (torch.float32, torch.bfloat16):
+        got = boxed(t, offsets, 2, 300, 8, stride, pl, 130, 4, boxes, dtype, filter="antialias")
+        want = per_row(t, offsets, 2, 300, 8, stride, pl, 130, 4, boxes, dtype, filter="antialias")
+        assert torch.equal(got, want)
+
+
+@pytest.mark.parametrize("filt", vops.FILTERS)
+@pytest.mark.parametrize("name", [c[0] for c in ORACLE_CASES])
+def test_boxed_kernels_against_the_oracle(name, filt):
+    check_views_against_oracle(name, filt, DEV)
+
+
+# -- 2. the device tables ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("filt", vops.FILTERS)
+def test_66_rows_use_the_device_tables_and_64_the_arguments(filt):
+    F, clips = 1, 22
+    t, stride, pl, W, H = source("bt601", "420", clips, F, 7)
+    vb = view_boxes(W, H, 16, 12, 13.7, 3)
+    order = np.random.default_rng(66).permutation(clips)
+    offsets = [int(c) * F * stride for c in order for _ in range(3)]
+    boxes = [vb[k] for _ in order for k in range(3)]
+    assert len(offsets) == 66 > vops.BOX_ROWS_IN_ARGS == 64
+    want = per_row(t, offsets, F, W, H, stride, pl, 16, 12, boxes, torch.float32, filter=filt)
+    for n in (66, 64):
+        got = boxed(t, offsets[:n], F, W, H, stride, pl, 16, 12, boxes[:n], torch.float32,
+                    filter=filt)
+        assert torch.equal(got, want[:n]), (filt, n)
+
+
+# -- 3. launcher refusals ------------------------------------------------------------------------------------
+def raw_boxes_call(t, offsets, F, W, H, stride, pl, out, ow, oh, boxes, filt, offs_dev=None,
+                   boxes_dev=None):
+    from rnb_amd.ops.native import kernels
+    n = len(offsets)
+    return kernels().lib.rnb_yuv_to_clip_boxes(
+        t.data_ptr(), t.numel(), (ctypes.c_longlong * n)(*offsets), offs_dev, n, F, W, H, stride,
+        (ctypes.c_longlong * 3)(*pl[:3]), (ctypes.c_int * 3)(*pl[3:6]), pl.c_step, out.data_ptr(),
+        ow, oh, (ctypes.c_float * (4 * n))(*[c for b in boxes for c in b]), boxes_dev,
+        (ctypes.c_float * 3)(*vops.KINETICS_MEAN), (ctypes.c_float * 3)(*vops.KINETICS_STD),
+        0, 0, int(filt == "antialias"), 0, torch.cuda.current_stream(DEV).cuda_stream)
+
+
+def test_boxed_launcher_refusals():
+    """Host-side checks only: nothing is launched."""
+    t, stride, pl, W, H = source("bt601", "420", 1, 1, 7)
+    out = torch.full((70, 1, 12, 16, 4), 9.0, device=DEV)
+    bad = (INSIDE[0], INSIDE[1], W - INSIDE[0] + 0.5, INSIDE[3])           # half a pixel too wide
+    assert raw_boxes_call(t, [0] * 3, 1, W, H, stride, pl, out, 16, 12, [INSIDE, bad, INSIDE],
+                          "antialias") == -5
+    # 65 rows: not without both tables in device memory
+    offs = torch.zeros(65, dtype=torch.int64, device=DEV)
+    assert raw_boxes_call(t, [0] * 65, 1, W, H, stride, pl, out, 16, 12, [INSIDE] * 65,
+                          "bilinear") == -3
+    assert raw_boxes_call(t, [0] * 65, 1, W, H, stride, pl, out, 16, 12, [INSIDE] * 65,
+                          "bilinear", offs_dev=offs.data_ptr()) == -3
+    # a row whose span leaves the buffer, among good ones
+    assert raw_boxes_call(t, [0, 1, 0], 1, W, H, stride, pl, out, 16, 12, [INSIDE] * 3,
+                          "bilinear") == -4
+    torch.cuda.synchronize()
+    assert torch.all(out == 9.0)
+    with pytest.raises(ValueError, match="antialias.*inside"):
+        vops.yuv420_to_clip(t, [0] * 3, 1, W, H, stride, pl, 16, 12, crop=[INSIDE, bad, INSIDE],
+                            filter="antialias", out=out[:3])
+    with pytest.raises(RuntimeError, match="contract"):
+        vops.yuv420_to_clip(t, [0, 1, 0], 1, W, H, stride, pl, 16, 12, crop=[INSIDE] * 3,
+                            out=out[:3])
+    torch.cuda.synchronize()
+    assert torch.all(out == 9.0)
+
+
+# -- 4. the old entry points against the new one ----------------------------------------------------------------
+@pytest.mark.parametrize("filt", vops.FILTERS)
+@pytest.mark.parametrize("matrix", vops.MATRICES)
+def test_old_entry_points_equal_the_boxed_one_with_a_uniform_box(matrix, filt):
+    """rnb_yuv420_to_clip / _aa with one box and rnb_yuv_to_clip_boxes with that
+    box in every row: bit-equal clips."""
+    y, u, v = orc.noise_planes(46, 34, 6, 77, matrix)
+    buf, stride, pl = orc.pack_i420(y, u, v, 7)
+    t = torch.from_numpy(buf).to(DEV)
+    offsets = [4 * stride, 0, 2 * stride]
+    for dtype in (torch.float32, torch.bfloat16):
+        old = vops.yuv420_to_clip(t, offsets, 2, 46, 34, stride, pl, 16, 12, crop=INSIDE,
+                                  dtype=dtype, matrix=matrix, filter=filt)
+        new = boxed(t, offsets, 2, 46, 34, stride, pl, 16, 12, [INSIDE] * 3, dtype, matrix=matrix,
+                    filter=filt)
+        assert torch.equal(old, new)
+
+
+# -- 5. decoders ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("filt", vops.FILTERS)
+def test_y4m_decoder_views_against_the_oracle(tmp_path, filt):
+    path, fr = write_y4m_file(tmp_path, 46, 34, 9, 21)
+    dec = make_decoder("y4m", DEV, filt)
+    vid, _ = dec.probe(path)
+    slot = torch.full((8, 2, 12, 16, 4), 7.0, device=DEV)
+    got = dec.decode(vid, [5, 0], out=slot[:6])
+    torch.cuda.synchronize()
+    assert got.data_ptr() == slot.data_ptr() and torch.all(slot[6:] == 7.0)
+    got = got.cpu().numpy()
+    exact = ov.boxes(46, 34, 16, 12, 13.7, 3)
+    for r, (s, k) in enumerate((s, k) for s in (5, 0) for k in range(3)):
+        y, u, v = (np.stack([fr[s + f][p] for f in range(2)]) for p in range(3))
+        ref, _, d, tol = occ.tolerance(y, u, v, 16, 12, exact[k], "bt601", "420", filt)
+        err = float(np.abs(got[r][..., :3].astype(np.float64) - ref).max())
+        print("y4m %s row %d: d = %.3g tol = %.3g err = %.3g" % (filt, r, d, tol, err))
+        assert d > 0 and tol <= orc.TOL_CEILING and err <= tol, (filt, r, err, tol)
+    # the row-indexed form, on the GPU as on the CPU
+    part = dec.decode(vid, [0, 5, 0], views=[2, 1, 0]).cpu().numpy()
+    assert np.array_equal(part, got[[5, 1, 3]])
+
+
+@pytest.mark.parametrize("kind", [d[0] for d in DECODERS if d[0] != "y4m"])
+def test_mjpeg_decoder_views_against_the_cpu_device(tmp_path, kind):
+    _, mpath = make_files(tmp_path)
+    dec, ref = make_decoder(kind, DEV), make_decoder(kind, CPU)
+    vid, _ = dec.probe(mpath)
+    want = ref.decode(ref.probe(mpath)[0], [5, 0])
+    slot = torch.full((8, 2, 12, 16, 4), 7.0, device=DEV)
+    got = dec.decode(vid, [5, 0], out=slot[:6])
+    dec.drain()
+    torch.cuda.synchronize()
+    assert got.data_ptr() == slot.data_ptr() and torch.all(slot[6:] == 7.0)
+    err = (got.cpu() - want).abs().max().item()
+    print("%s: max |gpu - cpu device| = %.3g" % (kind, err))
+    assert want.shape == (6, 2, 12, 16, 4) and err <= MIRROR_TOL, (kind, err)
+    assert dec.stats["requests"] == 1 == ref.stats["requests"]
+    assert dec.stats["uploaded_bytes"] == ref.stats["uploaded_bytes"]
+    part = dec.decode(vid, [0, 5, 0], views=[2, 1, 0])
+    dec.drain()
+    assert torch.equal(part, got[[5, 1, 3]])
+
+
+# -- 6. the shipped config ---------------------------------------------------------------------------------------------
+def test_y4m_3crop_config_end_to_end(tmp_path):
+    """configs/r2p1d-whole-y4m-3crop.json on a 3-file tree (64x48, 40 frames each;
+    short_side 112 so that the 112 x 112 window fits): every sampled video has
+    three rows per clip, at most 5 clips, and finite logits."""
+    root = tmp_path / "videos"
+    for i in range(3):
+        d = root / ("label%d" % (i % 2))
+        d.mkdir(parents=True, exist_ok=True)
+        (d / ("v%d.y4m" % i)).write_bytes(raw_y4m(64, 48, planes(64, 48, 40, 20 + i)))
+    check = tmp_path / "check"
+    check.mkdir()
+    cfg = json.load(open(os.path.join(ROOT, "configs", "r2p1d-whole-y4m-3crop.json")))
+    assert cfg["pipeline"][0]["decoder"] == "y4m" and cfg["defaults"]["crop"]["views"] == 3
+    proc, res, _ = run_cfg(tmp_path, cfg, "-v", "6", "-mi", "0", "--set", "depth=18",
+                           "--set", "warmup=1",
+                           "--set", 'crop={"short_side": 112, "views": 3}', timeout=600,
+                           env={"RNB_VIDEO_ROOT": str(root), "RNB_CHECK_DIR": str(check),
+                                "RNB_CHECK_EVERY": "1", "RNB_CHECK_MAX": "64"})
+    assert proc.returncode == 0, proc.stdout[-3000:] + proc.stderr[-3000:]
+    assert res["ok"] and res["videos_done"] >= 6, res
+    samples = [np.load(f) for f in sorted(check.glob("runner_v*.npz"))]
+    assert len(samples) >= 6, len(samples)
+    for s in samples:
+        n = len(s["starts"])
+        assert n % 3 == 0 and 3 <= n <= 15 and s["logits"].shape == (n, 400)
+        assert list(s["starts"][0::3]) == list(s["starts"][1::3]) == list(s["starts"][2::3])
+        assert 0 <= int(s["vid"]) < 3 and np.isfinite(s["logits"]).all()
