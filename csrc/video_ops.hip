@@ -7,15 +7,14 @@
 //  * rnb_preprocess      uint8 NFHWC3 -> normalised bf16 NDHWC8 (channels 3..7
 //                        zero), the fused form of the reference's
 //                        .float().permute() + slot copy.
-//  * rnb_nv12_to_clip /  decoder surfaces (NV12) or uploaded file spans (planar
-//    rnb_yuv420_to_clip  I420 of .y4m files, raw NV12) -> scaled, colour-
-//                        converted, normalised clips in the slot layout.
-//  * rnb_yuv420_to_clip_aa
-//                        the same with the antialiased triangle filter
-//                        (separable through LDS) for downscaled real frames.
+//  * rnb_nv12_to_clip    decoder surfaces (NV12) -> scaled, colour-converted,
+//                        normalised clips in the slot layout.
 //  * rnb_yuv_to_clip_boxes
-//                        both filters with a crop box per row, so that several
-//                        views of one clip read one uploaded span.
+//                        the same from uploaded file spans (planar 4:2:0 /
+//                        4:2:2 / 4:4:4 of .y4m files and JPEG surfaces, raw
+//                        NV12), bilinear or with the antialiased triangle filter
+//                        (separable through LDS), with a crop box per row, so
+//                        that several views of one clip read one uploaded span.
 //  * rnb_stem_pack       NDHWC8 -> zero-bordered pixel-pair-packed layout of
 //                        the stem conv (ops/conv.StemConv).
 //  * rnb_preprocess_packed  rnb_preprocess + rnb_stem_pack in one pass: uint8
@@ -177,16 +176,59 @@ __global__ void nv12gen_kernel(uint8_t* __restrict__ out, ClipgenArgs a,
   }
 }
 
-struct Nv12ClipArgs {
+struct NormParams {
+  float scale[3];   // 1 / (255 * std)
+  float shift[3];   // -mean / std
+};
+
+static NormParams norm_params(const float* mean, const float* stdv) {
+  NormParams n;
+  for (int c = 0; c < 3; ++c) {
+    n.scale[c] = 1.0f / (255.0f * stdv[c]);
+    n.shift[c] = -mean[c] / stdv[c];
+  }
+  return n;
+}
+
+struct ClipGeometry {
   int src_w, src_h, out_w, out_h;
+};
+
+struct Nv12ClipArgs {
+  ClipGeometry g;
   float crop_x, crop_y, crop_w, crop_h;   // source box scaled to the output
-  float scale[3], shift[3];               // normalisation (x / (255 std) - mean / std)
+  NormParams norm;
   int bf16;                               // 0: fp32 NDHWC4, 1: bf16 NDHWC8
 };
 
-static __device__ __forceinline__ uint32_t nv12_bf_bits(float f) {
+static __device__ __forceinline__ uint32_t f2bf_bits(float f) {
+  // round-to-nearest-even (inputs are finite)
   uint32_t u = __float_as_uint(f);
   return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+// What the clip kernels do with a resampled pixel: yv and the chroma samples
+// less 128 -> RGB (JFIF: full-range JFIF YCbCr, else video-range BT.601), clamp
+// to [0, 255], normalise, store as output pixel i (bf16 NDHWC8 or fp32 NDHWC4).
+// n by value: a reference into the kernel's argument struct makes the compiler
+// recompute the antialias kernel's per-plane set-up for the chroma planes.
+template <bool JFIF>
+static __device__ __forceinline__ void clip_store(float yv, float u, float v,
+                                                  const NormParams n, int bf16, void* out,
+                                                  long long i) {
+  const float yy = JFIF ? yv : 1.164f * (yv - 16.f);
+  float r = yy + (JFIF ? 1.402f : 1.596f) * v;
+  float g = yy - (JFIF ? 0.344136f : 0.392f) * u - (JFIF ? 0.714136f : 0.813f) * v;
+  float b = yy + (JFIF ? 1.772f : 2.017f) * u;
+  r = fminf(fmaxf(r, 0.f), 255.f) * n.scale[0] + n.shift[0];
+  g = fminf(fmaxf(g, 0.f), 255.f) * n.scale[1] + n.shift[1];
+  b = fminf(fmaxf(b, 0.f), 255.f) * n.scale[2] + n.shift[2];
+  if (bf16) {
+    uint16_t* o = (uint16_t*)out + i * 8;
+    *(uint4*)o = make_uint4(f2bf_bits(r) | (f2bf_bits(g) << 16), f2bf_bits(b), 0u, 0u);
+  } else {
+    *(float4*)((float*)out + i * 4) = make_float4(r, g, b, 0.f);
+  }
 }
 
 static __device__ __forceinline__ float nv12_sample(const uint8_t* __restrict__ plane, int w,
@@ -212,34 +254,22 @@ __global__ __launch_bounds__(256) void nv12_clip_kernel(const uint8_t* __restric
                                                         Nv12ClipArgs a) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= npix) return;
-  const int ohw = a.out_w * a.out_h;
+  const int ohw = a.g.out_w * a.g.out_h;
   const long long frame = i / ohw;
   const int p = (int)(i - frame * ohw);
-  const int oy = p / a.out_w, ox = p - oy * a.out_w;
-  const uint8_t* y_plane = nv12 + frame * ((long long)a.src_w * a.src_h * 3 / 2);
-  const uint8_t* uv_plane = y_plane + (long long)a.src_w * a.src_h;
+  const int oy = p / a.g.out_w, ox = p - oy * a.g.out_w;
+  const uint8_t* y_plane = nv12 + frame * ((long long)a.g.src_w * a.g.src_h * 3 / 2);
+  const uint8_t* uv_plane = y_plane + (long long)a.g.src_w * a.g.src_h;
   // output pixel centre -> source coordinate (align_corners = false)
-  const float sx = a.crop_x + ((float)ox + 0.5f) * (a.crop_w / (float)a.out_w) - 0.5f;
-  const float sy = a.crop_y + ((float)oy + 0.5f) * (a.crop_h / (float)a.out_h) - 0.5f;
-  const float yv = nv12_sample(y_plane, a.src_w, a.src_h, a.src_w, 1, 0, sx, sy);
+  const float sx = a.crop_x + ((float)ox + 0.5f) * (a.crop_w / (float)a.g.out_w) - 0.5f;
+  const float sy = a.crop_y + ((float)oy + 0.5f) * (a.crop_h / (float)a.g.out_h) - 0.5f;
+  const float yv = nv12_sample(y_plane, a.g.src_w, a.g.src_h, a.g.src_w, 1, 0, sx, sy);
   // chroma grid: half resolution, sample centres at 2x + 0.5
   const float cx = (sx + 0.5f) * 0.5f - 0.5f, cy = (sy + 0.5f) * 0.5f - 0.5f;
-  const int cw = a.src_w / 2, ch = a.src_h / 2;
-  const float u = nv12_sample(uv_plane, cw, ch, a.src_w, 2, 0, cx, cy) - 128.f;
-  const float v = nv12_sample(uv_plane, cw, ch, a.src_w, 2, 1, cx, cy) - 128.f;
-  const float yy = 1.164f * (yv - 16.f);
-  float r = yy + 1.596f * v;
-  float g = yy - 0.392f * u - 0.813f * v;
-  float b = yy + 2.017f * u;
-  r = fminf(fmaxf(r, 0.f), 255.f) * a.scale[0] + a.shift[0];
-  g = fminf(fmaxf(g, 0.f), 255.f) * a.scale[1] + a.shift[1];
-  b = fminf(fmaxf(b, 0.f), 255.f) * a.scale[2] + a.shift[2];
-  if (a.bf16) {
-    uint16_t* o = (uint16_t*)out + i * 8;
-    *(uint4*)o = make_uint4(nv12_bf_bits(r) | (nv12_bf_bits(g) << 16), nv12_bf_bits(b), 0u, 0u);
-  } else {
-    *(float4*)((float*)out + i * 4) = make_float4(r, g, b, 0.f);
-  }
+  const int cw = a.g.src_w / 2, ch = a.g.src_h / 2;
+  const float u = nv12_sample(uv_plane, cw, ch, a.g.src_w, 2, 0, cx, cy) - 128.f;
+  const float v = nv12_sample(uv_plane, cw, ch, a.g.src_w, 2, 1, cx, cy) - 128.f;
+  clip_store<false>(yv, u, v, a.norm, a.bf16, out, i);
 }
 
 // Planar / semi-planar YUV 4:2:0 frames inside an uploaded byte buffer (file
@@ -251,50 +281,29 @@ __global__ __launch_bounds__(256) void nv12_clip_kernel(const uint8_t* __restric
 // so none of these bases is aligned to more than a byte: every source access
 // is a byte load (nv12_sample), and only the output side is vectorised. The
 // launcher checked every span against the buffer length.
-#define YUV420_MAX_CLIPS 32
-struct Yuv420ClipArgs {
-  Nv12ClipArgs g;                          // geometry, crop, normalisation, dtype
-  int F, y_stride, u_stride, v_stride, c_step;
-  long long frame_stride, y_off, u_off, v_off;
-  long long offs[YUV420_MAX_CLIPS];        // per-clip base (FROM_ARRAY: unused)
-};
-
-// The boxed form (PER_CLIP_BOX) of the two clip kernels: row c of the launch
-// reads the frames at offs[c] through its own crop box, so several views of one
-// clip share one uploaded span (rows may repeat an offset). Up to
-// YUV_BOX_MAX_ROWS rows travel in the kernel arguments, offset (8 B) next to box
-// (16 B, one s_load_dwordx4): 1536 B of tables, 1664 B in all, under the 4 KB
-// of a dispatch packet's argument segment. 64, not 32, because a 15-clip request
+//
+// Row c of a launch reads the frames at offs[c] through its own crop box, so
+// several views of one clip share one uploaded span (rows may repeat an offset).
+// Up to YUV_BOX_MAX_ROWS rows travel in the kernel arguments, offset (8 B) next
+// to box (16 B, one s_load_dwordx4): 1536 B of tables, 1648 B in all, under the
+// 4 KB of a dispatch packet's argument segment. 64, because a 15-clip request
 // with three views is 45 rows. More rows read both tables from device memory
-// (offs, boxes_dev). g.crop_* are unused.
+// (offs, boxes_dev). The row is uniform per block: scalar loads either way.
 #define YUV_BOX_MAX_ROWS 64
 struct __attribute__((aligned(16))) YuvBox {
   float x, y, w, h;                        // luma pixels, as Nv12ClipArgs.crop_*
 };
-struct Yuv420BoxArgs {
-  Nv12ClipArgs g;
+struct YuvClipArgs {
+  ClipGeometry g;
+  NormParams norm;
+  int bf16;                                // 0: fp32 NDHWC4, 1: bf16 NDHWC8
   int F, y_stride, u_stride, v_stride, c_step;
   long long frame_stride, y_off, u_off, v_off;
   const YuvBox* boxes_dev;                 // FROM_ARRAY: per-row boxes (else unused)
   long long offs[YUV_BOX_MAX_ROWS];        // per-row base (FROM_ARRAY: unused)
   YuvBox boxes[YUV_BOX_MAX_ROWS];          // per-row box (FROM_ARRAY: unused)
 };
-static_assert(sizeof(Yuv420BoxArgs) <= 2048, "boxed clip arguments outgrew their budget");
-
-template <bool PER_CLIP_BOX>
-struct YuvClipArgsOf { typedef Yuv420ClipArgs type; };
-template <>
-struct YuvClipArgsOf<true> { typedef Yuv420BoxArgs type; };
-
-// the crop box of block row `clip`: the launch's one box, or the row's own (a
-// uniform address either way: scalar loads). `a` is the kernel's own argument.
-#define YUV_CLIP_BOX(box, a, clip)                                              \
-  YuvBox box;                                                                   \
-  if constexpr (PER_CLIP_BOX) {                                                 \
-    box = FROM_ARRAY ? a.boxes_dev[clip] : a.boxes[clip];                       \
-  } else {                                                                      \
-    box.x = a.g.crop_x; box.y = a.g.crop_y; box.w = a.g.crop_w; box.h = a.g.crop_h; \
-  }
+static_assert(sizeof(YuvClipArgs) <= 2048, "clip arguments outgrew their budget");
 
 // JFIF: full-range JFIF YCbCr (what JPEG frames hold) instead of the video-range
 // BT.601 matrix; the chroma planes of an odd-sized frame then round up.
@@ -336,10 +345,10 @@ static __device__ __forceinline__ float bilinear_fetch(const uint8_t* __restrict
   return top + (bot - top) * t.fy;
 }
 
-template <bool FROM_ARRAY, bool JFIF, int HS = 2, int VS = 2, bool PER_CLIP_BOX = false>
+template <bool FROM_ARRAY, bool JFIF, int HS, int VS>
 __global__ __launch_bounds__(256) void yuv420_clip_kernel(
     const uint8_t* __restrict__ buf, const long long* __restrict__ offs, void* __restrict__ out,
-    typename YuvClipArgsOf<PER_CLIP_BOX>::type a) {
+    YuvClipArgs a) {
   // grid = (pixel blocks of one frame, F, nclips): frame and clip are uniform
   // per block, so the base offset is one scalar load and no thread divides a
   // 64-bit pixel index (the cost of a flat grid: two such divisions per pixel)
@@ -350,7 +359,7 @@ __global__ __launch_bounds__(256) void yuv420_clip_kernel(
   const long long i = ((long long)clip * a.F + f) * ohw + p;
   const int oy = p / a.g.out_w, ox = p - oy * a.g.out_w;
   const uint8_t* fr = buf + (FROM_ARRAY ? offs[clip] : a.offs[clip]) + f * a.frame_stride;
-  YUV_CLIP_BOX(box, a, clip)
+  const YuvBox box = FROM_ARRAY ? a.boxes_dev[clip] : a.boxes[clip];
   // the arithmetic below is nv12_clip_kernel's, expression for expression
   const float sx = box.x + ((float)ox + 0.5f) * (box.w / (float)a.g.out_w) - 0.5f;
   const float sy = box.y + ((float)oy + 0.5f) * (box.h / (float)a.g.out_h) - 0.5f;
@@ -368,19 +377,7 @@ __global__ __launch_bounds__(256) void yuv420_clip_kernel(
     u = nv12_sample(fr + a.u_off, cw, ch, a.u_stride, a.c_step, 0, cx, cy) - 128.f;
     v = nv12_sample(fr + a.v_off, cw, ch, a.v_stride, a.c_step, 0, cx, cy) - 128.f;
   }
-  const float yy = JFIF ? yv : 1.164f * (yv - 16.f);
-  float r = yy + (JFIF ? 1.402f : 1.596f) * v;
-  float g = yy - (JFIF ? 0.344136f : 0.392f) * u - (JFIF ? 0.714136f : 0.813f) * v;
-  float b = yy + (JFIF ? 1.772f : 2.017f) * u;
-  r = fminf(fmaxf(r, 0.f), 255.f) * a.g.scale[0] + a.g.shift[0];
-  g = fminf(fmaxf(g, 0.f), 255.f) * a.g.scale[1] + a.g.shift[1];
-  b = fminf(fmaxf(b, 0.f), 255.f) * a.g.scale[2] + a.g.shift[2];
-  if (a.g.bf16) {
-    uint16_t* o = (uint16_t*)out + i * 8;
-    *(uint4*)o = make_uint4(nv12_bf_bits(r) | (nv12_bf_bits(g) << 16), nv12_bf_bits(b), 0u, 0u);
-  } else {
-    *(float4*)((float*)out + i * 4) = make_float4(r, g, b, 0.f);
-  }
+  clip_store<JFIF>(yv, u, v, a.norm, a.bf16, out, i);
 }
 
 // The antialiased form of yuv420_clip_kernel: the same inputs, mapping, colour
@@ -489,10 +486,10 @@ static __device__ __forceinline__ void aa_plane(const uint8_t* __restrict__ plan
   for (int k = 0; k < AA_PX; ++k) res[k] = wsum[k] > 0.f ? acc[k] / wsum[k] : 0.f;
 }
 
-template <bool FROM_ARRAY, bool JFIF, int HS = 2, int VS = 2, bool PER_CLIP_BOX = false>
+template <bool FROM_ARRAY, bool JFIF, int HS, int VS>
 __global__ __launch_bounds__(256) void yuv420_clip_aa_kernel(
     const uint8_t* __restrict__ buf, const long long* __restrict__ offs, void* __restrict__ out,
-    typename YuvClipArgsOf<PER_CLIP_BOX>::type a) {
+    YuvClipArgs a) {
   // grid = (column tiles x row bands of one frame, F, nclips): frame and clip are
   // uniform per block, as in yuv420_clip_kernel
   __shared__ float rows_lds[AA_CH * AA_TW];
@@ -512,7 +509,7 @@ __global__ __launch_bounds__(256) void yuv420_clip_aa_kernel(
     oy[k] = r < th ? oy0 + r : -1;
   }
   const int cw = chroma_dim<HS>(a.g.src_w, JFIF), ch = chroma_dim<VS>(a.g.src_h, JFIF);
-  YUV_CLIP_BOX(box, a, clip)
+  const YuvBox box = FROM_ARRAY ? a.boxes_dev[clip] : a.boxes[clip];
   float yv[AA_PX], u[AA_PX], v[AA_PX];
   aa_plane(fr + a.y_off, a.g.src_w, a.g.src_h, a.y_stride, 1, box.x, box.y,
            box.w, box.h, a.g.out_w, a.g.out_h, x0, tw, oy0, th, cx, oy, rows_lds, yv);
@@ -531,32 +528,8 @@ __global__ __launch_bounds__(256) void yuv420_clip_aa_kernel(
   for (int k = 0; k < AA_PX; ++k) {
     if (oy[k] < 0) continue;
     const long long i = frame_px + (long long)oy[k] * a.g.out_w + x0 + cx[k];
-    const float uu = u[k] - 128.f, vv = v[k] - 128.f;
-    const float yy = JFIF ? yv[k] : 1.164f * (yv[k] - 16.f);
-    float r = yy + (JFIF ? 1.402f : 1.596f) * vv;
-    float g = yy - (JFIF ? 0.344136f : 0.392f) * uu - (JFIF ? 0.714136f : 0.813f) * vv;
-    float b = yy + (JFIF ? 1.772f : 2.017f) * uu;
-    r = fminf(fmaxf(r, 0.f), 255.f) * a.g.scale[0] + a.g.shift[0];
-    g = fminf(fmaxf(g, 0.f), 255.f) * a.g.scale[1] + a.g.shift[1];
-    b = fminf(fmaxf(b, 0.f), 255.f) * a.g.scale[2] + a.g.shift[2];
-    if (a.g.bf16) {
-      uint16_t* o = (uint16_t*)out + i * 8;
-      *(uint4*)o = make_uint4(nv12_bf_bits(r) | (nv12_bf_bits(g) << 16), nv12_bf_bits(b), 0u, 0u);
-    } else {
-      *(float4*)((float*)out + i * 4) = make_float4(r, g, b, 0.f);
-    }
+    clip_store<JFIF>(yv[k], u[k] - 128.f, v[k] - 128.f, a.norm, a.bf16, out, i);
   }
-}
-
-struct NormParams {
-  float scale[3];   // 1 / (255 * std)
-  float shift[3];   // -mean / std
-};
-
-static __device__ __forceinline__ uint32_t f2bf_bits(float f) {
-  // round-to-nearest-even (inputs are finite)
-  uint32_t u = __float_as_uint(f);
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
 }
 
 // one thread per 4 pixels: 12 bytes in (three aligned dword loads), 4 x 16 B
@@ -835,10 +808,10 @@ __global__ __launch_bounds__(256) void head_pool_f32_kernel(const float* __restr
   *(float4*)(pooled + (size_t)n * C + c) = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
 }
 
-// yuv420_to_clip_launch's choice among the instantiations of the two clip kernels
+// rnb_yuv_to_clip_boxes' choice among the instantiations of the two clip kernels
 template <bool FROM_ARRAY, bool JFIF, int HS, int VS>
-static void yuv_clip_run(bool aa, dim3 grid, hipStream_t stream, const uint8_t* buf,
-                         const long long* table, void* out, const Yuv420ClipArgs& a) {
+static void yuv_box_run(bool aa, dim3 grid, hipStream_t stream, const uint8_t* buf,
+                        const long long* table, void* out, const YuvClipArgs& a) {
   if (aa)
     hipLaunchKernelGGL((yuv420_clip_aa_kernel<FROM_ARRAY, JFIF, HS, VS>), grid, dim3(256), 0,
                        stream, buf, table, out, a);
@@ -848,49 +821,12 @@ static void yuv_clip_run(bool aa, dim3 grid, hipStream_t stream, const uint8_t* 
 }
 
 template <bool FROM_ARRAY, bool JFIF>
-static void yuv_clip_run_sampling(int sampling, bool aa, dim3 grid, hipStream_t stream,
-                                  const uint8_t* buf, const long long* table, void* out,
-                                  const Yuv420ClipArgs& a) {
-  if (sampling == 0) yuv_clip_run<FROM_ARRAY, JFIF, 2, 2>(aa, grid, stream, buf, table, out, a);
-  else if (sampling == 1) yuv_clip_run<FROM_ARRAY, JFIF, 2, 1>(aa, grid, stream, buf, table, out, a);
-  else yuv_clip_run<FROM_ARRAY, JFIF, 1, 1>(aa, grid, stream, buf, table, out, a);
-}
-
-// the same choice among the boxed (PER_CLIP_BOX) instantiations
-template <bool FROM_ARRAY, bool JFIF, int HS, int VS>
-static void yuv_box_run(bool aa, dim3 grid, hipStream_t stream, const uint8_t* buf,
-                        const long long* table, void* out, const Yuv420BoxArgs& a) {
-  if (aa)
-    hipLaunchKernelGGL((yuv420_clip_aa_kernel<FROM_ARRAY, JFIF, HS, VS, true>), grid, dim3(256),
-                       0, stream, buf, table, out, a);
-  else
-    hipLaunchKernelGGL((yuv420_clip_kernel<FROM_ARRAY, JFIF, HS, VS, true>), grid, dim3(256), 0,
-                       stream, buf, table, out, a);
-}
-
-template <bool FROM_ARRAY, bool JFIF>
 static void yuv_box_run_sampling(int sampling, bool aa, dim3 grid, hipStream_t stream,
                                  const uint8_t* buf, const long long* table, void* out,
-                                 const Yuv420BoxArgs& a) {
+                                 const YuvClipArgs& a) {
   if (sampling == 0) yuv_box_run<FROM_ARRAY, JFIF, 2, 2>(aa, grid, stream, buf, table, out, a);
   else if (sampling == 1) yuv_box_run<FROM_ARRAY, JFIF, 2, 1>(aa, grid, stream, buf, table, out, a);
   else yuv_box_run<FROM_ARRAY, JFIF, 1, 1>(aa, grid, stream, buf, table, out, a);
-}
-
-// the fields Yuv420ClipArgs and Yuv420BoxArgs share
-template <typename Args>
-static void yuv_clip_fill(Args& a, int F, int src_w, int src_h, long long frame_stride,
-                          const long long* plane_off, const int* plane_stride, int c_step,
-                          int out_w, int out_h, const float* mean, const float* stdv, int bf16) {
-  a.g.src_w = src_w; a.g.src_h = src_h; a.g.out_w = out_w; a.g.out_h = out_h;
-  for (int c = 0; c < 3; ++c) {
-    a.g.scale[c] = 1.0f / (255.0f * stdv[c]);
-    a.g.shift[c] = -mean[c] / stdv[c];
-  }
-  a.g.bf16 = bf16;
-  a.F = F; a.c_step = c_step; a.frame_stride = frame_stride;
-  a.y_off = plane_off[0]; a.u_off = plane_off[1]; a.v_off = plane_off[2];
-  a.y_stride = plane_stride[0]; a.u_stride = plane_stride[1]; a.v_stride = plane_stride[2];
 }
 
 extern "C" {
@@ -962,12 +898,9 @@ int rnb_nv12_to_clip(const void* nv12, void* out, long long frames, int src_w, i
   if (src_w % 2 || src_h % 2 || out_w <= 0 || out_h <= 0) return -2;
   if (((uintptr_t)out & 15u) != 0) return -2;
   Nv12ClipArgs a;
-  a.src_w = src_w; a.src_h = src_h; a.out_w = out_w; a.out_h = out_h;
+  a.g.src_w = src_w; a.g.src_h = src_h; a.g.out_w = out_w; a.g.out_h = out_h;
   a.crop_x = crop[0]; a.crop_y = crop[1]; a.crop_w = crop[2]; a.crop_h = crop[3];
-  for (int c = 0; c < 3; ++c) {
-    a.scale[c] = 1.0f / (255.0f * stdv[c]);
-    a.shift[c] = -mean[c] / stdv[c];
-  }
+  a.norm = norm_params(mean, stdv);
   a.bf16 = bf16;
   const long long npix = frames * out_w * out_h;
   hipLaunchKernelGGL(nv12_clip_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0,
@@ -975,7 +908,7 @@ int rnb_nv12_to_clip(const void* nv12, void* out, long long frames, int src_w, i
   return (int)hipGetLastError();
 }
 
-// everything the clip launchers check but the crop boxes (0: fine). tables_ok:
+// everything the clip launcher checks but the crop boxes (0: fine). tables_ok:
 // the rows fit the kernel arguments, or their tables are in device memory.
 static int yuv_clip_check(long long buf_len, const long long* offs, int nclips, bool tables_ok,
                           int F, int src_w, int src_h, long long frame_stride,
@@ -1021,99 +954,25 @@ static dim3 yuv_clip_grid(int filter, int out_w, int out_h, int F, int nclips) {
   return dim3((unsigned)(filter ? tiles : (ohw + 255) / 256), (unsigned)F, (unsigned)nclips);
 }
 
-// buf: buf_len uploaded bytes; clip c's F frames start at offs[c] (host copy,
-// checked here) and are frame_stride bytes apart; plane_off / plane_stride:
-// byte offset within a frame and row stride of Y, U, V; c_step: bytes between
-// chroma samples (1 planar, 2 interleaved). out: [nclips][F][oh][ow][4] fp32 or
-// [..][8] bf16. Up to YUV420_MAX_CLIPS offsets travel in the kernel arguments;
-// more need offs_dev, the same table in device memory. -4: a frame or a span
-// would reach outside its frame stride / the buffer (nothing is launched).
-// matrix: 0 BT.601 video range (even frame sizes), 1 full-range JFIF (any size;
-// chroma planes of ceil(w / 2) x ceil(h / 2)).
-// filter: 0 the two-tap bilinear kernel, 1 the antialiased triangle filter
-// (yuv420_clip_aa_kernel), which also needs the crop box inside the frame: -5.
+// buf: buf_len uploaded bytes; row c of the launch reads the F frames that start
+// at offs[c] (host copy, checked here) and are frame_stride bytes apart, through
+// the crop box boxes[c] = (x, y, w, h), so the views of one clip share its
+// uploaded span (rows may repeat an offset, in any order). plane_off /
+// plane_stride: byte offset within a frame and row stride of Y, U, V; c_step:
+// bytes between chroma samples (1 planar, 2 interleaved). out:
+// [nclips][F][oh][ow][4] fp32 or [..][8] bf16. Up to YUV_BOX_MAX_ROWS rows travel
+// in the kernel arguments; more need offs_dev AND boxes_dev, both tables in
+// device memory (-3 otherwise). -4: a frame or a span would reach outside its
+// frame stride / the buffer (nothing is launched).
+// matrix: 0 BT.601 video range, 1 full-range JFIF (any size).
+// filter: 0 the two-tap bilinear kernel, which takes any box, 1 the antialiased
+// triangle filter (yuv420_clip_aa_kernel), which needs every box inside
+// [0, src_w] x [0, src_h] (a row of weights could be empty), else -5 and nothing
+// is launched.
 // sampling: 0 4:2:0 (luma factors 2x2), 1 4:2:2 (2x1), 2 4:4:4 (1x1); the chroma
 // planes are ceil(w / Hs) x ceil(h / Vs) under JFIF and w / Hs x h / Vs under
 // BT.601, which needs an even size only along an axis with factor 2.
-static int yuv420_to_clip_launch(const void* buf, long long buf_len, const long long* offs,
-                                 const void* offs_dev, int nclips, int F, int src_w, int src_h,
-                                 long long frame_stride, const long long* plane_off,
-                                 const int* plane_stride, int c_step, void* out, int out_w,
-                                 int out_h, const float* crop, const float* mean,
-                                 const float* stdv, int bf16, int matrix, int filter,
-                                 int sampling, hipStream_t stream) {
-  if (nclips <= 0) return 0;
-  const int rc = yuv_clip_check(buf_len, offs, nclips, nclips <= YUV420_MAX_CLIPS || offs_dev, F,
-                                src_w, src_h, frame_stride, plane_off, plane_stride, c_step, out,
-                                out_w, out_h, matrix, filter, sampling);
-  if (rc) return rc;
-  if (filter && !yuv_clip_box_inside(crop, src_w, src_h)) return -5;
-  Yuv420ClipArgs a;
-  yuv_clip_fill(a, F, src_w, src_h, frame_stride, plane_off, plane_stride, c_step, out_w, out_h,
-                mean, stdv, bf16);
-  a.g.crop_x = crop[0]; a.g.crop_y = crop[1]; a.g.crop_w = crop[2]; a.g.crop_h = crop[3];
-  const bool in_args = nclips <= YUV420_MAX_CLIPS;
-  for (int c = 0; c < YUV420_MAX_CLIPS; ++c) a.offs[c] = in_args && c < nclips ? offs[c] : 0;
-  const long long* table = in_args ? (const long long*)nullptr : (const long long*)offs_dev;
-  const dim3 grid = yuv_clip_grid(filter, out_w, out_h, F, nclips);
-  const uint8_t* src = (const uint8_t*)buf;
-  const bool aa = filter != 0;
-  if (in_args) {
-    if (matrix) yuv_clip_run_sampling<false, true>(sampling, aa, grid, stream, src, table, out, a);
-    else yuv_clip_run_sampling<false, false>(sampling, aa, grid, stream, src, table, out, a);
-  } else {
-    if (matrix) yuv_clip_run_sampling<true, true>(sampling, aa, grid, stream, src, table, out, a);
-    else yuv_clip_run_sampling<true, false>(sampling, aa, grid, stream, src, table, out, a);
-  }
-  return (int)hipGetLastError();
-}
-
-int rnb_yuv420_to_clip(const void* buf, long long buf_len, const long long* offs,
-                       const void* offs_dev, int nclips, int F, int src_w, int src_h,
-                       long long frame_stride, const long long* plane_off,
-                       const int* plane_stride, int c_step, void* out, int out_w, int out_h,
-                       const float* crop, const float* mean, const float* stdv, int bf16,
-                       int matrix, hipStream_t stream) {
-  return yuv420_to_clip_launch(buf, buf_len, offs, offs_dev, nclips, F, src_w, src_h,
-                               frame_stride, plane_off, plane_stride, c_step, out, out_w, out_h,
-                               crop, mean, stdv, bf16, matrix, 0, 0, stream);
-}
-
-// The same arguments and checks; the antialiased triangle filter. -5: the crop
-// box does not lie inside [0, src_w] x [0, src_h] (a row of weights could be empty).
-int rnb_yuv420_to_clip_aa(const void* buf, long long buf_len, const long long* offs,
-                          const void* offs_dev, int nclips, int F, int src_w, int src_h,
-                          long long frame_stride, const long long* plane_off,
-                          const int* plane_stride, int c_step, void* out, int out_w, int out_h,
-                          const float* crop, const float* mean, const float* stdv, int bf16,
-                          int matrix, hipStream_t stream) {
-  return yuv420_to_clip_launch(buf, buf_len, offs, offs_dev, nclips, F, src_w, src_h,
-                               frame_stride, plane_off, plane_stride, c_step, out, out_w, out_h,
-                               crop, mean, stdv, bf16, matrix, 1, 0, stream);
-}
-
-// rnb_yuv420_to_clip / rnb_yuv420_to_clip_aa for any of the three chroma
-// layouts. filter: 0 bilinear, 1 antialias; sampling: 0 4:2:0, 1 4:2:2, 2 4:4:4
-// (anything else: -2). With sampling 0 it is the entry points above.
-int rnb_yuv_to_clip(const void* buf, long long buf_len, const long long* offs,
-                    const void* offs_dev, int nclips, int F, int src_w, int src_h,
-                    long long frame_stride, const long long* plane_off, const int* plane_stride,
-                    int c_step, void* out, int out_w, int out_h, const float* crop,
-                    const float* mean, const float* stdv, int bf16, int matrix, int filter,
-                    int sampling, hipStream_t stream) {
-  if (filter != 0 && filter != 1) return -2;
-  return yuv420_to_clip_launch(buf, buf_len, offs, offs_dev, nclips, F, src_w, src_h,
-                               frame_stride, plane_off, plane_stride, c_step, out, out_w, out_h,
-                               crop, mean, stdv, bf16, matrix, filter, sampling, stream);
-}
-
-// rnb_yuv_to_clip with a crop box per row: row c reads the F frames at offs[c]
-// through boxes[c] = (x, y, w, h), so the views of one clip share its uploaded
-// span (rows may repeat an offset, in any order). The checks are
-// yuv420_to_clip_launch's, per row. Up to YUV_BOX_MAX_ROWS rows travel in the
-// kernel arguments; more need offs_dev AND boxes_dev, both tables in device
-// memory (-3 otherwise). filter 1: every box inside [0, src_w] x [0, src_h], else
-// -5 and nothing is launched; the bilinear filter takes any box.
+// Anything else in matrix, filter or sampling: -2.
 int rnb_yuv_to_clip_boxes(const void* buf, long long buf_len, const long long* offs,
                           const void* offs_dev, int nclips, int F, int src_w, int src_h,
                           long long frame_stride, const long long* plane_off,
@@ -1132,10 +991,13 @@ int rnb_yuv_to_clip_boxes(const void* buf, long long buf_len, const long long* o
   if (filter)
     for (int c = 0; c < nclips; ++c)
       if (!yuv_clip_box_inside(boxes + 4 * c, src_w, src_h)) return -5;
-  Yuv420BoxArgs a;
-  yuv_clip_fill(a, F, src_w, src_h, frame_stride, plane_off, plane_stride, c_step, out_w, out_h,
-                mean, stdv, bf16);
-  a.g.crop_x = a.g.crop_y = a.g.crop_w = a.g.crop_h = 0.f;
+  YuvClipArgs a;
+  a.g.src_w = src_w; a.g.src_h = src_h; a.g.out_w = out_w; a.g.out_h = out_h;
+  a.norm = norm_params(mean, stdv);
+  a.bf16 = bf16;
+  a.F = F; a.c_step = c_step; a.frame_stride = frame_stride;
+  a.y_off = plane_off[0]; a.u_off = plane_off[1]; a.v_off = plane_off[2];
+  a.y_stride = plane_stride[0]; a.u_stride = plane_stride[1]; a.v_stride = plane_stride[2];
   a.boxes_dev = in_args ? (const YuvBox*)nullptr : (const YuvBox*)boxes_dev;
   for (int c = 0; c < YUV_BOX_MAX_ROWS; ++c) {
     const bool live = in_args && c < nclips;
@@ -1162,11 +1024,7 @@ int rnb_yuv_to_clip_boxes(const void* buf, long long buf_len, const long long* o
 int rnb_preprocess(const void* in, void* out, long long npix, const float* mean,
                    const float* stdv, hipStream_t stream) {
   if (npix <= 0) return 0;
-  NormParams np;
-  for (int c = 0; c < 3; ++c) {
-    np.scale[c] = 1.0f / (255.0f * stdv[c]);
-    np.shift[c] = -mean[c] / stdv[c];
-  }
+  const NormParams np = norm_params(mean, stdv);
   if (((uintptr_t)in & 3u) != 0) return -2;         // dword loads of 4-pixel groups
   const int block = 256;
   const long long grid = ((npix + 3) / 4 + block - 1) / block;
@@ -1218,11 +1076,7 @@ int rnb_preprocess_packed(const void* in, void* out, long long frames, int H, in
   if (frames <= 0) return 0;
   if (W % 2 != 0 || H <= 0 || W <= 0) return -2;
   if ((((uintptr_t)out) & 15u) != 0) return -2;
-  NormParams np;
-  for (int c = 0; c < 3; ++c) {
-    np.scale[c] = 1.0f / (255.0f * stdv[c]);
-    np.shift[c] = -mean[c] / stdv[c];
-  }
+  const NormParams np = norm_params(mean, stdv);
   const int Hp = H + 6, Wq = (W + 6) / 2;
   const long long nout = frames * Hp * Wq;
   hipLaunchKernelGGL(preprocess_packed_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256),
@@ -1233,11 +1087,7 @@ int rnb_preprocess_packed(const void* in, void* out, long long frames, int H, in
 int rnb_preprocess_f32(const void* in, void* out, long long npix, const float* mean,
                        const float* stdv, hipStream_t stream) {
   if (npix <= 0) return 0;
-  NormParams np;
-  for (int c = 0; c < 3; ++c) {
-    np.scale[c] = 1.0f / (255.0f * stdv[c]);
-    np.shift[c] = -mean[c] / stdv[c];
-  }
+  const NormParams np = norm_params(mean, stdv);
   if (((uintptr_t)in & 3u) != 0 || ((uintptr_t)out & 15u) != 0) return -2;
   const int block = 256;
   const long long grid = ((npix + 3) / 4 + block - 1) / block;

@@ -25,6 +25,7 @@ Every decoder returns NDHWC clips normalised with the Kinetics mean/std:
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import mmap
 import numbers
@@ -49,8 +50,8 @@ class Decoder:
         raise NotImplementedError
 
     def empty(self):
-        c = vops.IN_CHANNELS_P_F32 if self.dtype == torch.float32 else vops.IN_CHANNELS_P
-        return torch.zeros((0, self.F, self.H, self.W, c), dtype=self.dtype, device=self.device)
+        return torch.zeros((0, self.F, self.H, self.W, vops.clip_channels(self.dtype)),
+                           dtype=self.dtype, device=self.device)
 
     def warmup(self, n: int) -> None:
         """Run the decode kernels once per warm-up round (no probe needed)."""
@@ -123,10 +124,9 @@ class SyntheticDecoder(Decoder):
             surf = self._surface[:n * self.F]
         surf = vops.nv12gen(int(vid), list(starts), self.F, self.src_h, self.src_w,
                             self.device, out=surf)
-        C = vops.IN_CHANNELS_P_F32 if self.dtype == torch.float32 else vops.IN_CHANNELS_P
         if out is None:
-            out = torch.empty((n, self.F, self.H, self.W, C), dtype=self.dtype,
-                              device=self.device)
+            out = torch.empty((n, self.F, self.H, self.W, vops.clip_channels(self.dtype)),
+                              dtype=self.dtype, device=self.device)
         vops.nv12_to_clip(surf, self.src_w, self.src_h, self.W, self.H, dtype=self.dtype,
                           out=out)
         return out
@@ -289,6 +289,38 @@ class _StagedFileDecoder(Decoder):
         self._next = 0
 
     # -- files ------------------------------------------------------------
+    EMPTY_FIELD = None       # the field an empty file is reported under
+
+    def _parse(self, path: str, mm, data):
+        """Header / index of the file just mapped (``mm``: the map, ``data``: its
+        uint8 view); ``ValueError`` naming file and field for what is not read."""
+        raise NotImplementedError
+
+    def probe(self, path):
+        vid = self._ids.get(path)
+        if vid is not None:
+            return vid, self._videos[vid][1].num_frames
+        if os.path.getsize(path) == 0:
+            raise ValueError("%s: empty file (field %r)" % (path, self.EMPTY_FIELD))
+        vid = len(self._ids)
+        mm, data = self._map(vid, path)
+        try:
+            hdr = self._parse(path, mm, data)
+            boxes = self._probe_boxes(path, hdr)
+        except ValueError:
+            del self._maps[vid]
+            raise
+        self._ids[path] = vid
+        self._videos[vid] = (path, hdr)
+        self._boxes[vid] = boxes
+        return vid, hdr.num_frames
+
+    def _check_starts(self, path: str, starts, num_frames: int) -> None:
+        for s in starts:
+            if s < 0 or s + self.F > num_frames:
+                raise ValueError("%s: clip at frame %d (+%d) is outside the %d frames"
+                                 % (path, s, self.F, num_frames))
+
     def _map(self, vid: int, path: str):
         got = self._maps.get(vid)
         if got is not None:
@@ -375,11 +407,30 @@ class _StagedFileDecoder(Decoder):
         e.acquire()
         return e
 
+    @contextlib.contextmanager
+    def _staged(self, nbytes: int, cpu_nbytes: Optional[int] = None):
+        """``(entry, host, buf)`` for a request: on a CUDA device a ring entry of
+        ``nbytes`` (the ring's size for such requests), its pinned bytes and its
+        device copy; on a CPU device ``None``, a fresh buffer of ``cpu_nbytes``
+        (the request's own size; default ``nbytes``) and its tensor view. On exit
+        the entry's event is recorded, also behind the uploads and kernels of a
+        request that raised."""
+        if self.device.type != "cuda":
+            host = np.empty(nbytes if cpu_nbytes is None else cpu_nbytes, dtype=np.uint8)
+            yield None, host, torch.from_numpy(host)
+            return
+        entry = self._entry(nbytes)
+        try:
+            yield entry, entry.host, entry.dev
+        finally:
+            entry.event.record(torch.cuda.current_stream(self.device))
+            entry.in_flight = True
+
     def _out(self, n: int, out):
         if out is not None:
             return out
-        C = vops.IN_CHANNELS_P_F32 if self.dtype == torch.float32 else vops.IN_CHANNELS_P
-        return torch.empty((n, self.F, self.H, self.W, C), dtype=self.dtype, device=self.device)
+        return torch.empty((n, self.F, self.H, self.W, vops.clip_channels(self.dtype)),
+                           dtype=self.dtype, device=self.device)
 
 
 class Y4mDecoder(_StagedFileDecoder):
@@ -419,28 +470,10 @@ class Y4mDecoder(_StagedFileDecoder):
 
     _PLANES = {"420": vops.i420_planes, "422": vops.i422_planes, "444": vops.i444_planes}
 
-    def probe(self, path):
-        vid = self._ids.get(path)
-        if vid is not None:
-            return vid, self._videos[vid][1].num_frames
-        if os.path.getsize(path) == 0:
-            raise ValueError("%s: empty file (field 'magic')" % path)
-        vid = len(self._ids)
-        mm, _ = self._map(vid, path)
-        try:
-            hdr = y4m.read_header(path, data=mm)
-        except ValueError:
-            del self._maps[vid]
-            raise
-        try:
-            boxes = self._probe_boxes(path, hdr)
-        except ValueError:
-            del self._maps[vid]
-            raise
-        self._ids[path] = vid
-        self._videos[vid] = (path, hdr)
-        self._boxes[vid] = boxes
-        return vid, hdr.num_frames
+    EMPTY_FIELD = "magic"
+
+    def _parse(self, path, mm, data):
+        return y4m.read_header(path, data=mm)
 
     def warmup(self, n: int) -> None:
         """Run the clip kernel on a zeroed upload buffer (no file needed)."""
@@ -448,16 +481,14 @@ class Y4mDecoder(_StagedFileDecoder):
             return
         W, H = self.WARMUP_W, self.WARMUP_H
         stride = len(y4m.FRAME_MARKER) + vops.nv12_frame_bytes(W, H)
+        offsets, crop = self._warm_crop(W, H)
         for i in range(n):
-            e = self._entry(15 * self.F * stride)
-            e.dev[:self.F * stride].zero_()
-            offsets, crop = self._warm_crop(W, H)
-            vops.yuv420_to_clip(e.dev, offsets, self.F, W, H, stride,
-                                vops.i420_planes(W, H, len(y4m.FRAME_MARKER)), self.W,
-                                self.H, crop=crop, dtype=self.dtype,
-                                out=self._out(len(offsets), None), filter=self.filter)
-            e.event.record(torch.cuda.current_stream(self.device))
-            e.in_flight = True
+            with self._staged(15 * self.F * stride) as (_, _, buf):
+                buf[:self.F * stride].zero_()
+                vops.yuv420_to_clip(buf, offsets, self.F, W, H, stride,
+                                    vops.i420_planes(W, H, len(y4m.FRAME_MARKER)), self.W,
+                                    self.H, crop=crop, dtype=self.dtype,
+                                    out=self._out(len(offsets), None), filter=self.filter)
 
     # -- decode ---------------------------------------------------------------
     def decode(self, vid, starts, out=None, views=None):
@@ -472,20 +503,10 @@ class Y4mDecoder(_StagedFileDecoder):
         _, data = self._map(vid, path)
         span = self.F * hdr.frame_stride
         marker = np.frombuffer(y4m.FRAME_MARKER, dtype=np.uint8)
-        for s in starts:
-            if s < 0 or s + self.F > hdr.num_frames:
-                raise ValueError("%s: clip at frame %d (+%d) is outside the %d frames"
-                                 % (path, s, self.F, hdr.num_frames))
+        self._check_starts(path, starts, hdr.num_frames)
         planes = self._PLANES[hdr.sampling](hdr.width, hdr.height, len(y4m.FRAME_MARKER))
         offsets, crop = self._clip_args(vid, hdr, rows, span)
-        cuda = self.device.type == "cuda"
-        if cuda:
-            entry = self._entry(max(n, 15) * span)
-            host, buf = entry.host, entry.dev
-        else:
-            host = np.empty(n * span, dtype=np.uint8)
-            buf = torch.from_numpy(host)
-        try:
+        with self._staged(max(n, 15) * span, n * span) as (entry, host, buf):
             for i, s in enumerate(starts):
                 a = hdr.frame_offset(s)
                 dst = host[i * span:(i + 1) * span]
@@ -496,7 +517,7 @@ class Y4mDecoder(_StagedFileDecoder):
                     raise ValueError("%s: frame %d does not start with a bare FRAME marker "
                                      "(field 'FRAME': %r); frame parameters are not supported"
                                      % (path, s + bad, bytes(heads[bad])))
-                if cuda:     # this clip uploads while the next one is staged
+                if entry is not None:     # this clip uploads while the next one is staged
                     buf[i * span:(i + 1) * span].copy_(
                         entry.pinned[i * span:(i + 1) * span], non_blocking=True)
             out = self._out(len(rows), out)
@@ -504,10 +525,6 @@ class Y4mDecoder(_StagedFileDecoder):
                                 hdr.frame_stride, planes, self.W, self.H,
                                 crop=crop, dtype=self.dtype, out=out,
                                 filter=self.filter, sampling=hdr.sampling)
-        finally:
-            if cuda:     # also behind the uploads of a request that raised
-                entry.event.record(torch.cuda.current_stream(self.device))
-                entry.in_flight = True
         return out
 
 
@@ -599,28 +616,10 @@ class MjpegDecoder(_StagedFileDecoder):
         self._rounds = None        # ... and, with subseq_bytes, its rounds per frame
         self._max_len = {}         # video id -> longest frame in bytes
 
-    def probe(self, path):
-        vid = self._ids.get(path)
-        if vid is not None:
-            return vid, self._videos[vid][1].num_frames
-        if os.path.getsize(path) == 0:
-            raise ValueError("%s: empty file (field 'SOI')" % path)
-        vid = len(self._ids)
-        _, data = self._map(vid, path)
-        try:
-            idx = mjpeg.read_index(path, data=data)
-        except ValueError:
-            del self._maps[vid]
-            raise
-        try:
-            boxes = self._probe_boxes(path, idx)
-        except ValueError:
-            del self._maps[vid]
-            raise
-        self._ids[path] = vid
-        self._videos[vid] = (path, idx)
-        self._boxes[vid] = boxes
-        return vid, idx.num_frames
+    EMPTY_FIELD = "SOI"
+
+    def _parse(self, path, mm, data):
+        return mjpeg.read_index(path, data=data)
 
     def _planes(self, nframes: int, frame_bytes: int) -> torch.Tensor:
         # one surface, reused: its uses are ordered on the stream
@@ -650,15 +649,11 @@ class MjpegDecoder(_StagedFileDecoder):
         W, H = self.WARMUP_W, self.WARMUP_H
         mw, mh, rb = mjpeg.geometry(W, H)
         for i in range(n):
-            e = self._entry(15 * self.F * rb)
-            e.dev[:self.F * rb].zero_()
-            try:
-                self._to_clips(e.dev[:self.F * rb], 1, W, H, mw, mh,
+            with self._staged(15 * self.F * rb) as (_, _, buf):
+                buf[:self.F * rb].zero_()
+                self._to_clips(buf[:self.F * rb], 1, W, H, mw, mh,
                                lambda span: self._warm_crop(W, H),
                                self._out(max(1, self.views), None))
-            finally:
-                e.event.record(torch.cuda.current_stream(self.device))
-                e.in_flight = True
 
     def decode(self, vid, starts, out=None, views=None):
         if len(starts) == 0:
@@ -670,37 +665,23 @@ class MjpegDecoder(_StagedFileDecoder):
         n = len(starts)
         path, idx = got
         _, data = self._map(vid, path)
-        for s in starts:
-            if s < 0 or s + self.F > idx.num_frames:
-                raise ValueError("%s: clip at frame %d (+%d) is outside the %d frames"
-                                 % (path, s, self.F, idx.num_frames))
+        self._check_starts(path, starts, idx.num_frames)
         self.stats["requests"] += 1
         if self.entropy == "gpu":
             return self._decode_gpu_entropy(vid, path, idx, data, starts, out, rows)
         span = self.F * idx.record_bytes
         self.stats["uploaded_bytes"] += n * span
-        cuda = self.device.type == "cuda"
-        if cuda:
-            entry = self._entry(max(n, 15) * span)
-            host, buf = entry.host, entry.dev
-        else:
-            host = np.empty(n * span, dtype=np.uint8)
-            buf = torch.from_numpy(host)
-        try:
+        with self._staged(max(n, 15) * span, n * span) as (entry, host, buf):
             for i, s in enumerate(starts):
                 mjpeg.entropy_decode(data, idx.offsets[s:s + self.F], idx.lengths[s:s + self.F],
                                      host[i * span:(i + 1) * span], idx.record_bytes,
                                      self.threads, name=path, sampling=idx.sampling)
-                if cuda:     # this clip uploads while the next one decodes
+                if entry is not None:     # this clip uploads while the next one decodes
                     buf[i * span:(i + 1) * span].copy_(
                         entry.pinned[i * span:(i + 1) * span], non_blocking=True)
             out = self._out(len(rows), out)
             self._to_clips(buf[:n * span], n, idx.width, idx.height, idx.mw, idx.mh,
                            lambda sp: self._clip_args(vid, idx, rows, sp), out, idx.sampling)
-        finally:
-            if cuda:     # also behind the uploads of a request that raised
-                entry.event.record(torch.cuda.current_stream(self.device))
-                entry.in_flight = True
         return out
 
     # -- entropy="gpu" ----------------------------------------------------------
@@ -754,28 +735,21 @@ class MjpegDecoder(_StagedFileDecoder):
         head = (8 * (cap + 1) + 15) & ~15                     # the offset table, then the records
         stat_at = head + cap * per                            # then the status words come back
         frames = [s + f for s in starts for f in range(F)]
-        cuda = self.device.type == "cuda"
-        if cuda:
-            entry = self._entry(stat_at + 4 * cap)
-            host, buf = entry.host, entry.dev
-        else:
-            host = np.empty(stat_at, dtype=np.uint8)
-            buf = torch.from_numpy(host)
-        offs = host[:8 * (nfr + 1)].view(np.int64)
-        try:
+        with self._staged(stat_at + 4 * cap, stat_at) as (entry, host, buf):
+            offs = host[:8 * (nfr + 1)].view(np.int64)
             pos = head
             for i, s in enumerate(starts):
                 got, rel = mjpeg.pack_scans(data, idx.offsets[s:s + F], idx.lengths[s:s + F],
                                             host[pos:stat_at], idx.width, idx.height,
                                             name=path, frame0=s, sampling=idx.sampling)
                 offs[i * F:(i + 1) * F] = rel[:F] + pos
-                if cuda:     # this clip uploads while the next one packs
+                if entry is not None:     # this clip uploads while the next one packs
                     buf[pos:pos + got].copy_(entry.pinned[pos:pos + got], non_blocking=True)
                 pos += got
             offs[nfr] = pos
             self.stats["uploaded_bytes"] += pos - head + 8 * (nfr + 1)
             rb = idx.record_bytes
-            if cuda:
+            if entry is not None:
                 buf[:8 * (nfr + 1)].copy_(entry.pinned[:8 * (nfr + 1)], non_blocking=True)
                 records, status = vops.jpeg_huff(
                     buf[:pos], offs, nfr, idx.mw, idx.mh,
@@ -796,10 +770,6 @@ class MjpegDecoder(_StagedFileDecoder):
             out = self._out(len(rows), out)
             self._to_clips(records, n, idx.width, idx.height, idx.mw, idx.mh,
                            lambda sp: self._clip_args(vid, idx, rows, sp), out, idx.sampling)
-        finally:
-            if cuda:     # also behind the uploads of a request that raised
-                entry.event.record(torch.cuda.current_stream(self.device))
-                entry.in_flight = True
         return out
 
 

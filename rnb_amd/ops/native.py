@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import struct
 import threading
 from typing import Optional
 
@@ -206,28 +207,17 @@ class Kernels:
                                          ctypes.POINTER(ctypes.c_float),
                                          ctypes.POINTER(ctypes.c_float), ctypes.c_int,
                                          ctypes.c_void_p]
-        lib.rnb_yuv420_to_clip.argtypes = [ctypes.c_void_p, ctypes.c_longlong,
-                                           ctypes.POINTER(ctypes.c_longlong), ctypes.c_void_p,
-                                           ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_longlong,
-                                           ctypes.POINTER(ctypes.c_longlong),
-                                           ctypes.POINTER(ctypes.c_int), ctypes.c_int,
-                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                           ctypes.POINTER(ctypes.c_float),
-                                           ctypes.POINTER(ctypes.c_float),
-                                           ctypes.POINTER(ctypes.c_float), ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_void_p]
-        lib.rnb_yuv420_to_clip.restype = ctypes.c_int
-        lib.rnb_yuv420_to_clip_aa.argtypes = lib.rnb_yuv420_to_clip.argtypes
-        lib.rnb_yuv420_to_clip_aa.restype = ctypes.c_int
-        # the same with trailing (matrix, filter, sampling) for 4:2:2 / 4:4:4 frames
-        lib.rnb_yuv_to_clip.argtypes = (lib.rnb_yuv420_to_clip.argtypes[:-1]
-                                        + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p])
-        lib.rnb_yuv_to_clip.restype = ctypes.c_int
-        # rnb_yuv_to_clip with (boxes [n][4], boxes_dev) in place of crop
-        at = lib.rnb_yuv_to_clip.argtypes
-        lib.rnb_yuv_to_clip_boxes.argtypes = at[:15] + [ctypes.POINTER(ctypes.c_float),
-                                                        ctypes.c_void_p] + at[16:]
+        lib.rnb_yuv_to_clip_boxes.argtypes = [
+            ctypes.c_void_p, ctypes.c_longlong,                          # buf, buf_len
+            ctypes.POINTER(ctypes.c_longlong), ctypes.c_void_p,          # offs, offs_dev
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,      # nclips, F, src_w, src_h
+            ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong),        # frame_stride, plane_off
+            ctypes.POINTER(ctypes.c_int), ctypes.c_int,                  # plane_stride, c_step
+            ctypes.c_void_p, ctypes.c_int, ctypes.c_int,                 # out, out_w, out_h
+            ctypes.c_void_p, ctypes.c_void_p,            # boxes [n][4] fp32 (bytes / array), boxes_dev
+            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),      # mean, std
+            ctypes.c_int, ctypes.c_int,                                  # bf16, matrix
+            ctypes.c_int, ctypes.c_int, ctypes.c_void_p]                 # filter, sampling, stream
         lib.rnb_yuv_to_clip_boxes.restype = ctypes.c_int
         lib.rnb_jpeg_idct.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -828,56 +818,29 @@ class Kernels:
         _check(self.lib.rnb_nv12_to_clip(in_ptr, out_ptr, frames, src_w, src_h, out_w, out_h,
                                          c, m, s, 1 if bf16 else 0, stream), "nv12_to_clip")
 
-    def yuv420_to_clip(self, buf_ptr, buf_len, offsets, offsets_dev_ptr, F, src_w, src_h,
-                       frame_stride, plane_offsets, plane_strides, c_step, out_ptr, out_w,
-                       out_h, crop, mean, std, bf16, stream, matrix=0, antialias=False,
-                       sampling=0):
-        """``offsets``: the per-clip byte offsets on the host (checked against
-        ``buf_len`` by the launcher); ``offsets_dev_ptr``: the same table in
-        device memory, needed for more than 32 clips (else None). ``matrix``:
-        0 BT.601 video range, 1 full-range JFIF. ``antialias``: the
-        ``rnb_yuv420_to_clip_aa`` entry (triangle filter widened by the
-        downscale factor; the crop box must lie inside the frame).
-        ``sampling``: 0 4:2:0 (the two entry points above), 1 4:2:2, 2 4:4:4
-        (``rnb_yuv_to_clip``)."""
-        n = len(offsets)
-        offs = (ctypes.c_longlong * max(1, n))(*offsets)
-        po = (ctypes.c_longlong * 3)(*plane_offsets)
-        ps = (ctypes.c_int * 3)(*plane_strides)
-        c = (ctypes.c_float * 4)(*crop)
-        m = (ctypes.c_float * 3)(*mean)
-        s = (ctypes.c_float * 3)(*std)
-        if sampling:
-            _check(self.lib.rnb_yuv_to_clip(buf_ptr, buf_len, offs, offsets_dev_ptr, n, F, src_w,
-                                            src_h, frame_stride, po, ps, c_step, out_ptr, out_w,
-                                            out_h, c, m, s, 1 if bf16 else 0, int(matrix),
-                                            1 if antialias else 0, int(sampling), stream),
-                   "yuv_to_clip")
-            return
-        fn = self.lib.rnb_yuv420_to_clip_aa if antialias else self.lib.rnb_yuv420_to_clip
-        _check(fn(buf_ptr, buf_len, offs, offsets_dev_ptr, n, F, src_w, src_h, frame_stride,
-                  po, ps, c_step, out_ptr, out_w, out_h, c, m, s, 1 if bf16 else 0,
-                  int(matrix), stream),
-               "yuv420_to_clip_aa" if antialias else "yuv420_to_clip")
-
     def yuv_to_clip_boxes(self, buf_ptr, buf_len, offsets, offsets_dev_ptr, F, src_w, src_h,
                           frame_stride, plane_offsets, plane_strides, c_step, out_ptr, out_w,
                           out_h, boxes, boxes_dev_ptr, mean, std, bf16, stream, matrix=0,
                           antialias=False, sampling=0):
-        """``yuv420_to_clip`` with one crop box per row (``rnb_yuv_to_clip_boxes``):
-        ``boxes`` holds ``len(offsets)`` boxes (x, y, w, h); rows may repeat an
-        offset. Past 64 rows both tables must also be in device memory
-        (``offsets_dev_ptr`` int64, ``boxes_dev_ptr`` fp32 ``[n][4]``)."""
+        """The clip launch (``rnb_yuv_to_clip_boxes``). ``offsets``: the per-row
+        byte offsets on the host (checked against ``buf_len`` by the launcher);
+        rows may repeat an offset. ``boxes``: the rows' crop boxes (x, y, w, h
+        per row), either ``bytes`` of packed native fp32, 16 per row (the cheap
+        form: ``struct.pack("4f", *box) * n``), or one flat sequence of
+        ``4 * len(offsets)`` numbers. Past 64 rows both tables must also be in
+        device memory (``offsets_dev_ptr`` int64, ``boxes_dev_ptr`` fp32
+        ``[n][4]``; else None). ``matrix``: 0 BT.601 video range, 1 full-range
+        JFIF. ``antialias``: the triangle filter widened by the downscale
+        factor; every box must then lie inside the frame. ``sampling``: 0
+        4:2:0, 1 4:2:2, 2 4:4:4."""
         n = len(offsets)
+        b = boxes if isinstance(boxes, bytes) else struct.pack("%df" % len(boxes), *boxes)
+        if len(b) != 16 * n:
+            raise ValueError("yuv_to_clip_boxes: %d offsets need %d box numbers, got %d"
+                             % (n, 4 * n, len(b) // 4))
         offs = (ctypes.c_longlong * max(1, n))(*offsets)
         po = (ctypes.c_longlong * 3)(*plane_offsets)
         ps = (ctypes.c_int * 3)(*plane_strides)
-        import numpy as np
-        table = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1)     # alive to the call
-        if table.size != 4 * n:
-            raise ValueError("yuv_to_clip_boxes: %d offsets need %d box numbers, got %d"
-                             % (n, 4 * n, table.size))
-        b = table.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
         m = (ctypes.c_float * 3)(*mean)
         s = (ctypes.c_float * 3)(*std)
         _check(self.lib.rnb_yuv_to_clip_boxes(buf_ptr, buf_len, offs, offsets_dev_ptr, n, F,

@@ -5,8 +5,10 @@ mirror (the mirrors are what the numerics tests compare the kernels with).
 """
 from __future__ import annotations
 
+import itertools
 import math
 import numbers
+import struct
 from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -17,6 +19,11 @@ KINETICS_MEAN = (0.43216, 0.394666, 0.37645)
 KINETICS_STD = (0.22803, 0.22145, 0.216989)
 IN_CHANNELS_P = 8   # RGB padded to 8 channels (16-byte NDHWC bf16 pixels)
 IN_CHANNELS_P_F32 = 4   # RGB padded to 4 channels (16-byte NDHWC fp32 pixels)
+
+
+def clip_channels(dtype) -> int:
+    """Channels per pixel of a clip of ``dtype``: every pixel is 16 bytes."""
+    return IN_CHANNELS_P_F32 if dtype == torch.float32 else IN_CHANNELS_P
 
 _M32 = 0xFFFFFFFF
 
@@ -163,8 +170,7 @@ def nv12_to_clip(nv12: torch.Tensor, src_w: int, src_h: int, out_w: int = 112,
     NVVL does after NVDEC; reference model.py:123-125)."""
     frames = nv12.shape[0]
     crop = tuple(float(c) for c in (crop or (0, 0, src_w, src_h)))
-    C = IN_CHANNELS_P_F32 if dtype == torch.float32 else IN_CHANNELS_P
-    shape = (frames, out_h, out_w, C)
+    shape = (frames, out_h, out_w, clip_channels(dtype))
     if nv12.is_cuda:
         from .native import kernels
         if out is None:
@@ -359,9 +365,15 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
     ``crop``: ``None`` (the whole frame), one box ``(x, y, w, h)`` for every
     clip, or a sequence of ``n`` boxes, one per entry of ``clip_offsets``. With
     a sequence, entries may repeat an offset: several views of one clip read
-    one uploaded span, in one launch of the boxed form of the kernels
-    (``rnb_yuv_to_clip_boxes``; up to 64 rows travel in the kernel arguments,
-    more through device tables). ``filter="antialias"`` checks every box."""
+    one uploaded span, in one launch. ``filter="antialias"`` checks every box.
+
+    On the GPU every form is one ``rnb_yuv_to_clip_boxes`` launch with a box per
+    row; one box (or ``None``) is that box in every row. Up to
+    ``BOX_ROWS_IN_ARGS`` = 64 rows travel in the kernel arguments; more go
+    through two device tables, uploaded here (a ``clip_offsets`` that is a
+    tensor on ``buf``'s device is the offset table as it stands). One box used
+    to switch to a device table past 32 rows; it now does so past 64, like a
+    box per row."""
     hs, vs = sampling_factors(sampling, "yuv420_to_clip")
     if matrix not in MATRICES:
         raise ValueError("yuv420_to_clip: matrix must be one of %s, got %r" % (MATRICES, matrix))
@@ -375,8 +387,7 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
     boxes = _crop_boxes(crop, n)
     if boxes is None:
         crop = tuple(float(c) for c in (crop if crop is not None else (0, 0, src_w, src_h)))
-    C = IN_CHANNELS_P_F32 if dtype == torch.float32 else IN_CHANNELS_P
-    shape = (n, F, out_h, out_w, C)
+    shape = (n, F, out_h, out_w, clip_channels(dtype))
     if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
         raise ValueError("yuv420_to_clip: buf must be a flat contiguous uint8 tensor")
     if out is not None and (out.dtype != dtype or not out.is_contiguous()
@@ -388,41 +399,28 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
         if bad is not None:
             raise ValueError("yuv420_to_clip: filter='antialias' needs the crop box inside "
                              "the %d x %d frame, got %r" % (src_w, src_h, bad))
-    if buf.is_cuda and boxes is not None:
+    if buf.is_cuda:
         from .native import kernels
         if out is None:
             out = torch.empty(shape, dtype=dtype, device=buf.device)
+        # the rows' boxes as packed fp32: the cheapest table to build per call
+        flat = struct.pack("4f", *crop) * n if boxes is None else \
+            struct.pack("%df" % (4 * n), *itertools.chain.from_iterable(boxes))
         table = box_table = None
         if n > BOX_ROWS_IN_ARGS:       # past the kernel-argument tables: both in device memory
-            table = torch.tensor(offsets, dtype=torch.int64).to(buf.device)
-            box_table = torch.tensor(boxes, dtype=torch.float32).to(buf.device)
+            table = clip_offsets if isinstance(clip_offsets, torch.Tensor) else \
+                torch.tensor(offsets, dtype=torch.int64)
+            table = table.to(device=buf.device, dtype=torch.int64).contiguous()
+            box_table = torch.frombuffer(bytearray(flat), dtype=torch.float32).to(buf.device)
         kernels().yuv_to_clip_boxes(buf.data_ptr(), buf.numel(), offsets,
                                     None if table is None else table.data_ptr(), F, src_w,
                                     src_h, frame_stride, planes[:3], planes[3:6], planes.c_step,
-                                    out.data_ptr(), out_w, out_h, boxes,
+                                    out.data_ptr(), out_w, out_h, flat,
                                     None if box_table is None else box_table.data_ptr(), mean,
                                     std, dtype == torch.bfloat16,
                                     torch.cuda.current_stream(buf.device).cuda_stream,
                                     matrix=1 if jfif else 0, antialias=antialias,
                                     sampling=SAMPLINGS.index(sampling))
-        return out
-    if buf.is_cuda:
-        from .native import kernels
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=buf.device)
-        table = None
-        if n > 32:          # past the kernel-argument table: offsets in device memory
-            table = clip_offsets if isinstance(clip_offsets, torch.Tensor) else \
-                torch.tensor(offsets, dtype=torch.int64)
-            table = table.to(device=buf.device, dtype=torch.int64).contiguous()
-        kernels().yuv420_to_clip(buf.data_ptr(), buf.numel(), offsets,
-                                 None if table is None else table.data_ptr(), F, src_w,
-                                 src_h, frame_stride, planes[:3], planes[3:6], planes.c_step,
-                                 out.data_ptr(), out_w, out_h, crop, mean, std,
-                                 dtype == torch.bfloat16,
-                                 torch.cuda.current_stream(buf.device).cuda_stream,
-                                 matrix=1 if jfif else 0, antialias=antialias,
-                                 sampling=SAMPLINGS.index(sampling))
         return out
     if (not jfif and ((hs == 2 and src_w % 2) or (vs == 2 and src_h % 2))) \
             or planes.c_step not in (1, 2):

@@ -1,7 +1,8 @@
 """Time the mjpeg decode path per 15-clip request at 340x256 (GPU required).
 
   * kernels: ``jpeg_idct_kernel`` on the request's 120 frame records, a device
-    copy moving the same number of bytes as its ceiling, and the clip kernel on
+    copy moving the same number of bytes as its ceiling, and the clip kernel
+    (``yuv420_to_clip``: one ``rnb_yuv_to_clip_boxes`` launch, the only form) on
     the IDCT surface with the JFIF and with the BT.601 matrix; alternating,
     device events around ``--reps`` back-to-back launches per round;
   * host: ``MjpegDecoder.decode`` with 1, 4 and 16 entropy-decode threads on a

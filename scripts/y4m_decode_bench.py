@@ -18,10 +18,12 @@ and prints what it always did.
 
 ``--short-side S [--views V]`` times the short-side resize + window protocol
 instead (``crop={"short_side": S, "views": V}``), for both filters: the clip
-kernels through the one-box entry points at ``--clips`` rows next to the boxed
-entry point at the same rows with that box repeated and at ``clips * V`` rows
-with the views' boxes, then ``Y4mDecoder.decode`` (host call, call + sync,
-sustained requests/s, uploaded bytes per request) for 1 view and for ``V``.
+launch (``rnb_yuv_to_clip_boxes``, the only one) through ``yuv420_to_clip`` at
+``--clips`` rows with one crop box ("one box": the op repeats it per row), at
+the same rows with that box given as a per-row list ("boxed") and at
+``clips * V`` rows with the views' boxes, then ``Y4mDecoder.decode`` (host call,
+call + sync, sustained requests/s, uploaded bytes per request) for 1 view and
+for ``V``.
 """
 import argparse
 import os
@@ -175,9 +177,10 @@ def host_antialias(dev, dtype, reqs, lines, w, h, clips):
 
 
 def views_kernels(dev, dtype, reps, rounds, lines, w, h, clips, short_side, nviews):
-    """The one-box kernels at ``clips`` rows, the boxed kernels at ``clips`` rows
-    (the centre box repeated) and at ``clips * nviews`` rows (each clip through
-    every view's box, one uploaded span per clip), both filters, alternating."""
+    """The clip launch at ``clips`` rows with one box, at ``clips`` rows with a
+    per-row list of that box (the centre box repeated) and at ``clips * nviews``
+    rows (each clip through every view's box, one uploaded span per clip), both
+    filters, alternating."""
     from rnb_amd.models.r2p1d.decoder import view_boxes
     rng = np.random.default_rng(0)
     stride = 6 + y4m.payload_bytes(w, h, SAMPLING)

@@ -306,8 +306,8 @@ def case_seed(name):
 
 
 def table_case(matrix, n=33, w=8, h=6, slot=77, shift=5):
-    """33 one-frame clips of 8 x 6 at distinct, shuffled, non-monotonic byte
-    offsets (I420, 72 bytes each in slots of 77 behind 5 bytes):
+    """``n`` (33 unless given) one-frame clips of 8 x 6 at distinct, shuffled,
+    non-monotonic byte offsets (I420, 72 bytes each in slots of 77 behind 5 bytes):
     ``(y, u, v, buffer, offsets, frame stride, YuvPlanes)``; planes in clip
     order."""
     y, u, v = noise_planes(w, h, n, 4100 + (matrix == "jfif"), matrix)

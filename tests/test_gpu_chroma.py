@@ -2,8 +2,8 @@
 kernels against the fp64 oracle, jpeg_idct and jpeg_huff (interval and
 subsequence forms) on 4:2:2 / 4:4:4 records against the host decoders, the
 decoders end to end against PIL and the oracle, one loader call per container,
-and the 4:2:0 entry points against the generalised one. Inputs, damage tables and
-bounds are tests/test_chroma_cpu.py's."""
+and the op with one crop box against a raw launch with that box. Inputs, damage
+tables and bounds are tests/test_chroma_cpu.py's."""
 import ctypes
 import os
 
@@ -46,14 +46,17 @@ def test_clip_kernels_against_oracle(sampling, name):
 
 @pytest.mark.parametrize("name", ["bt601_bil_up", "jfif_bil_45x33", "bt601_aa_full", "jfif_aa_up"])
 @pytest.mark.parametrize("sampling", SAMPLINGS)
-def test_clip_kernels_33_clips_use_the_device_offset_table(sampling, name):
-    check_clip_case(sampling, name, DEV, clips=33)
+def test_clip_kernels_65_clips_use_the_device_tables(sampling, name):
+    """65 clips, one more than the 64 rows that fit the kernel arguments: offsets
+    and boxes come from the device tables."""
+    check_clip_case(sampling, name, DEV, clips=65)
 
 
 @pytest.mark.parametrize("filt", ["bilinear", "antialias"])
 @pytest.mark.parametrize("matrix", ["bt601", "jfif"])
 def test_420_entry_points_equal_the_generalised_one(matrix, filt):
-    """rnb_yuv420_to_clip / _aa and rnb_yuv_to_clip at sampling 0: bit-equal clips."""
+    """The op with one crop box and a raw rnb_yuv_to_clip_boxes call with that
+    box at sampling 0: bit-equal clips."""
     from rnb_amd.ops.native import kernels
     y, u, v = orc.noise_planes(46, 34, 2, 77, matrix)
     buf, stride, pl = orc.pack_i420(y, u, v, 7)
@@ -66,9 +69,9 @@ def test_420_entry_points_equal_the_generalised_one(matrix, filt):
         offs = (ctypes.c_longlong * 1)(0)
         po = (ctypes.c_longlong * 3)(*pl[:3])
         ps = (ctypes.c_int * 3)(*pl[3:6])
-        rc = kernels().lib.rnb_yuv_to_clip(
+        rc = kernels().lib.rnb_yuv_to_clip_boxes(
             t.data_ptr(), t.numel(), offs, None, 1, 2, 46, 34, stride, po, ps, pl.c_step,
-            new.data_ptr(), 16, 12, (ctypes.c_float * 4)(*crop),
+            new.data_ptr(), 16, 12, (ctypes.c_float * 4)(*crop), None,
             (ctypes.c_float * 3)(*vops.KINETICS_MEAN), (ctypes.c_float * 3)(*vops.KINETICS_STD),
             int(dtype == torch.bfloat16), int(matrix == "jfif"), int(filt == "antialias"), 0,
             torch.cuda.current_stream(DEV).cuda_stream)

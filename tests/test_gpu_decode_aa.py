@@ -28,7 +28,7 @@ CPU = torch.device("cpu")
 @pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
 @pytest.mark.parametrize("name", [c[0] for c in aa.AA_CASES])
 def test_aa_kernel_against_oracle(name, bf16):
-    """<= 32 clips: the kernel-argument instances (bt601 and jfif); bf16 is the
+    """<= 64 clips: the kernel-argument instances (bt601 and jfif); bf16 is the
     fp32 result rounded to nearest even, bit for bit."""
     check_case(name, DEV, bf16)
 
@@ -39,8 +39,9 @@ def test_aa_kernel_two_clips_at_non_monotonic_offsets():
 
 @pytest.mark.parametrize("matrix", ["bt601", "jfif"])
 def test_aa_kernel_device_offset_table(matrix):
-    """33 clips: the FROM_ARRAY instances, ``offs[clip]`` from device memory."""
-    check_table(matrix, DEV)
+    """65 clips: the FROM_ARRAY instances, ``offs[clip]`` and ``boxes_dev[clip]``
+    from device memory."""
+    check_table(matrix, DEV, 65)
 
 
 def test_aa_kernel_ignores_the_padding_of_a_jpeg_surface():
@@ -70,10 +71,11 @@ def test_aa_launcher_refuses_what_the_bilinear_launcher_refuses():
         vops.yuv420_to_clip(d, [0], 3, 46, 34, stride - 1, pl, 16, 12, filter="antialias")
     out = torch.full((1, 3, 12, 16, 4), 7.0, device=DEV)
     with pytest.raises(RuntimeError, match="code -5"):
-        kernels().yuv420_to_clip(d.data_ptr(), d.numel(), [0], None, 3, 46, 34, stride, pl[:3],
-                                 pl[3:6], 1, out.data_ptr(), 16, 12, (-2.0, -1.0, 50.0, 37.0),
-                                 vops.KINETICS_MEAN, vops.KINETICS_STD, False,
-                                 torch.cuda.current_stream(DEV).cuda_stream, antialias=True)
+        kernels().yuv_to_clip_boxes(d.data_ptr(), d.numel(), [0], None, 3, 46, 34, stride,
+                                    pl[:3], pl[3:6], 1, out.data_ptr(), 16, 12,
+                                    (-2.0, -1.0, 50.0, 37.0), None, vops.KINETICS_MEAN,
+                                    vops.KINETICS_STD, False,
+                                    torch.cuda.current_stream(DEV).cuda_stream, antialias=True)
     torch.cuda.synchronize()
     assert torch.all(out == 7.0)
 

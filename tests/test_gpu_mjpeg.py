@@ -186,7 +186,7 @@ def test_mjpeg_decoder_slot_contract_and_ring_reuse(two_files):
 
 
 def test_mjpeg_decoder_device_offset_table_and_threads(two_files):
-    """33 clips in one request: past the 32 offsets that fit the clip kernel's
+    """65 clips in one request: past the 64 rows that fit the clip kernel's
     arguments; 1 and 4 entropy-decode threads give identical bytes."""
     from rnb_amd.models.r2p1d.decoder import MjpegDecoder
     kw = dict(clip_length=2, height=16, width=24, dtype=torch.float32)
@@ -195,13 +195,13 @@ def test_mjpeg_decoder_device_offset_table_and_threads(two_files):
     v1, n = d1.probe(two_files[0])
     v4, _ = d4.probe(two_files[0])
     vm, _ = mirror.probe(two_files[0])
-    starts = [(5 * k) % (n - 1) for k in range(33)]
+    starts = [(5 * k) % (n - 1) for k in range(65)]
     a, b = d1.decode(v1, starts), d4.decode(v4, starts)
     torch.cuda.synchronize()
-    assert a.shape == (33, 2, 16, 24, 4) and torch.equal(a, b)
-    assert torch.equal(d1._ring[0].pinned[:33 * 2 * 7296], d4._ring[0].pinned[:33 * 2 * 7296])
+    assert a.shape == (65, 2, 16, 24, 4) and torch.equal(a, b)
+    assert torch.equal(d1._ring[0].pinned[:65 * 2 * 7296], d4._ring[0].pinned[:65 * 2 * 7296])
     err = (a.cpu() - mirror.decode(vm, starts)).abs().max().item()
-    print("33 clips: max |decoder - mirror| =", err)
+    print("65 clips: max |decoder - mirror| =", err)
     assert err <= MIRROR_TOL, err
 
 

@@ -1,6 +1,6 @@
-"""Short-side resize and three-crop views on the GPU: the boxed form of the two
-clip kernels (``rnb_yuv_to_clip_boxes``) against one launch of the existing
-kernels per row, bit for bit, in the kernel arguments and through the device
+"""Short-side resize and three-crop views on the GPU: one launch of the two
+clip kernels (``rnb_yuv_to_clip_boxes``) with a box per row against one launch
+per row, bit for bit, in the kernel arguments and through the device
 tables; the launcher's refusals; the decoders with three views against the CPU
 device and the fp64 oracle; the shipped 3-crop config end to end. Inputs and
 bounds are tests/test_views_cpu.py's."""
@@ -36,7 +36,7 @@ def channels(dtype):
 
 
 def boxed(t, offsets, F, W, H, stride, pl, ow, oh, boxes, dtype, **kw):
-    """The new entry point into a buffer with one clip of sentinel behind the rows."""
+    """One launch for all rows into a buffer with one clip of sentinel behind them."""
     n = len(offsets)
     full = torch.full((n + 1, F, oh, ow, channels(dtype)), 3.0, dtype=dtype, device=DEV)
     got = vops.yuv420_to_clip(t, offsets, F, W, H, stride, pl, ow, oh, crop=boxes, dtype=dtype,
@@ -47,7 +47,7 @@ def boxed(t, offsets, F, W, H, stride, pl, ow, oh, boxes, dtype, **kw):
 
 
 def per_row(t, offsets, F, W, H, stride, pl, ow, oh, boxes, dtype, **kw):
-    """One launch of the existing kernels per row, each with its own box."""
+    """One launch per row, each with its own box."""
     return torch.cat([vops.yuv420_to_clip(t, [o], F, W, H, stride, pl, ow, oh, crop=b, dtype=dtype,
                                           **kw) for o, b in zip(offsets, boxes)])
 
@@ -67,7 +67,7 @@ def source(matrix, sampling, clips, F, header):
     return torch.from_numpy(buf).to(DEV), stride, pl, W, H
 
 
-# -- 1. the boxed kernels against the existing ones, bit for bit --------------------------------------
+# -- 1. one launch with a box per row against a launch per row, bit for bit ---------------------------
 @pytest.mark.parametrize("filt", vops.FILTERS)
 @pytest.mark.parametrize("sampling", vops.SAMPLINGS)
 @pytest.mark.parametrize("matrix", vops.MATRICES)
@@ -120,6 +120,13 @@ def test_66_rows_use_the_device_tables_and_64_the_arguments(filt):
         got = boxed(t, offsets[:n], F, W, H, stride, pl, 16, 12, boxes[:n], torch.float32,
                     filter=filt)
         assert torch.equal(got, want[:n]), (filt, n)
+    # one box at 65 rows: the same device tables as that box given per row
+    one = boxed(t, offsets[:65], F, W, H, stride, pl, 16, 12, INSIDE, torch.float32, filter=filt)
+    rows = boxed(t, offsets[:65], F, W, H, stride, pl, 16, 12, [INSIDE] * 65, torch.float32,
+                 filter=filt)
+    each = per_row(t, offsets[:65], F, W, H, stride, pl, 16, 12, [INSIDE] * 65, torch.float32,
+                   filter=filt)
+    assert torch.equal(one, rows) and torch.equal(one, each), filt
 
 
 # -- 3. launcher refusals ------------------------------------------------------------------------------------
@@ -163,12 +170,13 @@ def test_boxed_launcher_refusals():
     assert torch.all(out == 9.0)
 
 
-# -- 4. the old entry points against the new one ----------------------------------------------------------------
+# -- 4. one box for every row against that box per row -----------------------------------------------------------
 @pytest.mark.parametrize("filt", vops.FILTERS)
 @pytest.mark.parametrize("matrix", vops.MATRICES)
 def test_old_entry_points_equal_the_boxed_one_with_a_uniform_box(matrix, filt):
-    """rnb_yuv420_to_clip / _aa with one box and rnb_yuv_to_clip_boxes with that
-    box in every row: bit-equal clips."""
+    """One crop box for every clip and a per-row list of that box: bit-equal
+    clips. Both are one rnb_yuv_to_clip_boxes launch; the one-box entry points
+    this once compared it with are gone."""
     y, u, v = orc.noise_planes(46, 34, 6, 77, matrix)
     buf, stride, pl = orc.pack_i420(y, u, v, 7)
     t = torch.from_numpy(buf).to(DEV)

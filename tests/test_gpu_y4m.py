@@ -144,8 +144,8 @@ def test_y4m_decoder_slot_contract_and_ring_reuse(two_files):
 
 
 def test_y4m_decoder_device_offset_table(tmp_path):
-    """33 clips in one request: past the 32 offsets that fit the kernel
-    arguments, so the table is read from device memory."""
+    """65 clips in one request: past the 64 rows that fit the kernel
+    arguments, so the tables are read from device memory."""
     from rnb_amd.models.r2p1d.decoder import Y4mDecoder
     path = tmp_path / "long.y4m"
     path.write_bytes(raw_y4m(46, 34, planes(46, 34, 40, 13)))
@@ -153,13 +153,13 @@ def test_y4m_decoder_device_offset_table(tmp_path):
     dec, mirror = Y4mDecoder(DEV, **kw), Y4mDecoder(CPU, **kw)
     vid, n = dec.probe(str(path))
     mirror.probe(str(path))
-    starts = [(5 * k) % 39 for k in range(33)]
+    starts = [(5 * k) % 39 for k in range(65)]
     y = dec.decode(vid, starts)
     torch.cuda.synchronize()
     ref = mirror.decode(vid, starts)
-    assert y.shape == (33, 2, 16, 24, 4)
+    assert y.shape == (65, 2, 16, 24, 4)
     err = (y.cpu() - ref).abs().max().item()
-    print("33 clips: max |decoder - mirror| =", err)
+    print("65 clips: max |decoder - mirror| =", err)
     assert err <= 5e-4, err
 
 
