@@ -17,7 +17,9 @@ sampled frames' file spans and scales / colour-converts them on the GPU
 ``MjpegDecoder`` reads Motion-JPEG streams (``.mjpeg``), the one compressed
 format decoded here: Huffman decode on the host (``librnb_jpeg.so``), then
 dequantisation and inverse DCT (``jpeg_idct`` HIP kernel) and the same
-``yuv420_to_clip`` kernel with the full-range JFIF matrix on the GPU.
+``yuv420_to_clip`` kernel with the full-range JFIF matrix on the GPU;
+``reduce=2 | 4 | 8 | "auto"`` has the IDCT write the frame at 1/2, 1/4 or 1/8
+size (libjpeg's ``scale_denom``).
 
 Every decoder returns NDHWC clips normalised with the Kinetics mean/std:
 ``fp32 [n, 8, 112, 112, 4]`` (reference precision) or ``bf16 [n, 8, 112, 112, 8]``
@@ -583,6 +585,21 @@ class MjpegDecoder(_StagedFileDecoder):
     (``csrc/jpeg_huff.h``); records, status words and deferred errors are the
     same. 0: one lane per restart interval, i.e. per frame of such a stream.
 
+    ``reduce``: ``1`` (default), ``2``, ``4``, ``8`` or ``"auto"``: the
+    reduced-size decode of libjpeg's ``scale_denom`` / PIL's ``draft``, in every
+    entropy mode and on a CPU device. ``jpeg_idct(reduce=s)`` writes the frame
+    at ``ceil(W / s) x ceil(H / s)``, each sample the ``s x s`` box mean of the
+    unrounded full-size samples, into a surface ``s^2`` times smaller, and the
+    clip launch gets that frame size, the reduced planes and every crop box
+    divided by ``s`` (exact: a power of two), ``crop="full"`` as the explicit
+    box ``(0, 0, W / s, H / s)`` so that the MCU padding in the last reduced
+    column is not sampled. Records, Huffman decode and status handling are
+    untouched. ``"auto"`` is decided per file at ``probe`` by geometry alone
+    (``auto_reduce``): the largest ``s`` at which no crop box of the file,
+    divided by ``s``, is smaller than the output, so the reduced frame is never
+    upscaled (340x256 to 112x112: 2 in every crop mode; a 1280x720 centre
+    crop: 4). ``reduce_of(vid)`` is the value a probed file decodes with.
+
     ``stats``: ``requests`` served and ``uploaded_bytes`` staged for upload
     (records, or scan records and their offset table)."""
 
@@ -591,7 +608,7 @@ class MjpegDecoder(_StagedFileDecoder):
     def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
                  width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full",
                  threads: int = 4, entropy: str = "host", subseq_bytes: Optional[int] = None,
-                 filter: str = "bilinear"):
+                 filter: str = "bilinear", reduce=1):
         if isinstance(threads, bool) or not isinstance(threads, int) or not 1 <= threads <= 16:
             raise ValueError("MjpegDecoder: threads must be an integer in 1..16, got %r"
                              % (threads,))
@@ -605,10 +622,15 @@ class MjpegDecoder(_StagedFileDecoder):
         if subseq_bytes is None:
             subseq_bytes = self.SUBSEQ_BYTES if entropy == "gpu" else 0
         subseq_bytes = mjpeg.check_subseq_bytes(subseq_bytes, "MjpegDecoder")
+        if reduce != "auto":
+            vops.jpeg_reduce_points(reduce, "MjpegDecoder")
+            reduce = int(reduce)
         super().__init__(device, clip_length, height, width, dtype, depth, crop, filter)
         self.threads = threads
         self.entropy = entropy
         self.subseq_bytes = subseq_bytes
+        self.reduce = reduce
+        self._reduce = {}          # video id -> the reduce its frames decode with
         self.stats = {"requests": 0, "uploaded_bytes": 0}
         self._surface = None       # device I420 planes of the request being decoded
         self._records = None       # entropy="gpu": device frame records of that request
@@ -628,32 +650,78 @@ class MjpegDecoder(_StagedFileDecoder):
             self._surface = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._surface
 
-    def _to_clips(self, records, n, W, H, mw, mh, clip_args, out, sampling="420"):
+    def auto_reduce(self, W: int, H: int, boxes=None) -> int:
+        """The ``reduce`` of ``"auto"`` for ``W`` x ``H`` frames: the largest s in
+        8, 4, 2, 1 with ``box_w / s >= out_w`` and ``box_h / s >= out_h`` for
+        every crop box of such a file (``boxes``: its view boxes; without them
+        the whole frame for ``crop="full"``, the square of the short side for
+        ``"center"``, the windows of ``view_boxes`` for a short side)."""
+        if boxes is None and self.short_side is not None:
+            boxes = view_boxes(W, H, self.W, self.H, self.short_side, self.views)
+        if boxes is None:
+            side = min(W, H)
+            boxes = [(0.0, 0.0, float(W), float(H)) if self.crop == "full"
+                     else (0.0, 0.0, float(side), float(side))]
+        for s in (8, 4, 2):
+            if all(b[2] / s >= self.W and b[3] / s >= self.H for b in boxes):
+                return s
+        return 1
+
+    def reduce_of(self, vid: int) -> int:
+        """The reduce the frames of a probed file decode with."""
+        return self._reduce[vid]
+
+    def probe(self, path):
+        vid, num_frames = super().probe(path)
+        if vid not in self._reduce:
+            hdr = self._videos[vid][1]
+            self._reduce[vid] = self.reduce if self.reduce != "auto" else \
+                self.auto_reduce(hdr.width, hdr.height, self._boxes[vid])
+        return vid, num_frames
+
+    def _clip_args(self, vid, hdr, rows, span: int, reduce: int = 1):
+        """As ``_StagedFileDecoder._clip_args``, for frames decoded at 1 /
+        ``reduce``: every box divided by it, the whole frame as the explicit
+        box (0, 0, W / reduce, H / reduce)."""
+        offsets, crop = super()._clip_args(vid, hdr, rows, span)
+        if reduce == 1:
+            return offsets, crop
+        if crop is None:
+            return offsets, (0.0, 0.0, hdr.width / reduce, hdr.height / reduce)
+        if isinstance(crop, tuple):
+            return offsets, tuple(c / reduce for c in crop)
+        return offsets, [tuple(c / reduce for c in box) for box in crop]
+
+    def _to_clips(self, records, n, W, H, mw, mh, clip_args, out, sampling="420", reduce=1):
         """``n`` clips of frame records -> one IDCT over all of them, then one clip
         launch over the output rows; ``clip_args(span)``: (offsets, crop) of the
-        rows for clips ``span`` surface bytes apart."""
-        fbytes = vops.jpeg_frame_bytes(mw, mh, sampling)[1]
+        rows for clips ``span`` surface bytes apart, in the coordinates of the
+        frame at 1 / ``reduce``."""
+        fbytes = vops.jpeg_frame_bytes(mw, mh, sampling, reduce)[1]
         surf = vops.jpeg_idct(records, n * self.F, mw, mh,
                               out=self._planes(max(n, 15) * self.F, fbytes)
-                              if self.device.type == "cuda" else None, sampling=sampling)
+                              if self.device.type == "cuda" else None, sampling=sampling,
+                              reduce=reduce)
         offsets, crop = clip_args(self.F * fbytes)
-        return vops.yuv420_to_clip(surf, offsets, self.F, W, H,
-                                   fbytes, vops.jpeg_surface_planes(mw, mh, sampling), self.W,
-                                   self.H, crop=crop, dtype=self.dtype, out=out, matrix="jfif",
-                                   filter=self.filter, sampling=sampling)
+        return vops.yuv420_to_clip(surf, offsets, self.F, -(-W // reduce), -(-H // reduce),
+                                   fbytes, vops.jpeg_surface_planes(mw, mh, sampling, reduce),
+                                   self.W, self.H, crop=crop, dtype=self.dtype, out=out,
+                                   matrix="jfif", filter=self.filter, sampling=sampling)
 
     def warmup(self, n: int) -> None:
-        """Run both kernels on a zeroed record buffer (no file needed)."""
+        """Run both kernels on a zeroed record buffer (no file needed), at the
+        reduce in use (``"auto"``: the one the warm-up frame size resolves to)."""
         if self.device.type != "cuda":
             return
         W, H = self.WARMUP_W, self.WARMUP_H
         mw, mh, rb = mjpeg.geometry(W, H)
+        s = self.reduce if self.reduce != "auto" else self.auto_reduce(W, H)
         for i in range(n):
             with self._staged(15 * self.F * rb) as (_, _, buf):
                 buf[:self.F * rb].zero_()
                 self._to_clips(buf[:self.F * rb], 1, W, H, mw, mh,
-                               lambda span: self._warm_crop(W, H),
-                               self._out(max(1, self.views), None))
+                               lambda span: self._warm_crop(W / s, H / s),
+                               self._out(max(1, self.views), None), reduce=s)
 
     def decode(self, vid, starts, out=None, views=None):
         if len(starts) == 0:
@@ -680,8 +748,10 @@ class MjpegDecoder(_StagedFileDecoder):
                     buf[i * span:(i + 1) * span].copy_(
                         entry.pinned[i * span:(i + 1) * span], non_blocking=True)
             out = self._out(len(rows), out)
+            red = self._reduce[vid]
             self._to_clips(buf[:n * span], n, idx.width, idx.height, idx.mw, idx.mh,
-                           lambda sp: self._clip_args(vid, idx, rows, sp), out, idx.sampling)
+                           lambda sp: self._clip_args(vid, idx, rows, sp, red), out,
+                           idx.sampling, red)
         return out
 
     # -- entropy="gpu" ----------------------------------------------------------
@@ -768,8 +838,10 @@ class MjpegDecoder(_StagedFileDecoder):
                                                  sampling=idx.sampling)
                 mjpeg.raise_for_status(status.numpy(), path, frames)
             out = self._out(len(rows), out)
+            red = self._reduce[vid]
             self._to_clips(records, n, idx.width, idx.height, idx.mw, idx.mh,
-                           lambda sp: self._clip_args(vid, idx, rows, sp), out, idx.sampling)
+                           lambda sp: self._clip_args(vid, idx, rows, sp, red), out,
+                           idx.sampling, red)
         return out
 
 
@@ -777,7 +849,8 @@ def make_decoder(backend: str, device: torch.device, clip_length=8, height=112, 
                  dtype=torch.bfloat16, decoder_args: Optional[dict] = None) -> Decoder:
     """``decoder_args``: backend-specific constructor arguments (``y4m``:
     ``depth``, ``crop``, ``filter``; ``mjpeg``: ``depth``, ``crop``, ``filter``,
-    ``threads``, ``entropy``, ``subseq_bytes``); the other
+    ``threads``, ``entropy``, ``subseq_bytes``, ``reduce``: 1, 2, 4, 8 or
+    ``"auto"``, the reduced-size IDCT); the other
     backends take none and ignore it. ``crop`` is ``"full"``, ``"center"`` or
     ``{"short_side": S, "views": 1 or 3}``; with three views the decoder returns
     three rows per clip (``Decoder.views``; 1 for every other decoder)."""

@@ -239,6 +239,10 @@ class Kernels:
             fn = getattr(lib, base + "_s")
             fn.argtypes = getattr(lib, base).argtypes[:-1] + [ctypes.c_int, ctypes.c_void_p]
             fn.restype = ctypes.c_int
+        # reduced-size IDCT: sampling, then reduce (1, 2, 4, 8), in front of the stream
+        lib.rnb_jpeg_idct_r.argtypes = lib.rnb_jpeg_idct.argtypes[:-1] + \
+            [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        lib.rnb_jpeg_idct_r.restype = ctypes.c_int
         lib.rnb_preprocess.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
                                        ctypes.POINTER(ctypes.c_float),
                                        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
@@ -851,10 +855,17 @@ class Kernels:
                "yuv_to_clip_boxes")
 
     def jpeg_idct(self, rec_ptr, rec_len, record_bytes, nframes, mw, mh, surf_ptr, surf_len,
-                  stream, sampling=0):
+                  stream, sampling=0, reduce=1):
         """Frame records -> padded I420 surface; the launcher checks both
         lengths against (mw, mh, nframes) before it launches. ``sampling``: 0
-        4:2:0 (``rnb_jpeg_idct``), 1 4:2:2, 2 4:4:4 (``rnb_jpeg_idct_s``)."""
+        4:2:0 (``rnb_jpeg_idct``), 1 4:2:2, 2 4:4:4 (``rnb_jpeg_idct_s``).
+        ``reduce`` other than 1: the surface at 1 / reduce of the size
+        (``rnb_jpeg_idct_r``; the launcher refuses what is not 1, 2, 4 or 8)."""
+        if reduce != 1:
+            _check(self.lib.rnb_jpeg_idct_r(rec_ptr, rec_len, record_bytes, nframes, mw, mh,
+                                            surf_ptr, surf_len, int(sampling), int(reduce),
+                                            stream), "jpeg_idct")
+            return
         if sampling:
             _check(self.lib.rnb_jpeg_idct_s(rec_ptr, rec_len, record_bytes, nframes, mw, mh,
                                             surf_ptr, surf_len, int(sampling), stream),

@@ -455,25 +455,42 @@ def yuv420_to_clip(buf: torch.Tensor, clip_offsets, F: int, src_w: int, src_h: i
 # ---------------------------------------------------------------------------
 # MJPEG frame records (utils/mjpeg.py) -> padded I420 surfaces
 # ---------------------------------------------------------------------------
-def jpeg_surface_planes(mw: int, mh: int, sampling: str = "420") -> YuvPlanes:
+JPEG_REDUCES = (1, 2, 4, 8)
+
+
+def jpeg_reduce_points(reduce, who: str = "jpeg_reduce_points") -> int:
+    """N = 8 / ``reduce``, the samples a block keeps per axis at a reduced-size
+    decode; ``ValueError`` naming the argument for what is not 1, 2, 4 or 8."""
+    if isinstance(reduce, bool) or reduce not in JPEG_REDUCES:
+        raise ValueError("%s: reduce must be one of %s, got %r" % (who, JPEG_REDUCES, reduce))
+    return 8 // int(reduce)
+
+
+def jpeg_surface_planes(mw: int, mh: int, sampling: str = "420", reduce: int = 1) -> YuvPlanes:
     """Where ``jpeg_idct`` puts a frame's planes: Y [8 Vs mh, 8 Hs mw], then Cb
     and Cr [8 mh, 8 mw]; frame stride ``64 B mw mh``, B = Hs Vs + 2 (4:2:0:
-    ``384 mw mh``)."""
+    ``384 mw mh``). With ``reduce`` = s, N = 8 / s: Y [N Vs mh, N Hs mw], Cb and
+    Cr [N mh, N mw], frame stride ``N^2 B mw mh``."""
     hs, vs = sampling_factors(sampling, "jpeg_surface_planes")
+    N = jpeg_reduce_points(reduce, "jpeg_surface_planes")
     n, ny = mw * mh, hs * vs
-    return YuvPlanes(0, 64 * ny * n, 64 * (ny + 1) * n, 8 * hs * mw, 8 * mw, 8 * mw, 1)
+    return YuvPlanes(0, N * N * ny * n, N * N * (ny + 1) * n, N * hs * mw, N * mw, N * mw, 1)
 
 
-def jpeg_frame_bytes(mw: int, mh: int, sampling: str = "420") -> Tuple[int, int]:
-    """(frame record bytes, surface frame bytes) of an ``mw`` x ``mh`` MCU grid."""
+def jpeg_frame_bytes(mw: int, mh: int, sampling: str = "420", reduce: int = 1) -> Tuple[int, int]:
+    """(frame record bytes, surface frame bytes) of an ``mw`` x ``mh`` MCU grid;
+    the records do not depend on ``reduce``, the surface is ``(8 / reduce)^2 B
+    mw mh`` bytes."""
     hs, vs = sampling_factors(sampling, "jpeg_frame_bytes")
+    N = jpeg_reduce_points(reduce, "jpeg_frame_bytes")
     nb = hs * vs + 2
-    return 384 + 128 * nb * mw * mh, 64 * nb * mw * mh
+    return 384 + 128 * nb * mw * mh, N * N * nb * mw * mh
 
 
 def jpeg_idct(records: torch.Tensor, nframes: int, mw: int, mh: int,
               out: Optional[torch.Tensor] = None,
-              record_bytes: Optional[int] = None, sampling: str = "420") -> torch.Tensor:
+              record_bytes: Optional[int] = None, sampling: str = "420",
+              reduce: int = 1) -> torch.Tensor:
     """Dequantise + 8x8 inverse DCT of ``nframes`` frame records (flat uint8
     tensor, ``record_bytes`` apart, default ``384 + 768 mw mh``; layout in
     ``utils/mjpeg.py``) into 8-bit planar frames at the padded size: per frame
@@ -486,10 +503,22 @@ def jpeg_idct(records: torch.Tensor, nframes: int, mw: int, mh: int,
     ``sampling`` ``"422"`` / ``"444"``: records of ``384 + 128 B mw mh`` bytes
     (B = 4 / 3 blocks per MCU, the Y blocks over the ``Vs mh x Hs mw`` grid)
     into frames of Y [8 Vs mh, 8 Hs mw], Cb, Cr [8 mh, 8 mw], ``64 B mw mh``
-    bytes."""
+    bytes.
+
+    ``reduce`` = s in 1, 2, 4, 8 (``ValueError`` otherwise): the reduced-size
+    decode of libjpeg's ``scale_denom`` / PIL's ``draft``. With N = 8 / s a
+    block gives N x N samples, each the s x s box mean of the unrounded,
+    unclamped full-size samples (the same separable transform with the basis
+    averaged over s rows), then + 128, round, clamp: frames of Y
+    [N Vs mh, N Hs mw], Cb, Cr [N mh, N mw], ``N^2 B mw mh`` bytes; the frame's
+    ``ceil(W / s) x ceil(H / s)`` corner is the picture. The records are the
+    same. ``reduce=1`` is the code path and the bytes of the full-size decode;
+    the others run ``jpeg_idct_reduced_kernel`` (s = 2, 4) or
+    ``jpeg_idct_dc_kernel`` (s = 8: ``F[0][0] / 8 + 128``)."""
     hs, vs = sampling_factors(sampling, "jpeg_idct")
+    N = jpeg_reduce_points(reduce, "jpeg_idct")
     n, ny = mw * mh, hs * vs
-    rb_min, fbytes = jpeg_frame_bytes(mw, mh, sampling)
+    rb_min, fbytes = jpeg_frame_bytes(mw, mh, sampling, reduce)
     rb = rb_min if record_bytes is None else int(record_bytes)
     need = nframes * fbytes
     if records.dtype != torch.uint8 or records.dim() != 1 or not records.is_contiguous():
@@ -505,7 +534,7 @@ def jpeg_idct(records: torch.Tensor, nframes: int, mw: int, mh: int,
         kernels().jpeg_idct(records.data_ptr(), records.numel(), rb, nframes, mw, mh,
                             out.data_ptr(), out.numel(),
                             torch.cuda.current_stream(records.device).cuda_stream,
-                            sampling=SAMPLINGS.index(sampling))
+                            sampling=SAMPLINGS.index(sampling), reduce=int(reduce))
         return out[:need]
     if mw < 1 or mh < 1 or rb < rb_min or nframes * rb > records.numel() \
             or (out is not None and out.numel() < need):
@@ -516,6 +545,8 @@ def jpeg_idct(records: torch.Tensor, nframes: int, mw: int, mh: int,
     u = torch.arange(8, dtype=torch.float64)
     basis = 0.5 * torch.cos((2.0 * u.view(8, 1) + 1.0) * u.view(1, 8) * math.pi / 16.0)
     basis[:, 0] *= math.sqrt(0.5)
+    if N != 8:                                              # Bs[i][u]: the mean of 8 / N rows
+        basis = basis.view(N, 8 // N, 8).mean(dim=1)
     basis = basis.float()                                   # [x][u], as the kernel's table
     planes = []
     for c, (lo, hi, rows, cols) in enumerate(((0, ny * n, vs * mh, hs * mw),
@@ -524,7 +555,7 @@ def jpeg_idct(records: torch.Tensor, nframes: int, mw: int, mh: int,
         f = (co[:, lo:hi] * qt[:, c]).view(nframes, -1, 8, 8)           # [frame, block, u, v]
         s = torch.einsum("xu,fbuv,yv->fbxy", basis, f, basis) + 128.0
         s = s.round().clamp(0, 255).to(torch.uint8)
-        planes.append(s.view(nframes, rows, cols, 8, 8).permute(0, 1, 3, 2, 4)
+        planes.append(s.view(nframes, rows, cols, N, N).permute(0, 1, 3, 2, 4)
                       .reshape(nframes, -1))
     res = torch.cat(planes, dim=1).reshape(-1)
     if out is not None:

@@ -33,6 +33,13 @@
     ``entropy="gpu"``, both filters, for 1 view and for ``V``; the bytes
     uploaded per request do not depend on the views.
 
+    ``--reduce 1,2,4,auto [--size 1280x720]`` reports the reduced-size decode
+    instead (``MjpegDecoder(reduce=)``): per value the ``jpeg_idct`` launch, the
+    clip launch on its surface (both filters, one view and three of short side
+    128), the surface bytes, and the host and sustained rows of ``MjpegDecoder``
+    with ``threads=4`` and with ``entropy="gpu", subseq_bytes=48`` on three
+    antialiased views; the values alternate within every round.
+
     python scripts/mjpeg_decode_bench.py --out profiles/mjpeg_decode.txt
     python scripts/mjpeg_decode_bench.py --entropy gpu --restart-interval 22
     python scripts/mjpeg_decode_bench.py --entropy gpu --subseq-bytes 0,64,128,256,512
@@ -300,7 +307,78 @@ def views_host(dev, dtype, encoded, reqs, lines, sustained, short_side, nviews):
                                  "%s %s v=%d" % (label, filt[:4], v), filter=filt, crop=crop, **kw)
 
 
+def reduce_report(dev, encoded, reduces, reps, rounds, reqs, sustained, lines):
+    """``--reduce``: per value, the IDCT launch on the request's 120 records, the
+    clip launch on its surface (both filters, one view and three, the windows of
+    short side 128 divided by the reduce), the surface bytes, and
+    ``MjpegDecoder(crop={"short_side": 128, "views": 3}, filter="antialias")``
+    with ``threads=4`` and with ``entropy="gpu", subseq_bytes=48``. ``reduce=1``
+    passes no ``reduce`` argument anywhere: the calls of a tree without it."""
+    from rnb_amd.models.r2p1d.decoder import view_boxes
+    dtype = torch.float32
+    mw, mh, rb = mjpeg.geometry(W, H, SAMPLING)
+    n = CLIPS * F
+    qt = mjpeg.quality_tables(75)[[0, 1, 1]]
+    rec = torch.from_numpy(np.concatenate(
+        [mjpeg.pack_record(encoded[i % DISTINCT][1], qt) for i in range(n)])).to(dev)
+    probe = MjpegDecoder(torch.device("cpu"), crop={"short_side": 128, "views": 3},
+                         **({"reduce": "auto"} if "auto" in reduces else {}))
+    cases = []
+    for r in reduces:
+        s = probe.auto_reduce(W, H) if r == "auto" else int(r)
+        rk = {} if s == 1 else {"reduce": s}
+        fb = vops.jpeg_frame_bytes(mw, mh, SAMPLING, **rk)[1]
+        surf = torch.empty(n * fb, dtype=torch.uint8, device=dev)
+        planes = vops.jpeg_surface_planes(mw, mh, SAMPLING, **rk)
+        fns = [("jpeg_idct", lambda surf=surf, rk=rk: vops.jpeg_idct(
+            rec, n, mw, mh, out=surf, sampling=SAMPLING, **rk))]
+        for v in (1, 3):
+            boxes = [tuple(c / s for c in b) for b in view_boxes(W, H, 112, 112, 128, v)]
+            offs = [c * F * fb for c in range(CLIPS) for _ in range(v)]
+            out = torch.empty((CLIPS * v, F, 112, 112, 4), dtype=dtype, device=dev)
+            for filt in vops.FILTERS:
+                fns.append(("clip %s %dv" % (filt[:4], v),
+                            lambda surf=surf, offs=offs, fb=fb, planes=planes, out=out,
+                            boxes=boxes * CLIPS, filt=filt, s=s: vops.yuv420_to_clip(
+                                surf, offs, F, -(-W // s), -(-H // s), fb, planes, crop=boxes,
+                                dtype=dtype, out=out, matrix="jfif", filter=filt,
+                                sampling=SAMPLING)))
+        cases.append((r, s, fb, fns))
+    for _, _, _, fns in cases:
+        for _, fn in fns:
+            event_ms(fn, reps)                                # warm
+    times = {}
+    for _ in range(rounds):                                   # the reduces alternate per round
+        for r, _, _, fns in cases:
+            for name, fn in fns:
+                times.setdefault((r, name), []).append(event_ms(fn, reps))
+    for r, s, fb, fns in cases:
+        lines.append("reduce %s (s = %d): frame %dx%d, surface %d bytes per request (%d per frame)"
+                     % (r, s, -(-W // s), -(-H // s), n * fb, fb))
+        for name, _ in fns:
+            t = times[r, name]
+            lines.append("  %-14s median %.2f us/launch (min %.2f, max %.2f over %d rounds of %d)"
+                         % (name, statistics.median(t) * 1e3, min(t) * 1e3, max(t) * 1e3, rounds,
+                            reps))
+    frames = 300
+    starts = [20 * c for c in range(CLIPS)]
+    out = torch.empty((CLIPS * 3, F, 112, 112, 4), dtype=dtype, device=dev)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "v.mjpeg")
+        with open(path, "wb") as fp:
+            for i in range(frames):
+                fp.write(encoded[i % DISTINCT][0])
+        for label, kw in (("threads=4", dict(threads=4)),
+                          ("gpu S=48", dict(entropy="gpu", subseq_bytes=48))):
+            for r in reduces:
+                rk = {} if r == 1 else {"reduce": r}
+                decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines,
+                             "%s r=%s" % (label, r), filter="antialias",
+                             crop={"short_side": 128, "views": 3}, **dict(kw, **rk))
+
+
 def main():
+    global SAMPLING, W, H, DISTINCT
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
@@ -320,10 +398,18 @@ def main():
     ap.add_argument("--short-side", type=float, default=None,
                     help="report MjpegDecoder with crop={'short_side': S, 'views': V} instead")
     ap.add_argument("--views", type=int, choices=(1, 3), default=1, help="with --short-side")
+    ap.add_argument("--reduce", default="",
+                    help="comma-separated reduces (1, 2, 4, 8, auto): report the reduced-size "
+                         "decode instead (reduce_report)")
+    ap.add_argument("--size", default=None, help="WxH of the synthetic frames (default 340x256)")
+    ap.add_argument("--distinct", type=int, default=DISTINCT,
+                    help="frames encoded; the stream repeats them")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    global SAMPLING
     SAMPLING = args.sampling
+    DISTINCT = args.distinct
+    if args.size:
+        W, H = (int(x) for x in args.size.lower().split("x"))
     if not torch.cuda.is_available():
         raise SystemExit("mjpeg_decode_bench: needs a GPU")
     dev = torch.device("cuda:0")
@@ -334,6 +420,20 @@ def main():
     subseq = tuple(mjpeg.check_subseq_bytes(int(x), "--subseq-bytes")
                    for x in args.subseq_bytes.split(",") if x.strip())
     encoded = encode(75, args.restart_interval)
+    if args.reduce:
+        reduces = [r if r == "auto" else int(r) for r in
+                   (x.strip() for x in args.reduce.split(",")) if r]
+        lines[0] = ("mjpeg reduced-size decode, sampling %s, per 15-clip request at %dx%d -> "
+                    "112x112, short side 128 (%s)"
+                    % (":".join(SAMPLING), W, H, torch.cuda.get_device_name(0)))
+        reduce_report(dev, encoded, reduces, args.reps, args.rounds, args.requests,
+                      args.sustained, lines)
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        if args.out:
+            with open(args.out, "w") as fp:
+                fp.write(text)
+        return
     if args.short_side is not None:
         lines[0] = ("mjpeg decode path, sampling %s, short side %g, %d view(s), per 15-clip "
                     "request at %dx%d -> 112x112 (%s)"
