@@ -39,6 +39,7 @@
 // LDS-DMA'd into two 64-B-row planes with the x6 direct swizzle, the split
 // weights (128-B rows, x6_chunk order) linearly; 2 LDS stages, counted
 // vmcnt + raw barrier, gather-table entries through scalar loads.
+#include <type_traits>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -438,7 +439,116 @@ void conv_h3_kernel(const ConvF32Params p, const X6DStats st) {
 // with the weights streamed per tap group (LDS-DMA, double-buffered): the
 // gathered activation traffic of the direct kernel drops 9x and the split
 // runs once per input value instead of once per tap.
-template <int NW, int TP, int TC, int HALO_PX, int G, bool ST, bool AFF, int MINB = 1>
+//
+// STK ("stacked" bands): a band is R consecutive rows of the N * T * H rows of
+// the whole tensor and may cross frames, so only the tensor's last band is
+// partial (28 x 28 frames in 256-px bands: 9 + 9 + 9 + 1 rows per frame
+// become 9 everywhere). The patch is cut from a virtual tall image with a row
+// pitch of H + 1: frame f's row y is virtual row f * (H + 1) + y, and virtual
+// row H of every frame is a zero separator, the bottom pad of frame f and the
+// top pad of frame f + 1. Only the prologue tables differ; !STK (bands that
+// tile the frame) is the code without any of it.
+struct H3Band {
+  int f, r0;       // frame and row of the band's first output row
+  int rows;        // valid output rows
+  int prows;       // patch rows
+  int g0, u0;      // STK: first output row of N * T * H, and its virtual row
+  bool mixed;      // STK && AFF: the band's frames belong to several videos
+};
+// a staging table entry as read inside the chunk loop: ON = what derives from
+// it (LDS and scale / shift addresses) is computed per chunk; hoisted out of
+// the loop those cost more registers than the stacked AFF kernels have left
+template <bool ON>
+static __device__ __forceinline__ int h3_per_chunk(int v) {
+  if constexpr (ON) asm volatile("" : "+v"(v));
+  return v;
+}
+// Item `it` (= 4 * patch entry + channel quad qd) of the staging table of a
+// patch of npx entries in rows of W2: src = byte offset of the entry's quad in
+// x (X6D_INVALID: padding or separator, stays zero), dst = the entry's LDS
+// offset (-1: past the patch); STK && AFF: | (the entry's clip - n0) << 17
+template <bool STK, bool AFF>
+static __device__ __forceinline__ void h3_patch_entry(const ConvF32Params& p, const H3Band& bd,
+                                                      int it, int npx, int W2, int qd, int n0,
+                                                      uint32_t& src, int& dst) {
+  const int H = p.H, W = p.W;
+  const int q = it >> 2;
+  const int hy = q / W2, hx = q - hy * W2;
+  const int x = hx - 1;
+  int fy = bd.f, y = bd.r0 - 1 + hy;
+  bool ok = it < 4 * npx && x >= 0 && x < W;
+  if constexpr (STK) {
+    // virtual row u -> frame u / (H + 1), row u % (H + 1); row H is the separator
+    const int u = bd.u0 - 1 + hy;
+    fy = f32_fast_div(max(u, 0), p.mG, p.sG);
+    y = u - fy * (H + 1);
+    ok = ok && u >= 0 && y < H && fy < p.N * p.T;
+  } else {
+    ok = ok && y >= 0 && y < H;
+  }
+  src = ok ? (uint32_t)((((fy * H + y) * W + x) * p.Cin_p + qd * 4) * 4) : X6D_INVALID;
+  dst = it < 4 * npx ? q * 128 : -1;
+  if constexpr (STK && AFF) {
+    if (ok) dst |= (f32_fast_div(fy, p.mTo, p.sTo) - n0) << 17;
+  }
+}
+// patch entry at tap (0, 0) of output pixel pp of a band (0 past the band:
+// never stored); stacked: + one patch row per frame boundary above the row
+template <bool STK>
+static __device__ __forceinline__ int h3_patch_pixel(const ConvF32Params& p, const H3Band& bd,
+                                                     int pp, int R, int W2) {
+  const int W = p.W;
+  const int py = pp / W;
+  if constexpr (STK) {
+    const int hy = py + f32_fast_div(bd.g0 + py, p.mHo, p.sHo) - bd.f;
+    return pp < bd.rows * W ? hy * W2 + (pp - py * W) : 0;
+  } else {
+    return pp < R * W ? py * W2 + (pp - py * W) : 0;
+  }
+}
+// scale / shift of a staged entry of a band that spans several videos: the
+// rows of the video of clip n0 + (d >> 17) (d: the entry's dst)
+static __device__ __forceinline__ void h3_entry_ss(const ConvF32Params& p, const X6DStats& st,
+                                                   int n0, int d, int qd, int chunk,
+                                                   x6f32x4& sc0, x6f32x4& sc1, x6f32x4& sh0,
+                                                   x6f32x4& sh1) {
+  const float* ss = st.in_ss + qd * 4 + chunk * 32 +
+                    (size_t)st.in_seg[n0 + (d >> 17)] * 2 * p.Cin_p;
+  sc0 = *(const x6f32x4*)ss;
+  sc1 = *(const x6f32x4*)(ss + 16);
+  sh0 = *(const x6f32x4*)(ss + p.Cin_p);
+  sh1 = *(const x6f32x4*)(ss + p.Cin_p + 16);
+}
+template <bool STK, bool AFF>
+static __device__ __forceinline__ H3Band h3_band(const ConvF32Params& p, const X6DStats& st,
+                                                 int band, int R) {
+  H3Band b;
+  if constexpr (STK) {
+    b.g0 = band * R;
+    b.f = f32_fast_div(b.g0, p.mHo, p.sHo);
+    b.r0 = b.g0 - b.f * p.H;
+    b.rows = min(R, p.N * p.T * p.H - b.g0);
+    const int fl = f32_fast_div(b.g0 + b.rows - 1, p.mHo, p.sHo);
+    b.u0 = b.g0 + b.f;
+    b.prows = b.rows + 2 + (fl - b.f);           // + one separator per frame boundary
+    b.mixed = false;
+    if constexpr (AFF)
+      b.mixed = st.in_seg[f32_fast_div(b.f, p.mTo, p.sTo)] !=
+                st.in_seg[f32_fast_div(fl, p.mTo, p.sTo)];
+  } else {
+    const int bands = (p.H + R - 1) / R;
+    b.f = band / bands;
+    b.r0 = (band - b.f * bands) * R;
+    b.rows = min(R, p.H - b.r0);
+    b.prows = R + 2;
+    b.g0 = b.u0 = 0;
+    b.mixed = false;
+  }
+  return b;
+}
+
+template <int NW, int TP, int TC, int HALO_PX, int G, bool ST, bool AFF, int MINB = 1,
+          bool STK = false>
 __global__ __launch_bounds__(64 * NW, MINB)
 void conv_h3r_kernel(const ConvF32Params p, const X6DStats st) {
   constexpr int P_TILE = NW * TP * 16, C_TILE = TC * 16;
@@ -457,17 +567,17 @@ void conv_h3r_kernel(const ConvF32Params p, const X6DStats st) {
   const int frow = lane & 15, fq = lane >> 4;
   const int W = p.W, H = p.H, W2 = p.W + 2;
   const int R = p.ST;                        // rows per band (host: stride field reused)
-  const int bands = (H + R - 1) / R;
 
   const int nwg = gridDim.x, bid = blockIdx.x;
   const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
   const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   const int ctile = wgid % p.n_ctiles;
   const int band = wgid / p.n_ctiles;
-  const int f = band / bands, r0 = (band - f * bands) * R;
+  const H3Band bd = h3_band<STK, AFF>(p, st, band, R);
+  const int f = bd.f, r0 = bd.r0;
   const int c0 = ctile * C_TILE;
   const int p0 = (f * H + r0) * W;                       // first output row (NDHWC)
-  const int m_end = p0 + min(R, H - r0) * W;             // valid rows of this band
+  const int m_end = p0 + bd.rows * W;                    // valid rows of this band
   const int nck = p.Cin_p / 32;
 
   const x6d_u32x4 wr = x6d_rsrc(p.w, (uint32_t)(p.K_pad / 32) * (uint32_t)p.w_rows * 128u);
@@ -485,19 +595,17 @@ void conv_h3r_kernel(const ConvF32Params p, const X6DStats st) {
   // lane's quad is threadIdx.x & 3 for every item (NT % 4 == 0)
   const __amdgpu_buffer_rsrc_t xr =
       __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.x_bytes, 0x00020000);
-  const int npx = (R + 2) * W2;
+  const int npx = bd.prows * W2;
   const int qd = threadIdx.x & 3;
   uint32_t src[ITEMS];
   int dst[ITEMS];
+  static_assert(HALO_BYTES <= 1 << 17, "dst packs the entry's clip above bit 17");
+  // the band's first clip (stacked bands with the input BN: dst[i] >> 17 is
+  // the entry's clip - n0, read when the band's frames span several videos)
+  [[maybe_unused]] const int n0 = f32_fast_div(f, p.mTo, p.sTo);
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i) {
-    const int it = threadIdx.x + i * NT;
-    const int q = it >> 2;
-    const int hy = q / W2, hx = q - hy * W2;
-    const int y = r0 - 1 + hy, x = hx - 1;
-    const bool ok = it < 4 * npx && y >= 0 && y < H && x >= 0 && x < W;
-    src[i] = ok ? (uint32_t)((((f * H + y) * W + x) * p.Cin_p + qd * 4) * 4) : X6D_INVALID;
-    dst[i] = it < 4 * npx ? q * 128 : -1;
+    h3_patch_entry<STK, AFF>(p, bd, threadIdx.x + i * NT, npx, W2, qd, n0, src[i], dst[i]);
   }
   const float* ssv = nullptr;                // AFF: this frame's video's scale / shift
   if constexpr (AFF) ssv = st.in_ss + (size_t)st.in_seg[f / p.T] * 2 * p.Cin_p + qd * 4;
@@ -509,7 +617,9 @@ void conv_h3r_kernel(const ConvF32Params p, const X6DStats st) {
   // the largest batches that compile without scratch)
   // (four waves per SIMD, MINB 4: 128 registers a lane, one item at a time)
   constexpr int SB = MINB >= 4 ? 1 : AFF ? (NW > 8 ? 1 : (TP >= 4 ? 3 : ITEMS)) : ITEMS;
-  auto stage = [&](int chunk) {
+  // mix (STK && AFF only): the band's frames span several videos, scale / shift per entry
+  auto stage = [&](int chunk, auto mix) {
+    constexpr bool MIX = decltype(mix)::value;
     x6f32x4 sc0, sh0, sc1, sh1;
     if constexpr (AFF) {
       const float* ss = ssv + chunk * 32;
@@ -532,10 +642,13 @@ void conv_h3r_kernel(const ConvF32Params p, const X6DStats st) {
     for (int k = 0; k < SB; ++k) {
       const int i = i0 + k;
       if (i >= ITEMS || dst[i] < 0) continue;
-      const int q = dst[i] >> 7;
+      // (also in the one-video path: conv3 with BN on load at 128 clips ran 0.712 ms
+      // so and 0.726 ms with the addresses hoisted, the per-frame kernel's time)
+      const int d = h3_per_chunk<STK && AFF>(dst[i]), q = (d >> 7) & 1023;
       x6f32x4 a0 = v0[k], a1 = v1[k];
       if constexpr (AFF) {
         const float m = src[i] == X6D_INVALID ? 0.f : in_scale;      // padding stays zero
+        if constexpr (MIX) h3_entry_ss(p, st, n0, d, qd, chunk, sc0, sc1, sh0, sh1);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           a0[j] = fmaxf(fmaf(a0[j], sc0[j], sh0[j]), 0.f) * m;
@@ -548,7 +661,7 @@ void conv_h3r_kernel(const ConvF32Params p, const X6DStats st) {
       uint32_t h[4], l[4];
       h3_split4(a0, h, l);
       h3_split4(a1, h + 2, l + 2);
-      char* base = lds + dst[i];
+      char* base = lds + (d & 0x1FFFF);
       *(wu32x4*)(base + (x6r_swz(2 * qd, q) << 4)) = (wu32x4){h[0], h[1], h[2], h[3]};
       *(wu32x4*)(base + (x6r_swz(2 * qd + 1, q) << 4)) = (wu32x4){l[0], l[1], l[2], l[3]};
     }
@@ -560,8 +673,7 @@ void conv_h3r_kernel(const ConvF32Params p, const X6DStats st) {
 #pragma unroll
   for (int tp = 0; tp < TP; ++tp) {
     const int pp = (wave * TP + tp) * 16 + frow;
-    const int py = pp / W;
-    pq[tp] = pp < R * W ? py * W2 + (pp - py * W) : 0;     // past the band: never stored
+    pq[tp] = h3_patch_pixel<STK>(p, bd, pp, R, W2);
   }
 
   x6f32x4 acc[TP][TC];
@@ -586,7 +698,12 @@ void conv_h3r_kernel(const ConvF32Params p, const X6DStats st) {
   issue_group(0, 0, 0);
   int half = 0;
   for (int c = 0; c < nck; ++c) {
-    stage(c);
+    if constexpr (STK && AFF) {
+      if (bd.mixed) stage(c, std::true_type{});      // block-uniform
+      else stage(c, std::false_type{});
+    } else {
+      stage(c, std::false_type{});
+    }
     x6d_wait_vm<0>();
     x6d_barrier();
     H3_PHASE(1 + 2 * c);
@@ -625,8 +742,9 @@ void conv_h3r_kernel(const ConvF32Params p, const X6DStats st) {
     }
     H3_PHASE(2 + 2 * c);
   }
-  x6d_epilogue<TP, TC, NW, C_TILE, ST>(p, st, acc, p0, m_end, p0 + P_TILE, c0, wave, 0, lane,
-                                       lds, HALO_BYTES + 2 * G * W_BYTES, st.out_scale);
+  x6d_epilogue<TP, TC, NW, C_TILE, ST, STK>(p, st, acc, p0, m_end, p0 + P_TILE, c0, wave, 0,
+                                            lane, lds, HALO_BYTES + 2 * G * W_BYTES,
+                                            st.out_scale);
   H3_PHASE(15);
 }
 
@@ -641,7 +759,7 @@ void conv_h3r_kernel(const ConvF32Params p, const X6DStats st) {
 // fragment reads are software-pipelined: a channel tile's MFMAs run while
 // the next tile's weights and one of the next tap's activation fragments
 // are read (double-buffered registers, one scheduling region per tile).
-template <int NW, int TP, int HALO_PX, int G, int MINB, bool ST, bool AFF>
+template <int NW, int TP, int HALO_PX, int G, int MINB, bool ST, bool AFF, bool STK = false>
 __global__ __launch_bounds__(64 * NW, MINB)
 void conv_h3q_kernel(const ConvF32Params p, const X6DStats st) {
   constexpr int TC = 9;
@@ -663,17 +781,17 @@ void conv_h3q_kernel(const ConvF32Params p, const X6DStats st) {
   // a row and the left pad of the next (plus one zero entry at the end)
   const int W = p.W, H = p.H, W2 = p.W + 1;
   const int R = p.ST;                        // rows per band (host: stride field reused)
-  const int bands = (H + R - 1) / R;
 
   const int nwg = gridDim.x, bid = blockIdx.x;
   const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
   const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   const int ctile = wgid % p.n_ctiles;
   const int band = wgid / p.n_ctiles;
-  const int f = band / bands, r0 = (band - f * bands) * R;
+  const H3Band bd = h3_band<STK, AFF>(p, st, band, R);
+  const int f = bd.f, r0 = bd.r0;
   const int c0 = ctile * C_TILE;
   const int p0 = (f * H + r0) * W;
-  const int m_end = p0 + min(R, H - r0) * W;
+  const int m_end = p0 + bd.rows * W;
   const int nck = p.Cin_p / 32;
 
   const x6d_u32x4 wr = x6d_rsrc(p.w, (uint32_t)(p.K_pad / 32) * (uint32_t)p.w_rows * 128u);
@@ -690,25 +808,25 @@ void conv_h3q_kernel(const ConvF32Params p, const X6DStats st) {
   // patch staging as conv_h3r_kernel
   const __amdgpu_buffer_rsrc_t xr =
       __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.x_bytes, 0x00020000);
-  const int npx = (R + 2) * W2 + 1;
+  const int npx = bd.prows * W2 + 1;
   const int qd = threadIdx.x & 3;
   uint32_t src[ITEMS];
   int dst[ITEMS];
+  static_assert(HALO_BYTES <= 1 << 17, "dst packs the entry's clip above bit 17");
+  // the band's first clip (stacked bands with the input BN: dst[i] >> 17 is
+  // the entry's clip - n0, read when the band's frames span several videos)
+  [[maybe_unused]] const int n0 = f32_fast_div(f, p.mTo, p.sTo);
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i) {
-    const int it = threadIdx.x + i * NT;
-    const int q = it >> 2;
-    const int hy = q / W2, hx = q - hy * W2;
-    const int y = r0 - 1 + hy, x = hx - 1;
-    const bool ok = it < 4 * npx && y >= 0 && y < H && x >= 0 && x < W;
-    src[i] = ok ? (uint32_t)((((f * H + y) * W + x) * p.Cin_p + qd * 4) * 4) : X6D_INVALID;
-    dst[i] = it < 4 * npx ? q * 128 : -1;
+    h3_patch_entry<STK, AFF>(p, bd, threadIdx.x + i * NT, npx, W2, qd, n0, src[i], dst[i]);
   }
   const float* ssv = nullptr;
   if constexpr (AFF) ssv = st.in_ss + (size_t)st.in_seg[f / p.T] * 2 * p.Cin_p + qd * 4;
   const float in_scale = st.in_scale;
   constexpr int SB = AFF ? (NW == 4 && MINB == 1 ? 5 : 2) : 5;
-  auto stage = [&](int chunk) {
+  // mix (STK && AFF only): the band's frames span several videos, scale / shift per entry
+  auto stage = [&](int chunk, auto mix) {
+    constexpr bool MIX = decltype(mix)::value;
     x6f32x4 sc0, sh0, sc1, sh1;
     if constexpr (AFF) {
       const float* ss = ssv + chunk * 32;
@@ -731,10 +849,12 @@ void conv_h3q_kernel(const ConvF32Params p, const X6DStats st) {
       for (int k = 0; k < SB; ++k) {
         const int i = i0 + k;
         if (i >= ITEMS || dst[i] < 0) continue;
-        const int q = dst[i] >> 7;
+        // (also in the one-video path: the 256-px stacked kernels spill 16-20 B without)
+        const int d = h3_per_chunk<STK && AFF>(dst[i]), q = (d >> 7) & 1023;
         x6f32x4 a0 = v0[k], a1 = v1[k];
         if constexpr (AFF) {
           const float m = src[i] == X6D_INVALID ? 0.f : in_scale;
+          if constexpr (MIX) h3_entry_ss(p, st, n0, d, qd, chunk, sc0, sc1, sh0, sh1);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             a0[j] = fmaxf(fmaf(a0[j], sc0[j], sh0[j]), 0.f) * m;
@@ -747,7 +867,7 @@ void conv_h3q_kernel(const ConvF32Params p, const X6DStats st) {
         uint32_t h[4], l[4];
         h3_split4(a0, h, l);
         h3_split4(a1, h + 2, l + 2);
-        char* base = lds + dst[i];
+        char* base = lds + (d & 0x1FFFF);
         *(wu32x4*)(base + (x6r_swz(2 * qd, q) << 4)) = (wu32x4){h[0], h[1], h[2], h[3]};
         *(wu32x4*)(base + (x6r_swz(2 * qd + 1, q) << 4)) = (wu32x4){l[0], l[1], l[2], l[3]};
       }
@@ -758,8 +878,7 @@ void conv_h3q_kernel(const ConvF32Params p, const X6DStats st) {
 #pragma unroll
   for (int tp = 0; tp < TP; ++tp) {
     const int pp = (wave * TP + tp) * 16 + frow;
-    const int py = pp / W;
-    pq[tp] = pp < R * W ? py * W2 + (pp - py * W) : 0;
+    pq[tp] = h3_patch_pixel<STK>(p, bd, pp, R, W2);
   }
 
   x6f32x4 acc[TP][TC];
@@ -792,7 +911,12 @@ void conv_h3q_kernel(const ConvF32Params p, const X6DStats st) {
   issue_group(0, 0, 0);
   int half = 0;
   for (int c = 0; c < nck; ++c) {
-    stage(c);
+    if constexpr (STK && AFF) {
+      if (bd.mixed) stage(c, std::true_type{});      // block-uniform
+      else stage(c, std::false_type{});
+    } else {
+      stage(c, std::false_type{});
+    }
     x6d_wait_vm<0>();
     x6d_barrier();
     H3_PHASE(1 + 2 * c);
@@ -832,8 +956,9 @@ void conv_h3q_kernel(const ConvF32Params p, const X6DStats st) {
     }
     H3_PHASE(2 + 2 * c);
   }
-  x6d_epilogue<TP, TC, NW, C_TILE, ST>(p, st, acc, p0, m_end, p0 + P_TILE, c0, wave, 0, lane,
-                                       lds, HALO_BYTES + 2 * G * W_BYTES, st.out_scale);
+  x6d_epilogue<TP, TC, NW, C_TILE, ST, STK>(p, st, acc, p0, m_end, p0 + P_TILE, c0, wave, 0,
+                                            lane, lds, HALO_BYTES + 2 * G * W_BYTES,
+                                            st.out_scale);
   H3_PHASE(15);
 }
 
@@ -1293,36 +1418,70 @@ int rnb_conv_h3_launch(const ConvF32Params* pp, int config_id, hipStream_t strea
 // = 0 / 1 / 2 with 2 taps per barrier, 6 = conv_h3q_kernel (4 waves x 7
 // tiles, 448 px), 7 = conv_h3q_kernel (4 waves x 4 tiles, 256 px, two blocks
 // per CU); 144 channels per block.
+typedef void (*ConvH3RKernel)(const ConvF32Params, const X6DStats);
 struct ConvH3RConfig {
   int nw, tp, halo_px, q;        // q: conv_h3q_kernel patch layout
-  void (*kernel)(const ConvF32Params, const X6DStats);
-  void (*kernel_st)(const ConvF32Params, const X6DStats);
-  void (*kernel_aff)(const ConvF32Params, const X6DStats);
-  void (*kernel_aff_st)(const ConvF32Params, const X6DStats);
+  // [stats + 2 * affine]: bands per frame
+  ConvH3RKernel kernel[4];
+  // stacked bands (R rows of N * T * H, across frames) and their patch entries
+  int halo_stk;
+  ConvH3RKernel stacked[4];
 };
 #define H3RCFGM(NW, TP, HALO, G, MINB)                                             \
-  {NW, TP, HALO, 0, conv_h3r_kernel<NW, TP, 9, HALO, G, false, false, MINB>,       \
-   conv_h3r_kernel<NW, TP, 9, HALO, G, true, false, MINB>,                         \
-   conv_h3r_kernel<NW, TP, 9, HALO, G, false, true, MINB>,                         \
-   conv_h3r_kernel<NW, TP, 9, HALO, G, true, true, MINB>}
+  {NW, TP, HALO, 0,                                                                \
+   {conv_h3r_kernel<NW, TP, 9, HALO, G, false, false, MINB>,                       \
+    conv_h3r_kernel<NW, TP, 9, HALO, G, true, false, MINB>,                        \
+    conv_h3r_kernel<NW, TP, 9, HALO, G, false, true, MINB>,                        \
+    conv_h3r_kernel<NW, TP, 9, HALO, G, true, true, MINB>},                        \
+   HALO,                                                                           \
+   {conv_h3r_kernel<NW, TP, 9, HALO, G, false, false, MINB, true>,                 \
+    conv_h3r_kernel<NW, TP, 9, HALO, G, true, false, MINB, true>,                  \
+    conv_h3r_kernel<NW, TP, 9, HALO, G, false, true, MINB, true>,                  \
+    conv_h3r_kernel<NW, TP, 9, HALO, G, true, true, MINB, true>}}
 #define H3RCFG(NW, TP, HALO, G) H3RCFGM(NW, TP, HALO, G, 1)
-// one wave per SIMD (conv_h3q_kernel): 4 waves x TP tiles
-#define H3QCFG(NW, TP, HALO, G, MINB)                                             \
-  {NW, TP, HALO, 1, conv_h3q_kernel<NW, TP, HALO, G, MINB, false, false>,          \
-   conv_h3q_kernel<NW, TP, HALO, G, MINB, true, false>,                            \
-   conv_h3q_kernel<NW, TP, HALO, G, MINB, false, true>,                            \
-   conv_h3q_kernel<NW, TP, HALO, G, MINB, true, true>}
+// bands per frame only (14 waves x 2 tiles: the BN-on-load forms are out of
+// registers as they are)
+#define H3RCFG_PF(NW, TP, HALO, G)                                                 \
+  {NW, TP, HALO, 0,                                                                \
+   {conv_h3r_kernel<NW, TP, 9, HALO, G, false, false, 1>,                          \
+    conv_h3r_kernel<NW, TP, 9, HALO, G, true, false, 1>,                           \
+    conv_h3r_kernel<NW, TP, 9, HALO, G, false, true, 1>,                           \
+    conv_h3r_kernel<NW, TP, 9, HALO, G, true, true, 1>},                           \
+   0, {nullptr, nullptr, nullptr, nullptr}}
+// one wave per SIMD (conv_h3q_kernel): 4 waves x TP tiles; HSTK = the stacked
+// instantiations' patch entries
+#define H3QCFG(NW, TP, HALO, HSTK, G, MINB)                                        \
+  {NW, TP, HALO, 1,                                                                \
+   {conv_h3q_kernel<NW, TP, HALO, G, MINB, false, false>,                          \
+    conv_h3q_kernel<NW, TP, HALO, G, MINB, true, false>,                           \
+    conv_h3q_kernel<NW, TP, HALO, G, MINB, false, true>,                           \
+    conv_h3q_kernel<NW, TP, HALO, G, MINB, true, true>},                           \
+   HSTK,                                                                           \
+   {conv_h3q_kernel<NW, TP, HSTK, G, MINB, false, false, true>,                    \
+    conv_h3q_kernel<NW, TP, HSTK, G, MINB, true, false, true>,                     \
+    conv_h3q_kernel<NW, TP, HSTK, G, MINB, false, true, true>,                     \
+    conv_h3q_kernel<NW, TP, HSTK, G, MINB, true, true, true>}}
+#define H3QCFG_PF(NW, TP, HALO, G, MINB)                                           \
+  {NW, TP, HALO, 1,                                                                \
+   {conv_h3q_kernel<NW, TP, HALO, G, MINB, false, false>,                          \
+    conv_h3q_kernel<NW, TP, HALO, G, MINB, true, false>,                           \
+    conv_h3q_kernel<NW, TP, HALO, G, MINB, false, true>,                           \
+    conv_h3q_kernel<NW, TP, HALO, G, MINB, true, true>},                           \
+   0, {nullptr, nullptr, nullptr, nullptr}}
 static const ConvH3RConfig kH3RConfigs[] = {
-    H3RCFG(7, 4, 600, 1), H3RCFG(14, 2, 600, 1), H3RCFG(7, 3, 480, 1),
-    H3RCFG(7, 4, 600, 2), H3RCFG(14, 2, 600, 2), H3RCFG(7, 3, 480, 2),
-    H3QCFG(4, 7, 600, 2, 1),  // 6: 448 px, one block (one wave per SIMD) per CU
+    H3RCFG(7, 4, 600, 1), H3RCFG_PF(14, 2, 600, 1), H3RCFG(7, 3, 480, 1),
+    H3RCFG(7, 4, 600, 2), H3RCFG_PF(14, 2, 600, 2), H3RCFG(7, 3, 480, 2),
+    H3QCFG(4, 7, 600, 600, 2, 1),  // 6: 448 px, one block (one wave per SIMD) per CU
     // 7: 256 px, 1 tap per barrier, 79 KB of LDS: two blocks per CU, so one
     // block's patch staging and epilogue (HBM-bound phases) overlap the
     // other's MFMAs
-    H3QCFG(4, 4, 344, 1, 2),
+    // (stacked: 9 rows of a 28-px frame + 2 + a separator = 12 x 29 + 1 = 349
+    // entries; 352 entries make 80 KiB, still two blocks in a CU's 160 KiB)
+    H3QCFG(4, 4, 344, 352, 1, 2),
     // 8: 8 waves x 4 tiles = 512 px (two waves per SIMD: one wave issues an
     // MFMA every ~16.5 cycles, two together every ~8.5, profiles/r3_mfma_split.txt)
-    H3QCFG(8, 4, 640, 2, 1),
+    // (bands per frame only: out of registers, it spills as it is)
+    H3QCFG_PF(8, 4, 640, 2, 1),
     // (7 waves x 2 tiles = 224 px, one tap per barrier, 82 KB, four waves per
     // SIMD so two blocks share a CU: no faster on conv2 spatial, 1.62 vs 1.57
     // ms for variant 7, a tie on conv4 spatial;
@@ -1331,12 +1490,104 @@ static const ConvH3RConfig kH3RConfigs[] = {
 
 int rnb_conv_h3r_num_variants() { return (int)(sizeof(kH3RConfigs) / sizeof(kH3RConfigs[0])); }
 
-// band rows of a variant for frame width W (0: the variant cannot run it)
-static int h3r_rows(const ConvH3RConfig& cfg, int H, int W) {
-  const int R = cfg.nw * cfg.tp * 16 / W;
+// Blocks one round of the variant's per-frame kernel holds on the current
+// device (CUs x blocks per CU; 0: no device to ask)
+static long long h3r_round_blocks(int variant) {
+  static long long cache[16] = {};
+  if (variant < 0 || variant >= 16) return 0;
+  if (cache[variant] == 0) {
+    int dev = 0, cus = 0, nb = 0;
+    const ConvH3RConfig& cfg = kH3RConfigs[variant];
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)cfg.kernel[0],
+                                                     64 * cfg.nw, 0) == hipSuccess)
+      cache[variant] = (long long)cus * nb;
+    else
+      (void)hipGetLastError();
+    if (cache[variant] <= 0) cache[variant] = -1;
+  }
+  return cache[variant] > 0 ? cache[variant] : 0;
+}
+
+// 1: bands are stacked also where the per-frame grid fits one round of blocks
+static int g_h3r_stack_small = 0;
+void rnb_conv_h3r_stack_small(int on) { g_h3r_stack_small = on; }
+
+// The band rule. Band rows of a variant for H x W frames (0: the variant
+// cannot run them) and whether the bands are stacked. Stacked, R is the
+// largest row count within the pixel tile whose worst-case patch fits: R + 2
+// rows plus one separator row per frame boundary a band of R rows can hold,
+// floor((R + H - 2) / H). Bands of P_TILE / W rows per frame (the kernels
+// without the stacked prologue) stay where stacking cannot pay:
+// - they are no more blocks: always when they tile the frame (H % R == 0);
+// - a launch (frames = N * T > 0, n_ctiles) whose per-frame grid already fits
+//   one round of blocks: fewer, fuller blocks then only lengthen the round
+//   (conv4 at 16 clips 4 % slower stacked, conv3 with BN on load 4-8 % at 16
+//   and 1 clips; profiles/NOTES.md).
+static int h3r_rows(int variant, int H, int W, long long frames, int n_ctiles, bool* stacked) {
+  const ConvH3RConfig& cfg = kH3RConfigs[variant];
+  *stacked = false;
+  if (H < 1 || W < 1) return 0;
   // conv_h3r_kernel: rows of W + 2 entries; conv_h3q_kernel: W + 1 plus one
-  const int entries = cfg.q ? (R + 2) * (W + 1) + 1 : (R + 2) * (W + 2);
-  return (R >= 1 && entries <= cfg.halo_px) ? R : 0;
+  const int pitch = cfg.q ? W + 1 : W + 2, extra = cfg.q ? 1 : 0;
+  const int R0 = cfg.nw * cfg.tp * 16 / W;
+  const bool fits0 = R0 >= 1 && (R0 + 2) * pitch + extra <= cfg.halo_px;
+  int R = R0;
+  while (R >= 1 && (R + 2 + (R + H - 2) / H) * pitch + extra > cfg.halo_stk) --R;
+  // per frame: ceil(H / R0) bands a frame; stacked: H / R
+  if (fits0 && (R < 1 || (H + R0 - 1) / R0 * R <= H)) return R0;
+  if (fits0 && frames > 0 && !g_h3r_stack_small &&
+      frames * ((H + R0 - 1) / R0) * n_ctiles <= h3r_round_blocks(variant))
+    return R0;
+  *stacked = R >= 1;
+  return R >= 1 ? R : 0;
+}
+
+// band rows on H x W frames of a launch of more than one round of blocks
+// (per-frame bands: the rows a frame has)
+int rnb_conv_h3r_band_rows(int variant, int H, int W) {
+  if (variant < 0 || variant >= rnb_conv_h3r_num_variants()) return 0;
+  bool stacked;
+  const int R = h3r_rows(variant, H, W, 0, 1, &stacked);
+  return stacked ? R : (R < H ? R : H);
+}
+
+// 1: a launch of the shape runs stacked bands
+int rnb_conv_h3r_stacked(int variant, int N, int T, int H, int W, int Cout_p) {
+  if (variant < 0 || variant >= rnb_conv_h3r_num_variants()) return 0;
+  bool stacked;
+  h3r_rows(variant, H, W, (long long)N * T, (Cout_p + 143) / 144, &stacked);
+  return stacked ? 1 : 0;
+}
+
+// output pixels per block
+int rnb_conv_h3r_pixels(int variant) {
+  if (variant < 0 || variant >= rnb_conv_h3r_num_variants()) return 0;
+  return kH3RConfigs[variant].nw * kH3RConfigs[variant].tp * 16;
+}
+
+// blocks of a launch (0: the variant cannot run the shape)
+long long rnb_conv_h3r_blocks(int variant, int N, int T, int H, int W, int Cout_p) {
+  if (variant < 0 || variant >= rnb_conv_h3r_num_variants()) return 0;
+  bool stacked;
+  const long long frames = (long long)N * T;
+  const int n_ctiles = (Cout_p + 143) / 144;
+  const int R = h3r_rows(variant, H, W, frames, n_ctiles, &stacked);
+  if (R == 0) return 0;
+  const long long bands = stacked ? (frames * H + R - 1) / R : frames * ((H + R - 1) / R);
+  return bands * n_ctiles;
+}
+
+// blocks per CU of the variant's (stacked) plain kernel; < 0: a HIP error
+int rnb_conv_h3r_occupancy(int variant, int stacked) {
+  if (variant < 0 || variant >= rnb_conv_h3r_num_variants()) return -1;
+  const ConvH3RConfig& cfg = kH3RConfigs[variant];
+  int nb = 0;
+  if (stacked && !cfg.stacked[0]) return -1;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &nb, (const void*)(stacked ? cfg.stacked[0] : cfg.kernel[0]), 64 * cfg.nw, 0);
+  return e == hipSuccess ? nb : -(int)e;
 }
 
 int rnb_conv_h3r_launch(const ConvF32Params* pp, int variant, hipStream_t stream, double* sums,
@@ -1355,7 +1606,9 @@ int rnb_conv_h3r_launch(const ConvF32Params* pp, int variant, hipStream_t stream
   const long long xb = (long long)p.N * p.T * p.H * p.W * p.Cin_p * 4;
   if (xb > 0x7FFFFF00LL || (long long)p.M * p.y_stride * 4 > 0x7FFFFF00LL) return -5;
   if (p.res && (long long)p.M * p.res_stride * 4 > 0x7FFFFF00LL) return -6;
-  const int R = h3r_rows(cfg, p.H, p.W);
+  bool stacked;
+  const int R = h3r_rows(variant, p.H, p.W, (long long)p.N * p.T, (p.Cout_p + 143) / 144,
+                         &stacked);
   if (R == 0) return -13;
   if ((long long)(p.K_pad / 32) * p.w_rows * 128 > 0x7FFFFF00LL) return -11;
   if (!(in_scale > 0.f) || !(out_scale > 0.f)) return -15;
@@ -1364,11 +1617,11 @@ int rnb_conv_h3r_launch(const ConvF32Params* pp, int variant, hipStream_t stream
   f32_magic_div((uint32_t)p.Wo, &p.mWo, &p.sWo);
   f32_magic_div((uint32_t)p.Ho, &p.mHo, &p.sHo);
   f32_magic_div((uint32_t)p.To, &p.mTo, &p.sTo);
+  f32_magic_div((uint32_t)p.H + 1u, &p.mG, &p.sG);      // stacked bands' virtual rows
   p.ST = R;                                    // rows per band (read by the kernel)
-  const int bands = (p.H + R - 1) / R;
   p.n_ctiles = (p.Cout_p + 143) / 144;
   if (p.n_ctiles * 144 > p.w_rows) return -8;
-  const long long blocks = (long long)p.N * p.T * bands * p.n_ctiles;
+  const long long blocks = rnb_conv_h3r_blocks(variant, p.N, p.T, p.H, p.W, p.Cout_p);
   if (blocks > 0x7FFFFFFF) return -7;
   if (sums && (!clip_seg || stats_c < p.Cout_p)) return -12;
   X6DStats st;
@@ -1383,10 +1636,9 @@ int rnb_conv_h3r_launch(const ConvF32Params* pp, int variant, hipStream_t stream
   st.in_ss = in_ss;
   st.in_seg = in_seg;
   st.oflag = g_h3_range_flag;
-  const bool aff = in_ss != nullptr;
-  hipLaunchKernelGGL(aff ? (sums ? cfg.kernel_aff_st : cfg.kernel_aff)
-                         : (sums ? cfg.kernel_st : cfg.kernel),
-                     dim3((unsigned)blocks), dim3(64 * cfg.nw), 0, stream, p, st);
+  const int kid = (sums ? 1 : 0) + (in_ss ? 2 : 0);
+  hipLaunchKernelGGL(stacked ? cfg.stacked[kid] : cfg.kernel[kid], dim3((unsigned)blocks),
+                     dim3(64 * cfg.nw), 0, stream, p, st);
   return (int)hipGetLastError();
 }
 

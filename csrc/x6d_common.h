@@ -133,8 +133,12 @@ static __device__ __forceinline__ float x6d_row16_sum(float v) {
 // one 16-B store per tile, and (ST) the per-video BN sums. Rows m < m_end of
 // [p0, p_hi) are valid; `lds` (lds_bytes) is free scratch (no DMA in flight).
 // acc_mul scales the accumulators as they are read (h3: out_scale; one tile
-// at a time, so accumulators held in AGPRs move to VGPRs tile by tile)
-template <int TP, int TC, int NW, int CT_ALL, bool ST>
+// at a time, so accumulators held in AGPRs move to VGPRs tile by tile).
+// MSEG (the row-band kernels' stacked bands, where a band of small frames
+// routinely holds 2-3 videos): up to X6D_MSEG_MAX videos are summed from
+// registers, one masked pass of the one-video reduction per video.
+#define X6D_MSEG_MAX 8
+template <int TP, int TC, int NW, int CT_ALL, bool ST, bool MSEG = false>
 static __device__ __forceinline__ void x6d_epilogue(const ConvF32Params& p, const X6DStats& st,
                                                     x6f32x4 (&acc)[TP][TC], int p0, int m_end,
                                                     int p_hi, int c0, int wp, int wc, int lane,
@@ -194,8 +198,22 @@ static __device__ __forceinline__ void x6d_epilogue(const ConvF32Params& p, cons
     const int seg_lo = __builtin_amdgcn_readfirstlane(st.clip_seg[__builtin_amdgcn_readfirstlane(na)]);
     const int seg_hi = __builtin_amdgcn_readfirstlane(st.clip_seg[__builtin_amdgcn_readfirstlane(nz)]);
     const int nseg = seg_hi - seg_lo + 1;
-    const bool uni = nseg == 1;
     const bool in_lds = nseg * CT_ALL * 16 <= lds_bytes;
+    // uni: summed from registers (one video; MSEG: a few, videos without rows included)
+    const bool uni = MSEG ? nseg <= X6D_MSEG_MAX && in_lds : nseg == 1;
+    [[maybe_unused]] int sl[MSEG ? TP : 1];           // MSEG: the row's video - seg_lo, -1 = no row
+    if constexpr (MSEG) {
+#pragma unroll
+      for (int tp = 0; tp < TP; ++tp) {
+        const int m = p0 + (wp * TP + tp) * 16 + frow;
+        sl[tp] = m < m_end ? 0 : -1;
+        if (nseg > 1 && uni && m < m_end) {
+          int n;
+          f32_decode_row(p, m, n, t_, h_, w_);
+          sl[tp] = st.clip_seg[n] - seg_lo;
+        }
+      }
+    }
     double* red = (double*)lds;                       // [nseg][CT_ALL][2]
     if (in_lds)
       for (int i = threadIdx.x; i < nseg * CT_ALL * 2; i += NT) red[i] = 0.0;
@@ -228,6 +246,7 @@ static __device__ __forceinline__ void x6d_epilogue(const ConvF32Params& p, cons
         }
         __builtin_amdgcn_raw_buffer_store_b128(
             v, yr, ok ? (uint32_t)(m * p.y_stride + c) * 4u : X6D_INVALID, 0, 0);
+        if constexpr (MSEG) r[tp] = v;                // kept for the per-video passes
         if (!ok) continue;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -236,16 +255,47 @@ static __device__ __forceinline__ void x6d_epilogue(const ConvF32Params& p, cons
         }
       }
       if (uni) {
+        if constexpr (MSEG) {
+#pragma unroll 1
+          for (int s = 0; s < nseg; ++s) {
+            if (nseg > 1) {                           // video seg_lo + s's rows of this lane
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          s1[j] = x6d_row16_sum(s1[j]);
-          s2[j] = x6d_row16_sum(s2[j]);
-        }
-        if (frow == 0 && c < p.Cout_p) {
+              for (int j = 0; j < 4; ++j) s1[j] = s2[j] = 0.f;
+#pragma unroll
+              for (int tp = 0; tp < TP; ++tp) {
+                if (sl[tp] != s) continue;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                  s1[j] += r[tp][j];
+                  s2[j] = fmaf(r[tp][j], r[tp][j], s2[j]);
+                }
+              }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              s1[j] = x6d_row16_sum(s1[j]);
+              s2[j] = x6d_row16_sum(s2[j]);
+            }
+            if (frow == 0 && c < p.Cout_p) {
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                atomicAdd(red + (s * CT_ALL + cl + j) * 2, (double)s1[j]);
+                atomicAdd(red + (s * CT_ALL + cl + j) * 2 + 1, (double)s2[j]);
+              }
+            }
+          }
+        } else {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            atomicAdd(red + (cl + j) * 2, (double)s1[j]);
-            atomicAdd(red + (cl + j) * 2 + 1, (double)s2[j]);
+            s1[j] = x6d_row16_sum(s1[j]);
+            s2[j] = x6d_row16_sum(s2[j]);
+          }
+          if (frow == 0 && c < p.Cout_p) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              atomicAdd(red + (cl + j) * 2, (double)s1[j]);
+              atomicAdd(red + (cl + j) * 2 + 1, (double)s2[j]);
+            }
           }
         }
       }

@@ -991,23 +991,18 @@ class ConvLayerF32:
         return self.wino_ok and self.geom.cin_p % 32 == 0
 
     def h3r_fits(self, variant: int, x_shape, efficient: bool = True) -> bool:
-        """Whether variant ``variant``'s band (P pixels // W rows, halo of
-        (rows + 2) x (W + 2) pixels) fits frames of width W, and (when
-        ``efficient``) its band uses at least half of the block's pixels."""
+        """Whether variant ``variant`` has a band for frames of H x W (the
+        launch's rule, rnb_conv_h3r_band_rows: bands are rows of the stacked
+        N * T * H rows unless they tile the frame), and (when ``efficient``)
+        its band uses at least half of the block's pixels."""
         if x_shape is None:
             return True
+        from .native import kernels
         _, T, H, W, _ = x_shape
-        # csrc/conv_h3.hip kH3RConfigs: 0-5 conv_h3r_kernel (x 2 barrier
-        # groupings), 6 / 7 / 8 conv_h3q_kernel (4 waves x 7 / 4 tiles, 8 x 4)
-        nw, tp, halo = ((7, 4, 600), (14, 2, 600), (7, 3, 480))[variant % 3] if variant < 6 \
-            else ((4, 7, 600), (4, 4, 344), (8, 4, 640))[variant - 6]
-        rows = nw * tp * 16 // W
-        # conv_h3q_kernel rows hold W + 1 entries (one shared zero column) + 1
-        q = 6 <= variant <= 8
-        entries = (rows + 2) * (W + 1) + 1 if q else (rows + 2) * (W + 2)
-        if rows < 1 or entries > halo:
+        rows = kernels().conv_h3r_band_rows(variant, H, W)
+        if rows < 1:
             return False
-        return not efficient or 2 * min(rows, H) * W >= nw * tp * 16
+        return not efficient or 2 * rows * W >= kernels().conv_h3r_pixels(variant)
 
     def h3stem_ok(self, x_shape=None) -> bool:
         """The stem h3 kernel takes 1x7x7 stride-(1, 2, 2) pad-(0, 3, 3) convs of

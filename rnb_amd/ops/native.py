@@ -393,6 +393,18 @@ class Kernels:
                                             ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                             ctypes.c_void_p, ctypes.c_void_p]
         lib.rnb_conv_h3r_launch.restype = ctypes.c_int
+        lib.rnb_conv_h3r_band_rows.argtypes = [ctypes.c_int] * 3
+        lib.rnb_conv_h3r_band_rows.restype = ctypes.c_int
+        lib.rnb_conv_h3r_pixels.argtypes = [ctypes.c_int]
+        lib.rnb_conv_h3r_pixels.restype = ctypes.c_int
+        lib.rnb_conv_h3r_blocks.argtypes = [ctypes.c_int] * 6
+        lib.rnb_conv_h3r_blocks.restype = ctypes.c_longlong
+        lib.rnb_conv_h3r_stacked.argtypes = [ctypes.c_int] * 6
+        lib.rnb_conv_h3r_stacked.restype = ctypes.c_int
+        lib.rnb_conv_h3r_stack_small.argtypes = [ctypes.c_int]
+        lib.rnb_conv_h3r_stack_small.restype = None
+        lib.rnb_conv_h3r_occupancy.argtypes = [ctypes.c_int] * 2
+        lib.rnb_conv_h3r_occupancy.restype = ctypes.c_int
         lib.rnb_conv_h3t_launch.argtypes = lib.rnb_conv_h3r_launch.argtypes
         lib.rnb_conv_h3t_launch.restype = ctypes.c_int
         lib.rnb_conv_h3t_pixels.argtypes = [ctypes.c_int, ctypes.c_int]
@@ -558,6 +570,35 @@ class Kernels:
                                             sums or None, clip_seg or None, stats_c, in_scale,
                                             out_scale, in_ss or None, in_seg or None),
                "conv_h3r (variant %d)" % variant)
+
+    def conv_h3r_band_rows(self, variant: int, H: int, W: int) -> int:
+        """Rows per band of row-band variant ``variant`` on H x W frames (0:
+        the variant cannot run them): the launch's own rule."""
+        return self.lib.rnb_conv_h3r_band_rows(variant, H, W)
+
+    def conv_h3r_pixels(self, variant: int) -> int:
+        """Output pixels per block of row-band variant ``variant``."""
+        return self.lib.rnb_conv_h3r_pixels(variant)
+
+    def conv_h3r_blocks(self, variant: int, N: int, T: int, H: int, W: int, cout_p: int) -> int:
+        """Grid size of a row-band launch (0: the variant cannot run the shape)."""
+        return self.lib.rnb_conv_h3r_blocks(variant, N, T, H, W, cout_p)
+
+    def conv_h3r_stacked(self, variant: int, N: int, T: int, H: int, W: int,
+                         cout_p: int) -> bool:
+        """Whether a row-band launch of the shape runs stacked bands (rows of
+        the N * T * H rows, across frames) rather than bands per frame."""
+        return bool(self.lib.rnb_conv_h3r_stacked(variant, N, T, H, W, cout_p))
+
+    def conv_h3r_stack_small(self, on: bool) -> None:
+        """Stack the bands of launches whose per-frame grid fits one round of
+        blocks too (off by default: it only lengthens their round)."""
+        self.lib.rnb_conv_h3r_stack_small(1 if on else 0)
+
+    def conv_h3r_occupancy(self, variant: int, stacked: bool) -> int:
+        """Blocks per CU of the variant's kernel (``stacked``: the form whose
+        bands cross frames); needs a GPU."""
+        return self.lib.rnb_conv_h3r_occupancy(variant, 1 if stacked else 0)
 
     def conv_h3t(self, params: ConvParams, variant: int, stream: int, in_scale: float,
                  out_scale: float, sums: int = 0, clip_seg: int = 0, stats_c: int = 0,
