@@ -978,10 +978,26 @@ void conv_h3q_kernel(const ConvF32Params p, const X6DStats st) {
 // (the host pads each tap's weights to 32-channel chunks).
 // WB = weight buffers: 2 = the next chunk's weights DMA'd during this
 // chunk's MFMAs; 1 = after them (smaller LDS: two blocks per CU cover it).
-template <int NW, int TP, int TC, int HALO, int WB, int MINB, bool ST, bool AFF>
+//
+// STK = stacked pixel tiles and tap skipping (HALO = ROWS). Pixel tile j
+// covers [j P, j P + P) of the linear index g = clip * HW + pixel over the
+// whole launch, so only the launch's last tile has empty rows and a block
+// may hold several clips (and videos: scale / shift per staged entry and
+// per-video sums as the stacked row bands do, h3_entry_ss / x6d_epilogue's
+// MSEG). The patch holds the T real frames only, entry = frame * P + q, and a
+// tile of output frame fr issues tap k only when fr + k - 1 is a frame of the
+// clip. Which tap slots a tile issues is fixed at compile time per tp, the
+// same in every wave, so the schedule stays straight-line and the waves of a
+// block issue the same number of (tile, tap) pairs (STK = the form, by T):
+// 1, T = 2: a wave's tiles lie in one frame (2 of 3 taps, and of the weight
+// reads); 2, T = TP: a wave owns one 16-pixel tile in all frames (3 TP - 2
+// pairs of 3 TP); 3, T = 2 TP: in the clip's first or last TP frames (3 TP -
+// 1). Other T run per-clip tiles.
+template <int NW, int TP, int TC, int HALO, int WB, int MINB, bool ST, bool AFF, int STK = 0>
 __global__ __launch_bounds__(64 * NW, MINB)
 void conv_h3t_kernel(const ConvF32Params p, const X6DStats st) {
   constexpr int ROWS = NW * TP * 16, C_TILE = TC * 16;
+  static_assert(!STK || HALO == ROWS, "stacked: the patch is the block's T x P rows");
   constexpr int HALO_BYTES = HALO * 128;
   constexpr int TAP_BYTES = C_TILE * 128;            // one tap's weights of a chunk
   constexpr int W_BYTES = 3 * TAP_BYTES;
@@ -1029,6 +1045,29 @@ void conv_h3t_kernel(const ConvF32Params p, const X6DStats st) {
   const int qd = threadIdx.x & 3;
   uint32_t src[ITEMS];
   int dst[ITEMS];
+  // stacked: hw0 = the tile's first linear pixel g (n = 0), P a power of two;
+  // clips n0 .. n1 have rows here; mixed: they belong to several videos (AFF)
+  [[maybe_unused]] const int NG = p.N * HW, lgP = 31 - __clz(P);
+  [[maybe_unused]] int n0 = 0, n1 = 0;
+  [[maybe_unused]] bool mixed = false;
+  if constexpr (STK) {
+    n0 = __builtin_amdgcn_readfirstlane(f32_fast_div(hw0, p.mG, p.sG));
+    n1 = __builtin_amdgcn_readfirstlane(f32_fast_div(min(hw0 + P, NG) - 1, p.mG, p.sG));
+    if constexpr (AFF) mixed = st.in_seg[n0] != st.in_seg[n1];
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {                 // ITEMS NT = 4 ROWS: every item is an entry
+      const int e = (threadIdx.x + i * NT) >> 2;      // = frame * P + q
+      const int fr = e >> lgP, g = hw0 + (e & (P - 1));
+      const int nn = f32_fast_div(g, p.mG, p.sG);
+      const bool ok = g < NG;
+      src[i] = ok ? (uint32_t)((((nn * T + fr) * HW + (g - nn * HW)) * p.Cin_p + qd * 4) * 4)
+                  : X6D_INVALID;
+      dst[i] = e * 128;
+      if constexpr (AFF) {
+        if (ok) dst[i] |= (nn - n0) << 17;            // the entry's clip (mixed blocks)
+      }
+    }
+  } else {
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i) {
     const int it = threadIdx.x + i * NT;
@@ -1038,8 +1077,9 @@ void conv_h3t_kernel(const ConvF32Params p, const X6DStats st) {
     src[i] = ok ? (uint32_t)((((n * T + fr) * HW + hw0 + px) * p.Cin_p + qd * 4) * 4) : X6D_INVALID;
     dst[i] = it < 4 * nent ? e * 128 : -1;
   }
+  }
   const float* ssv = nullptr;
-  if constexpr (AFF) ssv = st.in_ss + (size_t)st.in_seg[n] * 2 * p.Cin_p + qd * 4;
+  if constexpr (AFF) ssv = st.in_ss + (size_t)st.in_seg[STK ? n0 : n] * 2 * p.Cin_p + qd * 4;
   const float in_scale = st.in_scale;
   x6f32x4 raw0[ITEMS], raw1[ITEMS];
   auto load_chunk = [&](int c) {
@@ -1065,8 +1105,19 @@ void conv_h3t_kernel(const ConvF32Params p, const X6DStats st) {
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
       if (dst[i] < 0) continue;
-      const int e = dst[i] >> 7;
+      const int e = (STK && AFF ? dst[i] & 0x1FFFF : dst[i]) >> 7;
       x6f32x4 a0 = raw0[i], a1 = raw1[i];
+      if constexpr (STK && AFF) {
+        if (mixed) {                                  // the rows of the entry's video
+          const bool hi_ok = c * 32 + 16 < p.Cin_p;
+          const float* ss = st.in_ss + qd * 4 + c * 32 +
+                            (size_t)st.in_seg[n0 + (dst[i] >> 17)] * 2 * p.Cin_p;
+          sc0 = *(const x6f32x4*)ss;
+          sh0 = *(const x6f32x4*)(ss + p.Cin_p);
+          sc1 = hi_ok ? *(const x6f32x4*)(ss + 16) : (x6f32x4){0.f, 0.f, 0.f, 0.f};
+          sh1 = hi_ok ? *(const x6f32x4*)(ss + p.Cin_p + 16) : (x6f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+      }
       if constexpr (AFF) {
         const float m = src[i] == X6D_INVALID ? 0.f : in_scale;      // padding stays zero
 #pragma unroll
@@ -1081,7 +1132,7 @@ void conv_h3t_kernel(const ConvF32Params p, const X6DStats st) {
       uint32_t h[4], l[4];
       h3_split4(a0, h, l);
       h3_split4(a1, h + 2, l + 2);
-      char* base = lds + dst[i];
+      char* base = lds + (STK && AFF ? dst[i] & 0x1FFFF : dst[i]);
       *(wu32x4*)(base + (x6r_swz(2 * qd, e) << 4)) = (wu32x4){h[0], h[1], h[2], h[3]};
       *(wu32x4*)(base + (x6r_swz(2 * qd + 1, e) << 4)) = (wu32x4){l[0], l[1], l[2], l[3]};
     }
@@ -1089,11 +1140,40 @@ void conv_h3t_kernel(const ConvF32Params p, const X6DStats st) {
 
   // the lane's rows: tile (wave, tp) = rows r0 .. r0 + 15 of one frame
   int pe[TP];                                        // patch entry at tap 0
+  // stacked: tile (wave, tp) = pixels tq .. tq + 15 of the block in output
+  // frame tf (wave-uniform). A wave's frames run from fb in direction sg and
+  // so do its taps: tap slot k reads weight tap 1 + sg (k - 1) at patch frame
+  // tf + sg (k - 1). A wave at the clip's end is then the mirror image of one
+  // at its start -- its slot 0 is the tap past the end -- and every wave of a
+  // launch leaves out the same slots (taps_skip): one straight-line schedule.
+  // STK 1 (T = 2): rows frame-major as per clip, a wave's tiles lie in frame
+  // 0 (sg = 1) or 1 (sg = -1), slot 0 left out everywhere. STK 2 (T = TP):
+  // tp = frame, slot 0 left out at frame 0 and slot 2 at frame T - 1. STK 3
+  // (T = 2 TP): wave & 1 = the clip's half, sg = 1 from frame 0 or -1 from
+  // frame T - 1, slot 0 left out in the first tile.
+  [[maybe_unused]] int tf[TP], tq[TP], sg = 1;
+  if constexpr (STK) {
+    int fb = 0;
+    if constexpr (STK == 1) {
+      fb = (wave * TP * 16) >> lgP;
+      sg = fb ? -1 : 1;
+    } else if constexpr (STK == 3) {
+      sg = (wave & 1) ? -1 : 1;
+      fb = (wave & 1) ? T - 1 : 0;
+    }
+#pragma unroll
+    for (int tp = 0; tp < TP; ++tp) {
+      tf[tp] = STK == 1 ? fb : fb + sg * tp;
+      tq[tp] = STK == 1 ? ((wave * TP + tp) * 16) & (P - 1) : (STK == 3 ? wave >> 1 : wave) * 16;
+      pe[tp] = (tf[tp] - sg) * P + tq[tp] + frow;    // slot k -> entry + k sg P
+    }
+  } else {
 #pragma unroll
   for (int tp = 0; tp < TP; ++tp) {
     const int r = (wave * TP + tp) * 16 + frow;
     const int fr = r / P;
     pe[tp] = fr * P + (r - fr * P);                  // frame fr + tap k - 1 -> entry + k P
+  }
   }
 
   x6f32x4 acc[TP][TC];
@@ -1107,13 +1187,14 @@ void conv_h3t_kernel(const ConvF32Params p, const X6DStats st) {
   }
   const int w_hh = x6_chunk(2 * fq, frow) << 4, w_ll = x6_chunk(2 * fq + 1, frow) << 4;
   auto rd_bf = [&](H3B& b, int k, int tp) {
-    const int e = pe[tp] + k * P;
+    const int e = pe[tp] + k * (STK ? sg * P : P);
     const char* base = lds + e * 128;
     b.h = *(const wu32x4*)(base + (x6r_swz(2 * fq, e) << 4));
     b.l = *(const wu32x4*)(base + (x6r_swz(2 * fq + 1, e) << 4));
   };
   auto rd_w = [&](wu32x4& ah, wu32x4& al, int buf, int k, int tc) {
-    const char* wrow = wbuf + buf * W_BYTES + k * TAP_BYTES + (tc * 16 + frow) * 128;
+    const char* wrow = wbuf + buf * W_BYTES + (STK ? 1 + sg * (k - 1) : k) * TAP_BYTES +
+                       (tc * 16 + frow) * 128;
     ah = *(const wu32x4*)(wrow + w_hh);
     al = *(const wu32x4*)(wrow + w_ll);
   };
@@ -1150,6 +1231,47 @@ void conv_h3t_kernel(const ConvF32Params p, const X6DStats st) {
       }
     }
   };
+  // stacked: the same with slot 0 left out for the tiles of mask M0 (bit tp)
+  // and slot 2 for those of M2; a slot no tile issues reads no weights
+  [[maybe_unused]] auto taps_skip = [&]() {
+    constexpr int ALL = (1 << TP) - 1;
+    constexpr int M0 = STK == 1 ? ALL : 1, M2 = STK == 2 ? 1 << (TP - 1) : 0;
+    constexpr int K0 = M0 == ALL ? 1 : 0, K1 = M2 == ALL ? 2 : 3;
+    auto on = [](int k, int tp) constexpr {
+      return !((k == 0 ? M0 : k == 2 ? M2 : 0) >> tp & 1);
+    };
+    H3B bf[2][TP];
+    wu32x4 wh[2], wl[2];
+#pragma unroll
+    for (int tp = 0; tp < TP; ++tp)
+      if (on(K0, tp)) rd_bf(bf[K0 & 1][tp], K0, tp);
+    rd_w(wh[0], wl[0], buf, K0, 0);
+#pragma unroll
+    for (int k = K0; k < K1; ++k) {
+#pragma unroll
+      for (int tc = 0; tc < TC; ++tc) {
+        const int cs = ((k - K0) * TC + tc) & 1;
+        if (tc + 1 < TC) rd_w(wh[cs ^ 1], wl[cs ^ 1], buf, k, tc + 1);
+        else if (k + 1 < K1) rd_w(wh[cs ^ 1], wl[cs ^ 1], buf, k + 1, 0);
+        if (k + 1 < K1) {
+#pragma unroll
+          for (int tp = 0; tp < TP; ++tp)
+            if (tp * TC / TP == tc && on(k + 1, tp)) rd_bf(bf[(k + 1) & 1][tp], k + 1, tp);
+        }
+        const H3B (&b)[TP] = bf[k & 1];
+#pragma unroll
+        for (int tp = 0; tp < TP; ++tp)
+          if (on(k, tp)) acc[tp][tc] = h3_mma(wl[cs], b[tp].h, acc[tp][tc]);
+#pragma unroll
+        for (int tp = 0; tp < TP; ++tp)
+          if (on(k, tp)) acc[tp][tc] = h3_mma(wh[cs], b[tp].l, acc[tp][tc]);
+#pragma unroll
+        for (int tp = 0; tp < TP; ++tp)
+          if (on(k, tp)) acc[tp][tc] = h3_mma(wh[cs], b[tp].h, acc[tp][tc]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  };
   issue_w(0, 0);
   load_chunk(0);
   for (int c = 0; c < nck; ++c) {
@@ -1163,7 +1285,8 @@ void conv_h3t_kernel(const ConvF32Params p, const X6DStats st) {
       load_chunk(c + 1);
     }
     buf = WB == 2 ? (c & 1) : 0;
-    taps();
+    if constexpr (STK) taps_skip();
+    else taps();
   }
 
   // ---- epilogue: rows (frame, pixel) of clip n, one video (ST) ----
@@ -1176,14 +1299,151 @@ void conv_h3t_kernel(const ConvF32Params p, const X6DStats st) {
       (void*)(has_res ? p.res : p.y), (short)0,
       has_res ? (uint32_t)p.M * (uint32_t)p.res_stride * 4u : 0u, 0x00020000);
   int mrow[TP];
+  double* red = (double*)lds;                        // [C_TILE][2] (patch no longer read)
+  bool bad = false;                                  // range guard (st.oflag)
+  if constexpr (STK) {
+    // rows of clips n0 .. n1; ST: the videos seg_lo .. seg_lo + nseg - 1 are
+    // summed from registers, one masked pass per video, as x6d_epilogue's MSEG
+    // path does (same cap; past it the block reads its rows back from L2)
+    constexpr int LDS_BYTES = HALO_BYTES + WB * W_BYTES, CQ = C_TILE / 4;
+    [[maybe_unused]] int sl[TP];                     // the row's video - seg_lo, -1 = no row
+    int seg_lo = 0, nseg = 1;
+    if constexpr (ST) {
+      seg_lo = __builtin_amdgcn_readfirstlane(st.clip_seg[n0]);
+      nseg = __builtin_amdgcn_readfirstlane(st.clip_seg[n1]) - seg_lo + 1;
+    }
+    const bool in_lds = nseg * C_TILE * 16 <= LDS_BYTES;
+    const bool uni = nseg <= X6D_MSEG_MAX && in_lds;
+#pragma unroll
+    for (int tp = 0; tp < TP; ++tp) {
+      const int g = hw0 + tq[tp] + frow;
+      const int nn = f32_fast_div(g, p.mG, p.sG);
+      mrow[tp] = g < NG ? (nn * T + tf[tp]) * HW + (g - nn * HW) : -1;
+      if constexpr (ST) {
+        sl[tp] = g < NG ? 0 : -1;
+        if (nseg > 1 && uni && g < NG) sl[tp] = st.clip_seg[nn] - seg_lo;
+      }
+    }
+    if constexpr (ST) {
+      x6d_barrier();                                 // every wave is done with the patch
+      if (in_lds)
+        for (int i = threadIdx.x; i < nseg * C_TILE * 2; i += NT) red[i] = 0.0;
+      __syncthreads();
+    }
+#pragma unroll
+    for (int tc = 0; tc < TC; ++tc) {
+      const int cl = tc * 16 + 4 * fq, c = c0 + cl;
+      x6f32x4 rv[TP];
+#pragma unroll
+      for (int tp = 0; tp < TP; ++tp) {
+        const bool ok = has_res && mrow[tp] >= 0 && c < p.Cout_p;
+        rv[tp] = has_res ? __builtin_amdgcn_raw_buffer_load_b128(
+                               rr, ok ? (uint32_t)(mrow[tp] * p.res_stride + c) * 4u : X6D_INVALID,
+                               0, 0)
+                         : (x6f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+      float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int tp = 0; tp < TP; ++tp) {
+        const bool ok = mrow[tp] >= 0 && c < p.Cout_p;
+        x6f32x4 v = acc[tp][tc] * out_scale + rv[tp];
+        if (st.oflag != nullptr && ok) bad |= x6d_nonfinite(v);
+        if (p.relu) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
+        }
+        __builtin_amdgcn_raw_buffer_store_b128(
+            v, yr, ok ? (uint32_t)(mrow[tp] * p.y_stride + c) * 4u : X6D_INVALID, 0, 0);
+        rv[tp] = v;                                  // kept for the per-video passes
+        if (ST && ok) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            s1[j] += v[j];
+            s2[j] = fmaf(v[j], v[j], s2[j]);
+          }
+        }
+      }
+      if constexpr (ST) {
+        if (uni) {
+#pragma unroll 1
+          for (int s = 0; s < nseg; ++s) {
+            if (nseg > 1) {                          // video seg_lo + s's rows of this lane
+#pragma unroll
+              for (int j = 0; j < 4; ++j) s1[j] = s2[j] = 0.f;
+#pragma unroll
+              for (int tp = 0; tp < TP; ++tp) {
+                if (sl[tp] != s) continue;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                  s1[j] += rv[tp][j];
+                  s2[j] = fmaf(rv[tp][j], rv[tp][j], s2[j]);
+                }
+              }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              s1[j] = x6d_row16_sum(s1[j]);
+              s2[j] = x6d_row16_sum(s2[j]);
+            }
+            if (frow == 0 && c < p.Cout_p) {
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                atomicAdd(red + (s * C_TILE + cl + j) * 2, (double)s1[j]);
+                atomicAdd(red + (s * C_TILE + cl + j) * 2 + 1, (double)s2[j]);
+              }
+            }
+          }
+        }
+      }
+    }
+    if constexpr (ST) {
+      if (!uni) {
+        // the block's stored rows, back from L2 (glc: not this CU's L1)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+#pragma unroll 1
+        for (int i = threadIdx.x; i < ROWS * CQ; i += NT) {
+          const int e = i / CQ, cl = (i % CQ) * 4, c = c0 + cl;
+          const int g = hw0 + (e & (P - 1));
+          if (g >= NG || c >= p.Cout_p) continue;
+          const int nn = f32_fast_div(g, p.mG, p.sG);
+          const int m = (nn * T + (e >> lgP)) * HW + (g - nn * HW);
+          const x6f32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
+              yr, (uint32_t)(m * p.y_stride + c) * 4u, 0, 1);
+          const int sg = st.clip_seg[nn];
+#pragma unroll 1
+          for (int j = 0; j < 4; ++j) {
+            const double a = (double)v[j], b = (double)v[j] * (double)v[j];
+            if (in_lds) {
+              atomicAdd(red + ((size_t)(sg - seg_lo) * C_TILE + cl + j) * 2, a);
+              atomicAdd(red + ((size_t)(sg - seg_lo) * C_TILE + cl + j) * 2 + 1, b);
+            } else {
+              atomicAdd(st.sums + ((size_t)sg * 2) * st.stats_c + c + j, a);
+              atomicAdd(st.sums + ((size_t)sg * 2 + 1) * st.stats_c + c + j, b);
+            }
+          }
+        }
+      }
+      __syncthreads();
+      if (in_lds) {
+        for (int i = threadIdx.x; i < nseg * C_TILE; i += NT) {
+          const int sg = seg_lo + i / C_TILE, c = c0 + i % C_TILE;
+          if (c < p.Cout_p) {
+            atomicAdd(st.sums + ((size_t)sg * 2) * st.stats_c + c, red[i * 2]);
+            atomicAdd(st.sums + ((size_t)sg * 2 + 1) * st.stats_c + c, red[i * 2 + 1]);
+          }
+        }
+      }
+    }
+    if (bad) *st.oflag = 1;
+    return;
+  }
 #pragma unroll
   for (int tp = 0; tp < TP; ++tp) {
     const int r = (wave * TP + tp) * 16 + frow;
     const int fr = r / P, px = r - fr * P;
     mrow[tp] = hw0 + px < HW ? (n * T + fr) * HW + hw0 + px : -1;
   }
-  double* red = (double*)lds;                        // [C_TILE][2] (patch no longer read)
-  bool bad = false;                                  // range guard (st.oflag)
   if constexpr (ST) {
     x6d_barrier();
     for (int i = threadIdx.x; i < C_TILE * 2; i += NT) red[i] = 0.0;
@@ -1648,35 +1908,120 @@ int rnb_conv_h3r_launch(const ConvF32Params* pp, int variant, hipStream_t stream
 // 64 channels, 2 = 8 waves x 2 tiles x 128 channels, 3 = 4 waves x 4 tiles
 // (256 rows) x 64 channels with one weight buffer (two blocks per CU). p.w = split weights with
 // every tap padded to whole 32-channel chunks: step s = tap * ceil(Cin_p / 32)
-// + chunk (p.K_pad = 3 * 32 * ceil(Cin_p / 32)).
+// + chunk (p.K_pad = 3 * 32 * ceil(Cin_p / 32)). Every variant also has the
+// stacked, tap-skipping forms of its tile (h3t_blocks decides per launch);
+// their T x P patch admits variants 0 and 3 at T = 2.
 struct ConvH3TConfig {
   int rows, c_tile, halo, nw;
   void (*kernel)(const ConvF32Params, const X6DStats);
   void (*kernel_st)(const ConvF32Params, const X6DStats);
   void (*kernel_aff)(const ConvF32Params, const X6DStats);
   void (*kernel_aff_st)(const ConvF32Params, const X6DStats);
+  int tp;
+  // stacked pixel tiles + tap skipping (patch = the block's rows):
+  // [STK - 1][st + 2 aff], STK 1: T = 2, 2: T = TP, 3: T = 2 TP (null: not built)
+  void (*stacked[3][4])(const ConvF32Params, const X6DStats);
 };
-#define H3TCFG(NW, TP, TC, HALO, WB, MINB)                                         \
-  {NW * TP * 16, TC * 16, HALO, NW,                                                  \
+#define H3TSTK(NW, TP, TC, WB, MINB, STK)                                           \
+  {conv_h3t_kernel<NW, TP, TC, NW * TP * 16, WB, MINB, false, false, STK>,          \
+   conv_h3t_kernel<NW, TP, TC, NW * TP * 16, WB, MINB, true, false, STK>,           \
+   conv_h3t_kernel<NW, TP, TC, NW * TP * 16, WB, MINB, false, true, STK>,           \
+   conv_h3t_kernel<NW, TP, TC, NW * TP * 16, WB, MINB, true, true, STK>}
+#define H3TPC(NW, TP, TC, HALO, WB, MINB)                                           \
+  NW * TP * 16, TC * 16, HALO, NW,                                                   \
    conv_h3t_kernel<NW, TP, TC, HALO, WB, MINB, false, false>,                       \
    conv_h3t_kernel<NW, TP, TC, HALO, WB, MINB, true, false>,                        \
    conv_h3t_kernel<NW, TP, TC, HALO, WB, MINB, false, true>,                        \
-   conv_h3t_kernel<NW, TP, TC, HALO, WB, MINB, true, true>}
+   conv_h3t_kernel<NW, TP, TC, HALO, WB, MINB, true, true>, TP
+#define H3TCFG(NW, TP, TC, HALO, WB, MINB)                                          \
+  {H3TPC(NW, TP, TC, HALO, WB, MINB),                                               \
+   {H3TSTK(NW, TP, TC, WB, MINB, 1), H3TSTK(NW, TP, TC, WB, MINB, 2),               \
+    H3TSTK(NW, TP, TC, WB, MINB, 3)}}
+// TP = 2: T = TP is T = 2 (STK 1)
+#define H3TCFG_TP2(NW, TC, HALO, WB, MINB)                                          \
+  {H3TPC(NW, 2, TC, HALO, WB, MINB),                                                \
+   {H3TSTK(NW, 2, TC, WB, MINB, 1), {nullptr, nullptr, nullptr, nullptr},           \
+    H3TSTK(NW, 2, TC, WB, MINB, 3)}}
 static const ConvH3TConfig kH3TConfigs[] = {
-    H3TCFG(8, 4, 4, 768, 2, 1), H3TCFG(8, 2, 4, 512, 2, 1), H3TCFG(8, 2, 8, 512, 2, 1),
+    H3TCFG(8, 4, 4, 768, 2, 1), H3TCFG_TP2(8, 4, 512, 2, 1), H3TCFG_TP2(8, 8, 512, 2, 1),
     // 3: 4 waves x 4 tiles x 64 channels, one weight buffer, 72 KB: two blocks per CU
     H3TCFG(4, 4, 4, 384, 1, 2),
 };
 
 int rnb_conv_h3t_num_variants() { return (int)(sizeof(kH3TConfigs) / sizeof(kH3TConfigs[0])); }
 
-// pixels per block of a variant for T frames (0: the variant cannot run it)
+// pixels per block of a variant's per-clip tiles for T frames (0: per-clip
+// tiles cannot run it)
 int rnb_conv_h3t_pixels(int variant, int T) {
   if (variant < 0 || variant >= rnb_conv_h3t_num_variants() || T < 2) return 0;
   const ConvH3TConfig& cfg = kH3TConfigs[variant];
   if (cfg.rows % T) return 0;
   const int P = cfg.rows / T;
   return (P % 16 == 0 && (T + 2) * P <= cfg.halo) ? P : 0;
+}
+
+// 0: the tile rule below; 1: stacked tiles wherever they can run; -1: per-clip
+// tiles wherever they can (measurements and tests of either form)
+static int g_h3t_form = 0;
+void rnb_conv_h3t_form(int mode) { g_h3t_form = mode; }
+
+// The tile rule. Blocks of a launch (0: the variant cannot run the shape) and
+// whether its pixel tiles are stacked over the clips (the STK kernels, which
+// also skip the taps that fall outside the clip; *stacked = STK). Stacked
+// tiles need T x P patch entries only (always there: HALO >= rows), a power
+// of two as P, and T = 2, TP or 2 TP: the frame counts at which every wave
+// leaves out the same tap slots. Per-clip tiles, (T + 2) x P entries, stay
+// where stacking removes no block (always when HW % P == 0, or with one
+// clip). Unlike the row bands (h3r_rows) a grid within one round of blocks is
+// stacked too: with the skipped taps the stacked form measured 7-14 % faster
+// there as well (conv3 at 16, conv4 at 16-64 clips; profiles/NOTES.md).
+static long long h3t_blocks(int variant, long long N, int T, int H, int W, int Cout_p,
+                            int* stacked) {
+  *stacked = 0;
+  if (variant < 0 || variant >= rnb_conv_h3t_num_variants()) return 0;
+  if (N < 1 || T < 2 || H < 1 || W < 1 || Cout_p < 1) return 0;
+  const ConvH3TConfig& cfg = kH3TConfigs[variant];
+  if (cfg.rows % T) return 0;
+  const int P = cfg.rows / T;
+  if (P % 16) return 0;
+  const long long HW = (long long)H * W;
+  const bool fits_pc = (T + 2) * P <= cfg.halo;
+  const int stk_form = T == 2 ? 1 : T == cfg.tp ? 2 : T == 2 * cfg.tp ? 3 : 0;
+  const bool fits_stk = stk_form && (P & (P - 1)) == 0 && N * HW + P <= 0x7FFFFFFFLL;
+  if (!fits_pc && !fits_stk) return 0;
+  const long long n_ctiles = (Cout_p + cfg.c_tile - 1) / cfg.c_tile;
+  const long long pc = N * ((HW + P - 1) / P) * n_ctiles;
+  const long long stk = (N * HW + P - 1) / P * n_ctiles;
+  bool on;
+  if (!fits_pc) on = true;
+  else if (!fits_stk) on = false;
+  else if (g_h3t_form != 0) on = g_h3t_form > 0;
+  else on = stk < pc;
+  *stacked = on ? stk_form : 0;
+  return on ? stk : pc;
+}
+
+// 1: a launch of the shape runs stacked pixel tiles
+int rnb_conv_h3t_stacked(int variant, int N, int T, int H, int W, int Cout_p) {
+  int stacked;
+  h3t_blocks(variant, N, T, H, W, Cout_p, &stacked);
+  return stacked ? 1 : 0;
+}
+
+// blocks of a launch (0: the variant cannot run the shape)
+long long rnb_conv_h3t_blocks(int variant, int N, int T, int H, int W, int Cout_p) {
+  int stacked;
+  return h3t_blocks(variant, N, T, H, W, Cout_p, &stacked);
+}
+
+// blocks per CU of the variant's (stacked) plain kernel; < 0: a HIP error
+int rnb_conv_h3t_occupancy(int variant, int stacked) {
+  if (variant < 0 || variant >= rnb_conv_h3t_num_variants()) return -1;
+  const ConvH3TConfig& cfg = kH3TConfigs[variant];
+  int nb = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &nb, (const void*)(stacked ? cfg.stacked[0][0] : cfg.kernel), 64 * cfg.nw, 0);
+  return e == hipSuccess ? nb : -(int)e;
 }
 
 int rnb_conv_h3t_launch(const ConvF32Params* pp, int variant, hipStream_t stream, double* sums,
@@ -1697,17 +2042,20 @@ int rnb_conv_h3t_launch(const ConvF32Params* pp, int variant, hipStream_t stream
   const long long xb = (long long)p.N * p.T * p.H * p.W * p.Cin_p * 4;
   if (xb > 0x7FFFFF00LL || (long long)p.M * p.y_stride * 4 > 0x7FFFFF00LL) return -5;
   if (p.res && (long long)p.M * p.res_stride * 4 > 0x7FFFFF00LL) return -6;
-  const int P = rnb_conv_h3t_pixels(variant, p.T);
-  if (P == 0) return -13;
+  int stacked;
+  const long long blocks = h3t_blocks(variant, p.N, p.T, p.H, p.W, p.Cout_p, &stacked);
+  if (blocks == 0) return -13;
+  const int P = cfg.rows / p.T;
   if ((long long)(p.K_pad / 32) * p.w_rows * 128 > 0x7FFFFF00LL) return -11;
   if (!(in_scale > 0.f) || !(out_scale > 0.f)) return -15;
   if (in_ss && !in_seg) return -16;
   p.x_bytes = (uint32_t)xb;
   p.ngroups = P;
-  p.n_ptiles = (p.H * p.W + P - 1) / P;
   p.n_ctiles = (p.Cout_p + cfg.c_tile - 1) / cfg.c_tile;
+  // stacked: one row of tiles over the launch's N * HW pixels (the kernel's n = 0)
+  p.n_ptiles = stacked ? (int)(blocks / p.n_ctiles) : (p.H * p.W + P - 1) / P;
+  f32_magic_div((uint32_t)(p.H * p.W), &p.mG, &p.sG);
   if (p.n_ctiles * cfg.c_tile > p.w_rows) return -8;
-  const long long blocks = (long long)p.N * p.n_ptiles * p.n_ctiles;
   if (blocks > 0x7FFFFFFF) return -7;
   if (sums && (!clip_seg || stats_c < p.Cout_p)) return -12;
   X6DStats st;
@@ -1723,8 +2071,9 @@ int rnb_conv_h3t_launch(const ConvF32Params* pp, int variant, hipStream_t stream
   st.in_seg = in_seg;
   st.oflag = g_h3_range_flag;
   const bool aff = in_ss != nullptr;
-  hipLaunchKernelGGL(aff ? (sums ? cfg.kernel_aff_st : cfg.kernel_aff)
-                         : (sums ? cfg.kernel_st : cfg.kernel),
+  hipLaunchKernelGGL(stacked ? cfg.stacked[stacked - 1][(sums ? 1 : 0) + (aff ? 2 : 0)]
+                     : aff   ? (sums ? cfg.kernel_aff_st : cfg.kernel_aff)
+                             : (sums ? cfg.kernel_st : cfg.kernel),
                      dim3((unsigned)blocks), dim3(64 * cfg.nw), 0, stream, p, st);
   return (int)hipGetLastError();
 }

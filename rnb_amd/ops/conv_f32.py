@@ -599,8 +599,13 @@ class ConvLayerF32:
                 and (x_shape is None or x_shape[1] >= 2))
 
     def h3t_fits(self, variant: int, x_shape) -> bool:
+        """Whether h3t variant ``variant`` runs the shape, with per-clip or
+        stacked pixel tiles (the launcher's rule, rnb_conv_h3t_blocks)."""
         from .native import kernels
-        return x_shape is None or kernels().conv_h3t_pixels(variant, x_shape[1]) > 0
+        if x_shape is None:
+            return True
+        N, T, H, W, _ = x_shape
+        return kernels().conv_h3t_blocks(variant, N, T, H, W, self.geom.cout_p) > 0
 
     def h3p_ok(self, x_shape=None) -> bool:
         """The pixel-major temporal h3 kernel: h3t's conditions with H * W %

@@ -408,6 +408,14 @@ class Kernels:
         lib.rnb_conv_h3t_launch.argtypes = lib.rnb_conv_h3r_launch.argtypes
         lib.rnb_conv_h3t_launch.restype = ctypes.c_int
         lib.rnb_conv_h3t_pixels.argtypes = [ctypes.c_int, ctypes.c_int]
+        lib.rnb_conv_h3t_blocks.argtypes = [ctypes.c_int] * 6
+        lib.rnb_conv_h3t_blocks.restype = ctypes.c_longlong
+        lib.rnb_conv_h3t_stacked.argtypes = [ctypes.c_int] * 6
+        lib.rnb_conv_h3t_stacked.restype = ctypes.c_int
+        lib.rnb_conv_h3t_form.argtypes = [ctypes.c_int]
+        lib.rnb_conv_h3t_form.restype = None
+        lib.rnb_conv_h3t_occupancy.argtypes = [ctypes.c_int] * 2
+        lib.rnb_conv_h3t_occupancy.restype = ctypes.c_int
         # experiment kernels (build.py --exp; absent from the product build):
         # conv_h3u / conv_h3s report 0 variants without their library
         self.exp = None
@@ -683,8 +691,28 @@ class Kernels:
         return int(self.exp.rnb_conv_h3u_pixels(variant, T)) if self.exp else 0
 
     def conv_h3t_pixels(self, variant: int, T: int) -> int:
-        """Pixels per block of h3t variant ``variant`` for T frames (0: cannot run)."""
+        """Pixels per block of h3t variant ``variant``'s per-clip tiles for T
+        frames (0: per-clip tiles cannot run it)."""
         return int(self.lib.rnb_conv_h3t_pixels(variant, T))
+
+    def conv_h3t_blocks(self, variant: int, N: int, T: int, H: int, W: int, cout_p: int) -> int:
+        """Grid size of an h3t launch (0: the variant cannot run the shape)."""
+        return int(self.lib.rnb_conv_h3t_blocks(variant, N, T, H, W, cout_p))
+
+    def conv_h3t_stacked(self, variant: int, N: int, T: int, H: int, W: int,
+                         cout_p: int) -> bool:
+        """Whether an h3t launch of the shape runs pixel tiles stacked over
+        the clips (and skips the taps outside the clip) rather than per clip."""
+        return bool(self.lib.rnb_conv_h3t_stacked(variant, N, T, H, W, cout_p))
+
+    def conv_h3t_form(self, mode: int) -> None:
+        """0: the launcher's tile rule; 1: stacked tiles wherever they can
+        run; -1: per-clip tiles wherever they can (measurements, tests)."""
+        self.lib.rnb_conv_h3t_form(mode)
+
+    def conv_h3t_occupancy(self, variant: int, stacked: bool) -> int:
+        """Blocks per CU of the variant's (stacked, T = 2) kernel; needs a GPU."""
+        return self.lib.rnb_conv_h3t_occupancy(variant, 1 if stacked else 0)
 
     def conv_h3_affine_ok(self, config_id: int, cin_p: int, rows_per_clip: int) -> bool:
         return bool(self.lib.rnb_conv_h3_affine_ok(config_id, cin_p, rows_per_clip))
