@@ -29,7 +29,8 @@ LIBRARIES = {
                            "video_ops.hip", "bn_ops.hip", "conv_halo_ws.hip", "conv21.hip",
                            "conv_f32.hip", "conv_wino_f32.hip", "conv_wino_x6.hip",
                            "conv_x6.hip", "conv_h3.hip", "conv_h3stem.hip", "conv_h3p.hip",
-                           "conv_h3w.hip", "jpeg_ops.hip", "jpeg_huff.hip"],
+                           "conv_h3w.hip", "jpeg_ops.hip", "jpeg_huff.hip",
+                           "score_ops.hip"],
                           [], []),
     "librnb_runtime.so": (["runtime.cpp"], [], []),
     # host-only C++ (no HIP headers): the MJPEG entropy decoder

@@ -35,15 +35,21 @@ DEFAULT_BUCKETS = (1, 2, 4, 8, 12, 16, 24, 32, 48, 64, 80, 96, 128, 160, 192, 25
 
 
 class _BucketGraph:
-    __slots__ = ("graph", "meta", "offsets", "frames", "logits", "sums", "argmax")
+    __slots__ = ("graph", "meta", "offsets", "frames", "logits", "sums", "argmax", "top_val")
 
 
 class Replica:
     """One stream + its own static buffers and graphs over a shared engine."""
 
     def __init__(self, engine: R2P1DEngine, max_clips: int, max_videos: int,
-                 buckets: Sequence[int], pinned_ring: int = 4):
+                 buckets: Sequence[int], pinned_ring: int = 4,
+                 scores: Optional[str] = None, top_k: int = 1):
         self.engine = engine
+        # scores set: the graph ends in video_scores (per-video class scores of
+        # that kind + top-k) instead of video_reduce (logit sums + argmax)
+        self.scores, self.top_k = scores, int(top_k)
+        if scores is not None:
+            vops.check_score_args(scores, self.top_k, engine.num_classes)
         self.device = engine.device
         self.max_videos = max_videos
         self.buckets = sorted({b for b in buckets if b < max_clips} | {max_clips})
@@ -60,6 +66,12 @@ class Replica:
                                    pin_memory=True),
                        torch.zeros(max_videos, dtype=torch.int32, pin_memory=True),
                        torch.cuda.Event()) for _ in range(pinned_ring)]
+        if scores is not None:     # [videos][k] class indices and, beside them, their scores
+            self._ring = [(h, torch.zeros((max_videos, self.top_k), dtype=torch.int32,
+                                          pin_memory=True), ev) for h, _, ev in self._ring]
+            self._ring_val = [torch.zeros((max_videos, self.top_k), dtype=torch.float32,
+                                          pin_memory=True) for _ in range(pinned_ring)]
+        self.last_top_val: Optional[torch.Tensor] = None
         self._ring_idx = 0
 
     def bucket_for(self, n: int) -> int:
@@ -86,7 +98,15 @@ class Replica:
         self._decode(bg)
         logits = self.engine.forward(bg.frames, packed=self.packed)
         bg.logits = logits
-        vops.video_reduce(logits, bg.offsets, sums=bg.sums)[1]
+        self._reduce(bg, logits)
+
+    def _reduce(self, bg: _BucketGraph, logits: torch.Tensor):
+        """Last node of the graph: per-video argmax, or scores + top-k."""
+        if self.scores is None:
+            _, bg.argmax = vops.video_reduce(logits, bg.offsets, sums=bg.sums)
+        else:
+            vops.video_scores(logits, bg.offsets, scores=self.scores, top_k=self.top_k,
+                              out=(bg.sums, bg.top_val, bg.argmax))
 
     def capture(self, b: int) -> _BucketGraph:
         if b in self.graphs:
@@ -99,6 +119,11 @@ class Replica:
                                 device=dev)
         bg.sums = torch.empty((self.max_videos, self.engine.num_classes),
                               dtype=torch.float32, device=dev)
+        if self.scores is not None:
+            bg.top_val = torch.zeros((self.max_videos, self.top_k), dtype=torch.float32,
+                                     device=dev)
+            bg.argmax = torch.zeros((self.max_videos, self.top_k), dtype=torch.int32,
+                                    device=dev)
         with torch.cuda.stream(self.stream):
             for _ in range(2):                         # warm-up outside capture
                 self._run_eager(bg)
@@ -107,7 +132,7 @@ class Replica:
             with torch.cuda.graph(g, pool=self.pool, stream=self.stream):
                 self._decode(bg)
                 bg.logits = self.engine.forward(bg.frames, packed=self.packed)
-                _, bg.argmax = vops.video_reduce(bg.logits, bg.offsets, sums=bg.sums)
+                self._reduce(bg, bg.logits)
             self.stream.synchronize()
         bg.graph = g
         self.graphs[b] = bg
@@ -116,7 +141,7 @@ class Replica:
     def _run_eager(self, bg):
         self._decode(bg)
         logits = self.engine.forward(bg.frames, packed=self.packed)
-        vops.video_reduce(logits, bg.offsets, sums=bg.sums)
+        self._reduce(bg, logits)
 
     def submit(self, videos: Sequence[Tuple[int, Sequence[int]]],
                out: Optional[torch.Tensor] = None):
@@ -127,7 +152,10 @@ class Replica:
         has completed. The argmax lands in ``out`` (a pinned host int32
         tensor of >= #videos entries) when given; otherwise in this
         replica's staging ring, whose slots are reused ``pinned_ring``
-        submissions later -- read it before then.
+        submissions later -- read it before then. With ``scores`` set the
+        second entry is the int32 [#videos][top_k] class indices, best first,
+        and their scores land in ``last_top_val`` (pinned fp32
+        [#videos][top_k], a ring slot, valid under the same event).
         """
         nvid = len(videos)
         if nvid == 0 or nvid > self.max_videos:
@@ -135,7 +163,8 @@ class Replica:
         n = sum(len(s) for _, s in videos)
         b = self.bucket_for(max(n, 1))
         bg = self.graphs.get(b) or self.capture(b)
-        host, out_host, ev = self._ring[self._ring_idx]
+        slot = self._ring_idx
+        host, out_host, ev = self._ring[slot]
         self._ring_idx = (self._ring_idx + 1) % len(self._ring)
         ev.synchronize()                      # previous use of this staging slot done
         vids, starts, offs = [], [], [0]
@@ -156,6 +185,10 @@ class Replica:
             bg.graph.replay()
             dst = out if out is not None else out_host
             dst[:nvid].copy_(bg.argmax[:nvid], non_blocking=True)
+            if self.scores is not None:
+                val = self._ring_val[slot]
+                val[:nvid].copy_(bg.top_val[:nvid], non_blocking=True)
+                self.last_top_val = val[:nvid]
             ev.record(self.stream)
         return ev, dst[:nvid], nvid
 
@@ -167,7 +200,8 @@ class FusedR2P1D:
                  replicas: int = 1, max_clips: int = 256, max_videos: int = 64,
                  buckets: Sequence[int] = DEFAULT_BUCKETS, autotune: bool = True,
                  seed: int = 0, ckpt_path: Optional[str] = None, dtype="bf16",
-                 clip_length: int = DEFAULT_CLIP_LENGTH):
+                 clip_length: int = DEFAULT_CLIP_LENGTH, scores: Optional[str] = None,
+                 top_k: int = 1):
         clip_length = check_clip_length(clip_length)
         check_max_clips(max_clips, 1, 5, _as_dtype(dtype), clip_length)
         net = build_network(1, 5, num_classes, depth=depth, seed=seed, ckpt_path=ckpt_path)
@@ -175,7 +209,8 @@ class FusedR2P1D:
                                   clip_length=clip_length)
         self.device = device
         self.autotune = autotune
-        self.replicas = [Replica(self.engine, max_clips, max_videos, buckets)
+        self.replicas = [Replica(self.engine, max_clips, max_videos, buckets,
+                                 scores=scores, top_k=top_k)
                          for _ in range(replicas)]
         self._tuned = set()
 

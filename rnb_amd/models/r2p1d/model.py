@@ -34,16 +34,18 @@ MI355X-specific behaviour (documented deviations):
 """
 from __future__ import annotations
 
+import json
 import os
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
+from ...ops import video as vops
 from ...runner_model import RunnerModel
 from ...selector import QueueSelector
 from ...timecard import TimeCard, TimeCardList
-from ...video_path_provider import (DirectoryVideoPathIterator,
+from ...video_path_provider import (DirectoryLabels, DirectoryVideoPathIterator,
                                     SyntheticVideoPathIterator, VideoPathIterator)
 from .decoder import make_decoder
 from .engine import (GraphedEngine, R2P1DEngine, boundary_channels_p, boundary_shape,
@@ -521,7 +523,13 @@ class R2P1DLoader(RunnerModel):
     ``views`` rows for each and counts rows in ``time_card.num_clips``, so
     slots, buckets and the aggregator (which sums every row of a video) are
     sized by ``max_clips`` as before. ``crop`` and ``filter`` are shorthands
-    for the same keys of ``decoder_args``."""
+    for the same keys of ``decoder_args``.
+
+    ``labels="dir"``: the class index of a ``root/<name>/<video>`` path
+    (``DirectoryLabels``: ``<name>``'s position among ``root``'s sorted
+    sub-directories, or its line in ``class_names=FILE``) travels in
+    ``time_card.extra["label"]`` to the aggregator, which counts top-1 / top-k
+    hits by it; synthetic paths get none."""
 
     # decode kernels are tiny and gate the consumers: run them on a
     # high-priority HIP stream so they do not queue behind the conv kernels
@@ -530,8 +538,15 @@ class R2P1DLoader(RunnerModel):
     def __init__(self, device, num_clips_population=(1, 15), num_clips_weights=(10, 1),
                  decoder="synthetic", seed=None, max_clips=DEFAULT_MAX_CLIPS,
                  warmup=3, dtype=None, decoder_args=None,
-                 clip_length=DEFAULT_CLIP_LENGTH, crop=None, filter=None, **unused):
+                 clip_length=DEFAULT_CLIP_LENGTH, crop=None, filter=None, labels=None,
+                 class_names=None, **unused):
         super().__init__(device)
+        if labels not in (None, "dir"):
+            raise ValueError("R2P1DLoader: labels = %r, expected None or \"dir\"" % (labels,))
+        if class_names is not None and labels is None:
+            raise ValueError("R2P1DLoader: class_names = %r needs labels = \"dir\""
+                             % (class_names,))
+        self.labels = DirectoryLabels(class_names) if labels == "dir" else None
         self.clip_length = check_clip_length(clip_length)
         self.sampler = R2P1DSampler(clip_length=self.clip_length,
                                     num_clips_population=num_clips_population,
@@ -555,6 +570,10 @@ class R2P1DLoader(RunnerModel):
         with what a numerics check needs to decode the same clips again."""
         vid, length = self.decoder.probe(path)
         starts = (self.sampler.sample(length) or [])[:self.max_clips // self.views]
+        if time_card is not None and self.labels is not None:
+            label = self.labels.label(path)
+            if label is not None:
+                time_card.extra["label"] = label
         if time_card is not None and (time_card.id % CHECK_EVERY == 0 or (
                 len(starts) >= 15 and time_card.id % CHECK_EVERY_LARGE == 0)):
             # one start per output row, so that the sample files keep
@@ -696,9 +715,26 @@ class R2P1DAggregator(RunnerModel):
     one brought (``extra["rows"]``, set by the gathering runner) or, for whole
     videos, by their clip counts. Segments of one video may arrive in
     different batches; a video is emitted once all ``aggregate`` segments
-    arrived (reference model.py:238-285, with batching added)."""
+    arrived (reference model.py:238-285, with batching added).
 
-    def __init__(self, device, aggregate=1, clip_length=DEFAULT_CLIP_LENGTH, **unused):
+    ``scores`` / ``top_k`` (ops/video.video_scores: "logit_sum", "logit_mean",
+    "softmax_sum", "softmax_mean"; 1 <= top_k <= 16): with the defaults
+    ("logit_sum", 1) a video's output is the argmax of its summed logits, an
+    int, computed on the host as the reference does. Otherwise one
+    ``video_scores`` launch per call scores every video of the call on the
+    tensor's device (the torch mirror on a CPU device), only the [videos][k]
+    results cross to the host, and a video's output is ``(classes, scores)``,
+    two k-tuples, best first. With ``aggregate`` > 1 a segment contributes its
+    "_sum" scores and its row count; the last one to arrive takes the top-k of
+    the total (divided by the total row count for the "_mean" kinds).
+
+    A time card with ``extra["label"]`` (R2P1DLoader ``labels``) is counted in
+    every mode: ``runtime_stats()`` returns ``eval_videos``, ``eval_top1`` and
+    ``eval_top<k>``. ``results_path``: one JSON line per emitted video (id,
+    label, classes, scores) appended to ``<results_path>.<pid>.jsonl``."""
+
+    def __init__(self, device, aggregate=1, clip_length=DEFAULT_CLIP_LENGTH,
+                 scores="logit_sum", top_k=1, results_path=None, **unused):
         super().__init__(device)
         # sizes nothing by it (logit rows only); checked so that a pipeline's
         # "defaults" value is validated at every step
@@ -707,12 +743,112 @@ class R2P1DAggregator(RunnerModel):
         self.results = {}
         self._check_dir = os.environ.get("RNB_CHECK_DIR") or None
         self._checked = 0
+        self.scores, self.top_k = str(scores), int(top_k)
+        vops.check_score_args(self.scores, self.top_k)
+        self._scored = (self.scores, self.top_k) != ("logit_sum", 1)
+        self.results_path = results_path or None
+        self._results_file = None
+        self.eval_videos = self.eval_top1 = self.eval_topk = 0
 
     def _sum(self, tensor) -> np.ndarray:
         return tensor.detach().float().cpu().numpy().sum(axis=0)
 
+    def runtime_stats(self) -> dict:
+        if self._results_file is not None:
+            self._results_file.flush()
+        if not self.eval_videos:
+            return {}
+        st = {"eval_videos": self.eval_videos, "eval_top1": self.eval_top1}
+        st["eval_top%d" % self.top_k] = self.eval_topk
+        return st
+
+    def _tracks(self, tc) -> bool:
+        return self.results_path is not None or "label" in tc.extra
+
+    def _emit(self, tc, classes, scores) -> None:
+        """Count one finished video against its label; log it to results_path."""
+        label = tc.extra.get("label")
+        if label is not None:
+            self.eval_videos += 1
+            self.eval_top1 += int(classes[0] == label)
+            self.eval_topk += int(label in classes)
+        if self.results_path is not None:
+            if self._results_file is None:
+                self._results_file = open("%s.%d.jsonl" % (self.results_path, os.getpid()), "a")
+            self._results_file.write(json.dumps(
+                {"id": int(tc.id), "label": None if label is None else int(label),
+                 "classes": [int(c) for c in classes],
+                 "scores": [float(s) for s in scores]}) + "\n")
+            self._results_file.flush()
+
+    @staticmethod
+    def _card_rows(tc) -> int:
+        n = tc.extra.get("rows")
+        if n is None:
+            n = tc.num_clips if tc.num_clips is not None else 1
+        return n
+
+    def _top(self, rows, offs, kind):
+        """One video_scores launch over ``rows``; the [videos][k] results on the host."""
+        off = torch.tensor(offs, dtype=torch.int32, device=rows.device)
+        sc, tv, ti = vops.video_scores(rows, off, scores=kind, top_k=self.top_k)
+        return sc, tv.cpu().tolist(), ti.cpu().tolist()
+
+    def _call_scored(self, tensor, time_card):
+        batched = isinstance(time_card, TimeCardList)
+        cards = time_card.time_cards if batched else [time_card]
+        offs = [0]
+        for tc in cards:
+            offs.append(offs[-1] + (self._card_rows(tc) if batched else int(tensor.shape[0])))
+        rows = tensor.detach().float()
+        k = self.top_k
+        empty = ((-1,) * k, (0.0,) * k)
+        done_cards, outs = [], []
+        if self.aggregate == 1:
+            _, tv, ti = self._top(rows, offs, self.scores)
+            for v, tc in enumerate(cards):
+                out = (tuple(ti[v]), tuple(tv[v]))
+                self._emit(tc, *out)
+                done_cards.append(tc)
+                outs.append(out)
+        else:
+            # segments add their "_sum" scores (kept on the tensor's device)
+            # and row counts per id; the finished totals are ranked together
+            sums = self._top(rows, offs, self.scores.replace("mean", "sum"))[0]
+            totals, slots, firsts = [], [], []
+            for v, tc in enumerate(cards):
+                n = offs[v + 1] - offs[v]
+                prev = self.results.get(tc.id)
+                total = sums[v].clone() if prev is None else prev[0] + sums[v]
+                got = [tc] if prev is None else prev[1] + [tc]
+                n += 0 if prev is None else prev[2]
+                if len(got) < self.aggregate:
+                    self.results[tc.id] = (total, got, n)
+                    continue
+                del self.results[tc.id]
+                done_cards.append(TimeCard.merge(got))
+                firsts.append(got[0])       # merge() drops extra: the label is read here
+                outs.append(empty)
+                if n > 0:
+                    totals.append(total / n if self.scores.endswith("mean") else total)
+                    slots.append(len(outs) - 1)
+            if totals:
+                _, tv, ti = self._top(torch.stack(totals), list(range(len(totals) + 1)),
+                                      "logit_sum")
+                for j, slot in enumerate(slots):
+                    outs[slot] = (tuple(ti[j]), tuple(tv[j]))
+            for tc, out in zip(firsts, outs):
+                self._emit(tc, *out)
+        if not done_cards:
+            return None, None, None
+        if not batched:
+            return None, outs[0], done_cards[0]
+        return None, outs, TimeCardList(done_cards)
+
     def __call__(self, tensors, non_tensors, time_card):
         tensor = tensors[0]
+        if self._scored:
+            return self._call_scored(tensor, time_card)
         if isinstance(time_card, TimeCardList):
             cards = time_card.time_cards
             arr = tensor.detach().float().cpu().numpy()
@@ -734,6 +870,8 @@ class R2P1DAggregator(RunnerModel):
                 done_cards.append(tc)
                 batched = isinstance(time_card, TimeCardList)
                 outs.append(int(result.argmax()) if part.shape[0] or not batched else -1)
+                if self._tracks(tc):
+                    self._emit(tc, (outs[-1],), (float(result[outs[-1]]),))
                 continue
             prev = self.results.get(tc.id)
             total = result if prev is None else prev[0] + result
@@ -750,6 +888,8 @@ class R2P1DAggregator(RunnerModel):
                              segments=self.aggregate, clip_length=self.clip_length)
             done_cards.append(TimeCard.merge(got))
             outs.append(int(total.argmax()))
+            if self._tracks(got[0]):
+                self._emit(got[0], (outs[-1],), (float(total[outs[-1]]),))
         if not done_cards:
             return None, None, None
         if not isinstance(time_card, TimeCardList):

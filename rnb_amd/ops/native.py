@@ -70,9 +70,12 @@ def loaded_paths():
     return sorted(_lib_path(n) for n in _libs)
 
 
-def _check(rc: int, what: str, lib: Optional[ctypes.CDLL] = None) -> None:
+def _check(rc: int, what: str, lib: Optional[ctypes.CDLL] = None, args=None) -> None:
+    """``args``: {negative code: description of the argument it rejects}."""
     if rc == 0:
         return
+    if rc < 0 and args and rc in args:
+        raise ValueError("%s: argument %s (code %d)" % (what, args[rc], rc))
     if rc < 0:
         raise RuntimeError("%s: shape/contract check failed (code %d)" % (what, rc))
     msg = ""
@@ -332,6 +335,8 @@ class Kernels:
         lib.rnb_video_reduce.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_void_p]
+        lib.rnb_video_scores.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + \
+            [ctypes.c_void_p]
         lib.rnb_halo_launch_v.argtypes = [ctypes.POINTER(HaloParams), ctypes.c_int,
                                           ctypes.c_void_p]
         lib.rnb_halo_launch_v.restype = ctypes.c_int
@@ -1009,6 +1014,16 @@ class Kernels:
                      stream):
         _check(self.lib.rnb_video_reduce(logits_ptr, offsets_ptr, sums_ptr, argmax_ptr,
                                          nvid, ncls, stream), "video_reduce")
+
+    def video_scores(self, logits_ptr, offsets_ptr, scores_ptr, top_val_ptr, top_idx_ptr,
+                     nvid, ncls, k, softmax, mean, stream):
+        # the SC_ERR_* codes of csrc/score_ops.hip; nothing is launched on any of them
+        _check(self.lib.rnb_video_scores(logits_ptr, offsets_ptr, scores_ptr, top_val_ptr,
+                                         top_idx_ptr, nvid, ncls, k, int(softmax), int(mean),
+                                         stream), "video_scores", args={
+            -21: "ncls = %d is outside 1..4096" % ncls,
+            -22: "k = %d is outside 1..min(16, ncls = %d)" % (k, ncls),
+            -23: "offsets / top_val / top_idx is a null pointer"})
 
 
 class Jpeg:

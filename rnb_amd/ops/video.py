@@ -826,3 +826,89 @@ def video_reduce(logits: torch.Tensor, offsets: torch.Tensor,
     arg = torch.tensor([int(torch.argmax(out[v])) if off[v + 1] > off[v] else -1
                         for v in range(nvid)], dtype=torch.int32)
     return out, arg
+
+
+SCORE_KINDS = ("logit_sum", "logit_mean", "softmax_sum", "softmax_mean")
+SCORE_MAX_CLASSES = 4096
+SCORE_MAX_K = 16
+
+
+def check_score_args(scores: str, top_k: int, ncls: Optional[int] = None) -> None:
+    """The limits of the video_scores kernel, shared with its CPU mirror."""
+    if scores not in SCORE_KINDS:
+        raise ValueError("video_scores: scores = %r, expected one of %s"
+                         % (scores, ", ".join(SCORE_KINDS)))
+    if ncls is not None and not 1 <= ncls <= SCORE_MAX_CLASSES:
+        raise ValueError("video_scores: argument ncls = %d is outside 1..%d"
+                         % (ncls, SCORE_MAX_CLASSES))
+    if not 1 <= top_k <= SCORE_MAX_K or (ncls is not None and top_k > ncls):
+        raise ValueError("video_scores: argument k = %d is outside 1..min(%d, ncls%s)"
+                         % (top_k, SCORE_MAX_K, "" if ncls is None else " = %d" % ncls))
+
+
+def top_k_stable(scores: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k largest per row, descending, ties to the lower index (a stable
+    sort: ``torch.topk`` promises no tie order). Returns (values, int32 indices)."""
+    order = torch.sort(scores, dim=1, descending=True, stable=True)[1][:, :k]
+    return scores.gather(1, order), order.to(torch.int32)
+
+
+def video_scores(logits: torch.Tensor, offsets: torch.Tensor, scores: str = "softmax_mean",
+                 top_k: int = 5, out=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Per-video class scores over the rows [offsets[v], offsets[v+1]) + top-k.
+
+    ``scores``: "logit_sum" / "logit_mean" add the rows as they are,
+    "softmax_sum" / "softmax_mean" add each row's softmax; "_mean" divides by
+    the row count. Returns (scores [nvid][ncls] fp32, top_val [nvid][k] fp32,
+    top_idx [nvid][k] int32): the k largest scores, descending, ties to the
+    lower class index. An empty video has scores 0, top_idx -1 and top_val 0.
+    ``out``: the three tensors preallocated (graph capture). On a GPU this is
+    one launch of the video_scores kernel; on the CPU a torch fp32 mirror."""
+    nvid = offsets.numel() - 1
+    ncls = int(logits.shape[1])
+    k = int(top_k)
+    check_score_args(scores, k, None)
+    softmax, mean = scores.startswith("softmax"), scores.endswith("mean")
+    if logits.is_cuda:
+        from .native import kernels
+        if logits.dtype != torch.float32:
+            raise ValueError("video_scores: logits must be fp32, got %s" % logits.dtype)
+        dev = logits.device
+        if out is None:
+            out = (torch.empty((nvid, ncls), dtype=torch.float32, device=dev),
+                   torch.empty((nvid, k), dtype=torch.float32, device=dev),
+                   torch.empty((nvid, k), dtype=torch.int32, device=dev))
+        sc, tv, ti = out
+        if sc.shape[0] < nvid or sc.shape[1] != ncls or tuple(tv.shape) != (sc.shape[0], k) \
+                or tuple(ti.shape) != (sc.shape[0], k) or ti.dtype != torch.int32 \
+                or sc.dtype != torch.float32 or tv.dtype != torch.float32 \
+                or not (sc.is_contiguous() and tv.is_contiguous() and ti.is_contiguous()):
+            raise ValueError("video_scores: out must be contiguous (fp32 [>=%d][%d], "
+                             "fp32 [n][%d], int32 [n][%d])" % (nvid, ncls, k, k))
+        kernels().video_scores(logits.contiguous().data_ptr(),
+                               offsets.to(torch.int32).contiguous().data_ptr(),
+                               sc.data_ptr(), tv.data_ptr(), ti.data_ptr(), nvid, ncls, k,
+                               softmax, mean, torch.cuda.current_stream(dev).cuda_stream)
+        return sc, tv, ti
+    check_score_args(scores, k, ncls)
+    off = offsets.tolist()
+    rows = logits.float()
+    if softmax:
+        rows = torch.softmax(rows, dim=1)
+    sc = torch.zeros((nvid, ncls), dtype=torch.float32)
+    for v in range(nvid):
+        n = off[v + 1] - off[v]
+        if n > 0:
+            sc[v] = rows[off[v]:off[v + 1]].sum(0)
+            if mean:
+                sc[v] /= n
+    tv, ti = top_k_stable(sc, k)
+    for v in range(nvid):
+        if off[v + 1] <= off[v]:
+            tv[v] = 0.
+            ti[v] = -1
+    if out is not None:
+        for dst, src in zip(out, (sc, tv, ti)):
+            dst[:nvid].copy_(src)
+        return out
+    return sc, tv, ti

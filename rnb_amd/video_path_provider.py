@@ -29,6 +29,47 @@ class DirectoryVideoPathIterator(VideoPathIterator):
         return itertools.cycle(self.videos)
 
 
+class DirectoryLabels:
+    """Class index of a ``root/<name>/<video>`` path: the index of ``<name>``.
+
+    By default that is its position in the sorted list of ``root``'s
+    sub-directories (the Kinetics / torchvision ``ImageFolder`` convention),
+    listed once per root. ``class_names``: a file of one name per line, index =
+    line number, for a tree that holds a subset of the model's classes; a
+    directory name that is not in it is an error. Synthetic paths have no
+    label (``None``)."""
+
+    def __init__(self, class_names=None):
+        self.class_names = class_names
+        self._index = None
+        if class_names is not None:
+            with open(class_names) as f:
+                names = [line.rstrip("\r\n") for line in f]
+            while names and not names[-1]:
+                names.pop()
+            self._index = {}
+            for i, name in enumerate(names):
+                self._index.setdefault(name, i)
+        self._roots = {}
+
+    def label(self, path):
+        if not isinstance(path, str) or path.startswith("synthetic://"):
+            return None
+        ldir = os.path.dirname(os.path.abspath(path))
+        name, root = os.path.basename(ldir), os.path.dirname(ldir)
+        if self._index is not None:
+            if name not in self._index:
+                raise ValueError("labels: directory %r of %s is not a line of class_names = %r"
+                                 % (name, path, self.class_names))
+            return self._index[name]
+        index = self._roots.get(root)
+        if index is None:
+            index = {d: i for i, d in enumerate(sorted(
+                d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d))))}
+            self._roots[root] = index
+        return index[name]
+
+
 class SyntheticVideoPathIterator(VideoPathIterator):
     """Endless ``synthetic://<id>?frames=<n>`` paths.
 
