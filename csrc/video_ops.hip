@@ -81,8 +81,11 @@ __global__ void clipgen_u8_kernel(uint8_t* __restrict__ out, const int* __restri
 // arguments (no metadata upload, no host synchronisation: the loader stage
 // issues it per video; rnb_amd/models/r2p1d/decoder.py).
 #define CLIPGEN_MAX_CLIPS 32
+// step_p / step_q: frame f of a clip is source frame start + (f * step_p) /
+// step_q (sampler.clip_frames); the launcher keeps F * step_p inside an int.
 struct ClipgenArgs {
   int vid, nclips;
+  int step_p, step_q;
   int starts[CLIPGEN_MAX_CLIPS];
 };
 
@@ -95,7 +98,8 @@ __global__ void clipgen_video_kernel(uint8_t* __restrict__ out, ClipgenArgs a, i
   const long long frame = px0 / hw;
   const int clip = (int)(frame / F);
   const uint32_t vid = (uint32_t)a.vid;
-  const uint32_t fr = (uint32_t)(a.starts[clip] + (int)(frame - (long long)clip * F));
+  const int f = (int)(frame - (long long)clip * F);
+  const uint32_t fr = (uint32_t)(a.starts[clip] + (f * a.step_p) / a.step_q);
   const uint32_t pix0 = (uint32_t)(px0 - frame * hw);
   const int n = (int)min(16LL, min(total_px - px0, hw - (long long)pix0));
   uint32_t words[12];
@@ -150,7 +154,9 @@ __global__ void nv12gen_kernel(uint8_t* __restrict__ out, ClipgenArgs a,
   const int clip = (int)(frame / F);
   const int start = FROM_ARRAYS ? starts[clip] : a.starts[clip];
   const uint32_t vid = (uint32_t)(FROM_ARRAYS ? vids[clip] : a.vid);
-  const uint32_t fr = (uint32_t)(start + (int)(frame - (long long)clip * F));
+  const int f = (int)(frame - (long long)clip * F);
+  // the device-array form has no step: its clips are consecutive frames
+  const uint32_t fr = (uint32_t)(start + (FROM_ARRAYS ? f : (f * a.step_p) / a.step_q));
   const long long off0 = b0 - frame * fbytes;
   uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -844,14 +850,23 @@ int rnb_clipgen_u8(void* out, const int* vids, const int* starts, int nclips, in
   return (int)hipGetLastError();
 }
 
-int rnb_clipgen_video(void* out, int vid, const int* starts, int nclips, int F, int H, int W,
-                      hipStream_t stream) {
+// F * step_p must fit an int: the kernels compute (f * step_p) / step_q in 32 bits
+static bool clipgen_step_ok(int F, int step_p, int step_q) {
+  return F >= 1 && F <= 65535 && step_p >= 1 && step_q >= 1 &&
+         (long long)F * step_p <= 2147483647LL;
+}
+
+int rnb_clipgen_video_step(void* out, int vid, const int* starts, int nclips, int F, int H,
+                           int W, int step_p, int step_q, hipStream_t stream) {
   if (nclips <= 0) return 0;
   if (nclips > CLIPGEN_MAX_CLIPS) return -3;
   if (((long long)H * W) % 16 != 0) return -2;
+  if (!clipgen_step_ok(F, step_p, step_q)) return -2;
   ClipgenArgs a;
   a.vid = vid;
   a.nclips = nclips;
+  a.step_p = step_p;
+  a.step_q = step_q;
   for (int i = 0; i < CLIPGEN_MAX_CLIPS; ++i) a.starts[i] = i < nclips ? starts[i] : 0;
   const long long threads = ((long long)nclips * F * H * W + 15) / 16;
   hipLaunchKernelGGL(clipgen_video_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
@@ -859,13 +874,21 @@ int rnb_clipgen_video(void* out, int vid, const int* starts, int nclips, int F, 
   return (int)hipGetLastError();
 }
 
-int rnb_nv12gen_video(void* out, int vid, const int* starts, int nclips, int F, int H, int W,
+int rnb_clipgen_video(void* out, int vid, const int* starts, int nclips, int F, int H, int W,
                       hipStream_t stream) {
+  return rnb_clipgen_video_step(out, vid, starts, nclips, F, H, W, 1, 1, stream);
+}
+
+int rnb_nv12gen_video_step(void* out, int vid, const int* starts, int nclips, int F, int H,
+                           int W, int step_p, int step_q, hipStream_t stream) {
   if (nclips <= 0) return 0;
   if (nclips > CLIPGEN_MAX_CLIPS || H % 2 || W % 2) return -3;
+  if (!clipgen_step_ok(F, step_p, step_q)) return -2;
   ClipgenArgs a;
   a.vid = vid;
   a.nclips = nclips;
+  a.step_p = step_p;
+  a.step_q = step_q;
   for (int i = 0; i < CLIPGEN_MAX_CLIPS; ++i) a.starts[i] = i < nclips ? starts[i] : 0;
   const long long bytes = (long long)nclips * F * H * W * 3 / 2;
   const long long threads = (bytes + 15) / 16;
@@ -873,6 +896,11 @@ int rnb_nv12gen_video(void* out, int vid, const int* starts, int nclips, int F, 
                      0, stream, (uint8_t*)out, a, (const int*)nullptr, (const int*)nullptr, F, H,
                      W);
   return (int)hipGetLastError();
+}
+
+int rnb_nv12gen_video(void* out, int vid, const int* starts, int nclips, int F, int H, int W,
+                      hipStream_t stream) {
+  return rnb_nv12gen_video_step(out, vid, starts, nclips, F, H, W, 1, 1, stream);
 }
 
 // batched form (per-clip video id / start frame in device arrays: graph-capturable)
@@ -883,6 +911,7 @@ int rnb_nv12gen(void* out, const int* vids, const int* starts, int nclips, int F
   ClipgenArgs a;
   a.vid = 0;
   a.nclips = nclips;
+  a.step_p = a.step_q = 1;
   const long long bytes = (long long)nclips * F * H * W * 3 / 2;
   const long long threads = (bytes + 15) / 16;
   hipLaunchKernelGGL(nv12gen_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,

@@ -21,6 +21,14 @@ dequantisation and inverse DCT (``jpeg_idct`` HIP kernel) and the same
 ``reduce=2 | 4 | 8 | "auto"`` has the IDCT write the frame at 1/2, 1/4 or 1/8
 size (libjpeg's ``scale_denom``).
 
+A clip is ``clip_length`` frames of the file taken at a step: every ``decode``
+takes ``step=(p, q)`` and reads the source frames ``sampler.clip_frames(start,
+F, step)``, frame ``f`` at ``start + (f * p) // q``. ``(1, 1)``, the default,
+is consecutive frames. ``source_fps_of(vid)`` is the file's frame rate as an
+``(n, d)`` pair where one is known (the Y4M header's ``F`` field, else the
+``source_fps`` constructor argument), which the loader turns into a step for a
+target ``fps``.
+
 Every decoder returns NDHWC clips normalised with the Kinetics mean/std:
 ``fp32 [n, 8, 112, 112, 4]`` (reference precision) or ``bf16 [n, 8, 112, 112, 8]``
 (the layouts the fp32 / bf16 stem conv kernels consume).
@@ -41,11 +49,22 @@ import torch
 from ...ops import video as vops
 from ...utils import mjpeg, y4m
 from ...video_path_provider import parse_synthetic_path
+from .sampler import clip_frames, clip_span, parse_rate
+
+
+def _rate_pair(source_fps, name: str) -> Optional[Tuple[int, int]]:
+    """A decoder's ``source_fps`` argument (a number or ``"n:d"``) as ``(n, d)``."""
+    try:
+        rate = parse_rate(source_fps, "source_fps")
+    except ValueError as err:
+        raise ValueError("%s: %s" % (name, err))
+    return None if rate is None else (rate.numerator, rate.denominator)
 
 
 class Decoder:
     dtype = torch.bfloat16
     views = 1                # output rows per clip (file-backed decoders: crop={"views": 3})
+    source_fps = None        # (n, d) frames per second of the files, where it was given
 
     def probe(self, path: str) -> Tuple[int, int]:
         """(video id, number of frames)."""
@@ -64,8 +83,13 @@ class Decoder:
     def _decode_surface(self, surf, out=None):
         return vops.preprocess(surf, out=out, dtype=self.dtype)
 
-    def decode(self, vid: int, starts: Sequence[int], out: Optional[torch.Tensor] = None
-               ) -> torch.Tensor:
+    def source_fps_of(self, vid: int) -> Optional[Tuple[int, int]]:
+        """Frame rate of a probed video as ``(n, d)``, or ``None`` if unknown."""
+        return self.source_fps
+
+    def decode(self, vid: int, starts: Sequence[int], out: Optional[torch.Tensor] = None,
+               step=(1, 1)) -> torch.Tensor:
+        """Clips of ``clip_frames(start, F, step)`` for every start."""
         raise NotImplementedError
 
 
@@ -82,9 +106,11 @@ class SyntheticDecoder(Decoder):
 
     def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
                  width: int = 112, dtype=torch.bfloat16, source: str = "nv12",
-                 src_width: int = vops.SOURCE_W, src_height: int = vops.SOURCE_H):
+                 src_width: int = vops.SOURCE_W, src_height: int = vops.SOURCE_H,
+                 source_fps=None):
         if source not in ("nv12", "rgb"):
             raise ValueError("unknown synthetic source %r" % (source,))
+        self.source_fps = _rate_pair(source_fps, "SyntheticDecoder")
         self.device = device
         self.F, self.H, self.W = clip_length, height, width
         self.dtype = dtype
@@ -95,12 +121,12 @@ class SyntheticDecoder(Decoder):
     def probe(self, path):
         return parse_synthetic_path(path)
 
-    def decode(self, vid, starts, out=None):
+    def decode(self, vid, starts, out=None, step=(1, 1)):
         n = len(starts)
         if n == 0:
             return self.empty()
         if self.source == "nv12":
-            return self._decode_nv12(vid, starts, out)
+            return self._decode_nv12(vid, starts, out, step)
         surf = None
         if self.device.type == "cuda":
             # one reusable decoder surface: uses of it are ordered on the stream
@@ -108,14 +134,15 @@ class SyntheticDecoder(Decoder):
                 self._surface = torch.empty((max(n, 15), self.F, self.H, self.W, 3),
                                             dtype=torch.uint8, device=self.device)
             surf = self._surface[:n]
-        surf = vops.clipgen_video(vid, starts, self.F, self.H, self.W, self.device, out=surf)
+        surf = vops.clipgen_video(vid, starts, self.F, self.H, self.W, self.device, out=surf,
+                                  step=step)
         return vops.preprocess(surf, out=out, dtype=self.dtype)
 
     def warmup(self, n: int) -> None:
         for i in range(n):
             self.decode(i, [0])
 
-    def _decode_nv12(self, vid, starts, out):
+    def _decode_nv12(self, vid, starts, out, step=(1, 1)):
         n = len(starts)
         surf = None
         if self.device.type == "cuda":
@@ -125,7 +152,7 @@ class SyntheticDecoder(Decoder):
                                             dtype=torch.uint8, device=self.device)
             surf = self._surface[:n * self.F]
         surf = vops.nv12gen(int(vid), list(starts), self.F, self.src_h, self.src_w,
-                            self.device, out=surf)
+                            self.device, out=surf, step=step)
         if out is None:
             out = torch.empty((n, self.F, self.H, self.W, vops.clip_channels(self.dtype)),
                               dtype=self.dtype, device=self.device)
@@ -138,11 +165,13 @@ class NpyDecoder(Decoder):
     """Pre-decoded ``.npy`` videos (uint8 [frames, H, W, 3])."""
 
     def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
-                 width: int = 112, dtype=torch.bfloat16):
+                 width: int = 112, dtype=torch.bfloat16, source_fps=None):
         self.device = device
         self.F, self.H, self.W = clip_length, height, width
         self.dtype = dtype
+        self.source_fps = _rate_pair(source_fps, "NpyDecoder")
         self._ids = {}
+        self._paths = {}           # video id -> path
         self._arrays = {}          # video id -> memory-mapped frames
 
     def probe(self, path):
@@ -151,16 +180,26 @@ class NpyDecoder(Decoder):
             raise ValueError("%s: expected uint8 [F, %d, %d, 3], got %s %s"
                              % (path, self.H, self.W, arr.dtype, arr.shape))
         vid = self._ids.setdefault(path, len(self._ids))
+        self._paths[vid] = path
         self._arrays[vid] = arr
         return vid, arr.shape[0]
 
-    def decode(self, vid, starts, out=None):
+    def decode(self, vid, starts, out=None, step=(1, 1)):
         if len(starts) == 0:
             return self.empty()
         arr = self._arrays.get(vid)
         if arr is None:
             raise KeyError("video id %r was not probed" % (vid,))
-        clips = np.stack([np.asarray(arr[s:s + self.F]) for s in starts])
+        if tuple(step) == (1, 1):
+            clips = np.stack([np.asarray(arr[s:s + self.F]) for s in starts])
+        else:
+            span = clip_span(self.F, step)
+            for s in starts:
+                if s < 0 or s + span > arr.shape[0]:
+                    raise ValueError("%s: clip at frame %d (span %d at step %d/%d) is outside "
+                                     "the %d frames" % (self._paths[vid], s, span, step[0],
+                                                        step[1], arr.shape[0]))
+            clips = np.stack([np.asarray(arr[clip_frames(s, self.F, step)]) for s in starts])
         t = torch.from_numpy(clips)
         if self.device.type == "cuda":
             t = t.pin_memory().to(self.device, non_blocking=True)
@@ -251,8 +290,9 @@ class _StagedFileDecoder(Decoder):
 
     def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
                  width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full",
-                 filter: str = "bilinear"):
+                 filter: str = "bilinear", source_fps=None):
         name = type(self).__name__
+        self.source_fps = _rate_pair(source_fps, name)
         self.views, self.short_side = 1, None
         if isinstance(crop, dict):
             unknown = sorted(set(crop) - {"short_side", "views"})
@@ -317,11 +357,12 @@ class _StagedFileDecoder(Decoder):
         self._boxes[vid] = boxes
         return vid, hdr.num_frames
 
-    def _check_starts(self, path: str, starts, num_frames: int) -> None:
+    def _check_starts(self, path: str, starts, num_frames: int, step=(1, 1)) -> None:
+        span = clip_span(self.F, step)
         for s in starts:
-            if s < 0 or s + self.F > num_frames:
-                raise ValueError("%s: clip at frame %d (+%d) is outside the %d frames"
-                                 % (path, s, self.F, num_frames))
+            if s < 0 or s + span > num_frames:
+                raise ValueError("%s: clip at frame %d (span %d at step %d/%d) is outside the "
+                                 "%d frames" % (path, s, span, step[0], step[1], num_frames))
 
     def _map(self, vid: int, path: str):
         got = self._maps.get(vid)
@@ -468,7 +509,12 @@ class Y4mDecoder(_StagedFileDecoder):
     uploaded once. ``filter``: ``"bilinear"`` (two taps per axis, the default) or
     ``"antialias"``, the triangle filter widened by the downscale factor that
     PIL's ``resize(BILINEAR)`` and torchvision's ``Resize(antialias=True)``
-    apply (``yuv420_to_clip(filter=)``); both boxes lie inside the frame."""
+    apply (``yuv420_to_clip(filter=)``); both boxes lie inside the frame.
+
+    With a ``step`` other than ``(1, 1)`` a clip is no contiguous span: its F
+    selected frames (``clip_frames``) are copied one by one into the clip's
+    staging slot, packed ``frame_stride`` apart, each one's marker checked; the
+    upload per clip, its ``F * frame_stride`` bytes and the launch are the same."""
 
     _PLANES = {"420": vops.i420_planes, "422": vops.i422_planes, "444": vops.i444_planes}
 
@@ -476,6 +522,12 @@ class Y4mDecoder(_StagedFileDecoder):
 
     def _parse(self, path, mm, data):
         return y4m.read_header(path, data=mm)
+
+    def source_fps_of(self, vid):
+        """The header's ``F`` field; the ``source_fps`` argument where the
+        header has none (``F0:0`` or no ``F`` field)."""
+        n, d = self._videos[vid][1].fps
+        return (n, d) if n > 0 and d > 0 else self.source_fps
 
     def warmup(self, n: int) -> None:
         """Run the clip kernel on a zeroed upload buffer (no file needed)."""
@@ -493,7 +545,7 @@ class Y4mDecoder(_StagedFileDecoder):
                                     out=self._out(len(offsets), None), filter=self.filter)
 
     # -- decode ---------------------------------------------------------------
-    def decode(self, vid, starts, out=None, views=None):
+    def decode(self, vid, starts, out=None, views=None, step=(1, 1)):
         if len(starts) == 0:
             return self.empty()
         got = self._videos.get(vid)
@@ -501,24 +553,33 @@ class Y4mDecoder(_StagedFileDecoder):
             raise KeyError("video id %r was not probed" % (vid,))
         starts, rows = self._rows(starts, views)
         n = len(starts)
+        stepped = tuple(step) != (1, 1)
         path, hdr = got
         _, data = self._map(vid, path)
         span = self.F * hdr.frame_stride
         marker = np.frombuffer(y4m.FRAME_MARKER, dtype=np.uint8)
-        self._check_starts(path, starts, hdr.num_frames)
+        self._check_starts(path, starts, hdr.num_frames, step)
         planes = self._PLANES[hdr.sampling](hdr.width, hdr.height, len(y4m.FRAME_MARKER))
         offsets, crop = self._clip_args(vid, hdr, rows, span)
         with self._staged(max(n, 15) * span, n * span) as (entry, host, buf):
             for i, s in enumerate(starts):
-                a = hdr.frame_offset(s)
                 dst = host[i * span:(i + 1) * span]
-                np.copyto(dst, data[a:a + span])
-                heads = dst.reshape(self.F, hdr.frame_stride)[:, :len(marker)]
+                frames = dst.reshape(self.F, hdr.frame_stride)
+                if stepped:
+                    src = clip_frames(s, self.F, step)
+                    for f, fr in enumerate(src):
+                        a = hdr.frame_offset(fr)
+                        np.copyto(frames[f], data[a:a + hdr.frame_stride])
+                else:
+                    a = hdr.frame_offset(s)
+                    np.copyto(dst, data[a:a + span])
+                heads = frames[:, :len(marker)]
                 if not (heads == marker).all():
                     bad = int(np.nonzero((heads != marker).any(axis=1))[0][0])
                     raise ValueError("%s: frame %d does not start with a bare FRAME marker "
                                      "(field 'FRAME': %r); frame parameters are not supported"
-                                     % (path, s + bad, bytes(heads[bad])))
+                                     % (path, src[bad] if stepped else s + bad,
+                                        bytes(heads[bad])))
                 if entry is not None:     # this clip uploads while the next one is staged
                     buf[i * span:(i + 1) * span].copy_(
                         entry.pinned[i * span:(i + 1) * span], non_blocking=True)
@@ -608,7 +669,7 @@ class MjpegDecoder(_StagedFileDecoder):
     def __init__(self, device: torch.device, clip_length: int = 8, height: int = 112,
                  width: int = 112, dtype=torch.bfloat16, depth: int = 4, crop: str = "full",
                  threads: int = 4, entropy: str = "host", subseq_bytes: Optional[int] = None,
-                 filter: str = "bilinear", reduce=1):
+                 filter: str = "bilinear", reduce=1, source_fps=None):
         if isinstance(threads, bool) or not isinstance(threads, int) or not 1 <= threads <= 16:
             raise ValueError("MjpegDecoder: threads must be an integer in 1..16, got %r"
                              % (threads,))
@@ -625,7 +686,8 @@ class MjpegDecoder(_StagedFileDecoder):
         if reduce != "auto":
             vops.jpeg_reduce_points(reduce, "MjpegDecoder")
             reduce = int(reduce)
-        super().__init__(device, clip_length, height, width, dtype, depth, crop, filter)
+        super().__init__(device, clip_length, height, width, dtype, depth, crop, filter,
+                         source_fps)
         self.threads = threads
         self.entropy = entropy
         self.subseq_bytes = subseq_bytes
@@ -723,7 +785,17 @@ class MjpegDecoder(_StagedFileDecoder):
                                lambda span: self._warm_crop(W / s, H / s),
                                self._out(max(1, self.views), None), reduce=s)
 
-    def decode(self, vid, starts, out=None, views=None):
+    def _clip_index(self, idx, s: int, step):
+        """(offsets, lengths, source frames) of the clip at ``s``: slices of the
+        index for consecutive frames, else gathered by ``clip_frames`` (a
+        repeated frame is listed, and decoded, again)."""
+        if tuple(step) == (1, 1):
+            return idx.offsets[s:s + self.F], idx.lengths[s:s + self.F], None
+        src = clip_frames(s, self.F, step)
+        return (np.ascontiguousarray(idx.offsets[src]), np.ascontiguousarray(idx.lengths[src]),
+                src)
+
+    def decode(self, vid, starts, out=None, views=None, step=(1, 1)):
         if len(starts) == 0:
             return self.empty()
         got = self._videos.get(vid)
@@ -733,15 +805,16 @@ class MjpegDecoder(_StagedFileDecoder):
         n = len(starts)
         path, idx = got
         _, data = self._map(vid, path)
-        self._check_starts(path, starts, idx.num_frames)
+        self._check_starts(path, starts, idx.num_frames, step)
         self.stats["requests"] += 1
         if self.entropy == "gpu":
-            return self._decode_gpu_entropy(vid, path, idx, data, starts, out, rows)
+            return self._decode_gpu_entropy(vid, path, idx, data, starts, out, rows, step)
         span = self.F * idx.record_bytes
         self.stats["uploaded_bytes"] += n * span
         with self._staged(max(n, 15) * span, n * span) as (entry, host, buf):
             for i, s in enumerate(starts):
-                mjpeg.entropy_decode(data, idx.offsets[s:s + self.F], idx.lengths[s:s + self.F],
+                offsets, lengths, _ = self._clip_index(idx, s, step)
+                mjpeg.entropy_decode(data, offsets, lengths,
                                      host[i * span:(i + 1) * span], idx.record_bytes,
                                      self.threads, name=path, sampling=idx.sampling)
                 if entry is not None:     # this clip uploads while the next one decodes
@@ -794,7 +867,7 @@ class MjpegDecoder(_StagedFileDecoder):
             setattr(self, name, buf)
         return buf
 
-    def _decode_gpu_entropy(self, vid, path, idx, data, starts, out, rows):
+    def _decode_gpu_entropy(self, vid, path, idx, data, starts, out, rows, step=(1, 1)):
         n, F = len(starts), self.F
         nfr = n * F
         longest = self._max_len.get(vid)
@@ -804,14 +877,16 @@ class MjpegDecoder(_StagedFileDecoder):
         cap = max(n, 15) * F                                  # frames the entry is sized for
         head = (8 * (cap + 1) + 15) & ~15                     # the offset table, then the records
         stat_at = head + cap * per                            # then the status words come back
-        frames = [s + f for s in starts for f in range(F)]
+        frames = [fr for s in starts for fr in clip_frames(s, F, step)]
         with self._staged(stat_at + 4 * cap, stat_at) as (entry, host, buf):
             offs = host[:8 * (nfr + 1)].view(np.int64)
             pos = head
             for i, s in enumerate(starts):
-                got, rel = mjpeg.pack_scans(data, idx.offsets[s:s + F], idx.lengths[s:s + F],
+                offsets, lengths, src = self._clip_index(idx, s, step)
+                got, rel = mjpeg.pack_scans(data, offsets, lengths,
                                             host[pos:stat_at], idx.width, idx.height,
-                                            name=path, frame0=s, sampling=idx.sampling)
+                                            name=path, frame0=s, sampling=idx.sampling,
+                                            frames=src)
                 offs[i * F:(i + 1) * F] = rel[:F] + pos
                 if entry is not None:     # this clip uploads while the next one packs
                     buf[pos:pos + got].copy_(entry.pinned[pos:pos + got], non_blocking=True)
@@ -848,22 +923,28 @@ class MjpegDecoder(_StagedFileDecoder):
 def make_decoder(backend: str, device: torch.device, clip_length=8, height=112, width=112,
                  dtype=torch.bfloat16, decoder_args: Optional[dict] = None) -> Decoder:
     """``decoder_args``: backend-specific constructor arguments (``y4m``:
-    ``depth``, ``crop``, ``filter``; ``mjpeg``: ``depth``, ``crop``, ``filter``,
-    ``threads``, ``entropy``, ``subseq_bytes``, ``reduce``: 1, 2, 4, 8 or
-    ``"auto"``, the reduced-size IDCT); the other
-    backends take none and ignore it. ``crop`` is ``"full"``, ``"center"`` or
+    ``depth``, ``crop``, ``filter``, ``source_fps``; ``mjpeg``: ``depth``,
+    ``crop``, ``filter``, ``threads``, ``entropy``, ``subseq_bytes``,
+    ``source_fps``, ``reduce``: 1, 2, 4, 8 or ``"auto"``, the reduced-size
+    IDCT); the other backends take ``source_fps`` and ignore the rest.
+    ``source_fps`` (a number or ``"n:d"``) is the frame rate of files that
+    carry none, which a loader's ``fps`` needs (a Y4M header's ``F`` field
+    comes first). ``crop`` is ``"full"``, ``"center"`` or
     ``{"short_side": S, "views": 1 or 3}``; with three views the decoder returns
     three rows per clip (``Decoder.views``; 1 for every other decoder)."""
     if backend == "y4m":
         return Y4mDecoder(device, clip_length, height, width, dtype, **(decoder_args or {}))
     if backend == "mjpeg":
         return MjpegDecoder(device, clip_length, height, width, dtype, **(decoder_args or {}))
+    source_fps = (decoder_args or {}).get("source_fps")
     if backend in ("synthetic", "synthetic-nv12"):
-        return SyntheticDecoder(device, clip_length, height, width, dtype, source="nv12")
+        return SyntheticDecoder(device, clip_length, height, width, dtype, source="nv12",
+                                source_fps=source_fps)
     if backend == "synthetic-rgb":
-        return SyntheticDecoder(device, clip_length, height, width, dtype, source="rgb")
+        return SyntheticDecoder(device, clip_length, height, width, dtype, source="rgb",
+                                source_fps=source_fps)
     if backend == "npy":
-        return NpyDecoder(device, clip_length, height, width, dtype)
+        return NpyDecoder(device, clip_length, height, width, dtype, source_fps=source_fps)
     if backend in ("rocdecode", "nvvl"):
         raise RuntimeError("decoder backend %r is not available on this system "
                            "(no rocDecode/VCN library installed); use 'synthetic', "

@@ -53,7 +53,7 @@ from .engine import (GraphedEngine, R2P1DEngine, boundary_channels_p, boundary_s
 from .network import (DEFAULT_CLIP_LENGTH, LAYER_INPUT_CTHW, R2Plus1DLayerWrapper,
                       check_clip_length, init_random_, load_reference_state_dict,
                       normalize_layer_sizes)
-from .sampler import R2P1DSampler
+from .sampler import PLACEMENTS, R2P1DSampler, check_frame_step, clip_span, parse_rate, step_of
 
 DEFAULT_MAX_CLIPS = 15
 CLIP_SHAPE = (8, 112, 112)
@@ -427,7 +427,8 @@ class R2P1DRunner(RunnerModel):
                     write_sample(self._check_dir, tc.id, "runner", src[0], src[1],
                                  y[off:off + n].float().cpu().numpy(), self.bn_mode,
                                  str(self.dtype), call_rows=call_rows,
-                                 clip_length=self.clip_length)
+                                 clip_length=self.clip_length,
+                                 step=tc.extra.get("clip_step", (1, 1)))
             off += n
 
     def __call__(self, tensors, non_tensors, time_card):
@@ -529,7 +530,18 @@ class R2P1DLoader(RunnerModel):
     (``DirectoryLabels``: ``<name>``'s position among ``root``'s sorted
     sub-directories, or its line in ``class_names=FILE``) travels in
     ``time_card.extra["label"]`` to the aggregator, which counts top-1 / top-k
-    hits by it; synthetic paths get none."""
+    hits by it; synthetic paths get none.
+
+    ``frame_step`` (an integer >= 1) or ``fps`` (a positive number or
+    ``"n:d"``; not both) sets the step ``(p, q)`` clips are taken at
+    (``sampler.clip_frames``): every ``frame_step``-th frame, or the exact
+    ``source_fps / fps`` of each file, whose rate the decoder knows
+    (``source_fps_of``: a Y4M header's ``F`` field, else the decoder's
+    ``source_fps`` argument; a file without one raises). The sampler fits
+    clips by the span they cover, every ``decode`` gets the step, and a tagged
+    request carries it in ``time_card.extra["clip_step"]`` when it is not
+    ``(1, 1)``. ``placement="uniform"`` centres the clips instead of drawing
+    their offset (``R2P1DSampler``)."""
 
     # decode kernels are tiny and gate the consumers: run them on a
     # high-priority HIP stream so they do not queue behind the conv kernels
@@ -539,8 +551,19 @@ class R2P1DLoader(RunnerModel):
                  decoder="synthetic", seed=None, max_clips=DEFAULT_MAX_CLIPS,
                  warmup=3, dtype=None, decoder_args=None,
                  clip_length=DEFAULT_CLIP_LENGTH, crop=None, filter=None, labels=None,
-                 class_names=None, **unused):
+                 class_names=None, frame_step=1, fps=None, placement="random", **unused):
         super().__init__(device)
+        try:
+            self.frame_step = check_frame_step(frame_step)
+            self.fps = parse_rate(fps, "fps")
+            if self.fps is not None and self.frame_step != 1:
+                raise ValueError("frame_step = %r and fps = %r: give one of them"
+                                 % (frame_step, fps))
+            if placement not in PLACEMENTS:
+                raise ValueError("placement = %r, expected one of %s"
+                                 % (placement, PLACEMENTS))
+        except ValueError as err:
+            raise ValueError("R2P1DLoader: %s" % err)
         if labels not in (None, "dir"):
             raise ValueError("R2P1DLoader: labels = %r, expected None or \"dir\"" % (labels,))
         if class_names is not None and labels is None:
@@ -550,7 +573,8 @@ class R2P1DLoader(RunnerModel):
         self.clip_length = check_clip_length(clip_length)
         self.sampler = R2P1DSampler(clip_length=self.clip_length,
                                     num_clips_population=num_clips_population,
-                                    num_clips_weights=num_clips_weights, seed=seed)
+                                    num_clips_weights=num_clips_weights, seed=seed,
+                                    placement=placement)
         self.dtype = _dtype(dtype)
         self.decoder = make_decoder(decoder, device, *clip_shape(self.clip_length),
                                     dtype=self.dtype,
@@ -565,11 +589,29 @@ class R2P1DLoader(RunnerModel):
         if device.type == "cuda":
             torch.cuda.current_stream(device).synchronize()
 
-    def _sample(self, path: str, time_card=None):
-        """(video id, clip start frames) of ``path``; tags sampled requests
-        with what a numerics check needs to decode the same clips again."""
+    def _step_of(self, vid: int, path: str):
+        """The step (p, q) the clips of a probed file are taken at."""
+        if self.fps is None:
+            return self.frame_step, 1
+        source = self.decoder.source_fps_of(vid)
+        if source is None:
+            raise ValueError("%s: fps = %s needs the file's frame rate, and it has none (a Y4M "
+                             "header's field 'F', or the decoder argument 'source_fps')"
+                             % (path, self.fps))
+        return step_of(fps=self.fps, source_fps=source)
+
+    def place(self, path: str):
+        """(video id, clip start frames, step) of ``path``: the probe, the
+        file's step and one draw of the sampler for clips of that span."""
         vid, length = self.decoder.probe(path)
-        starts = (self.sampler.sample(length) or [])[:self.max_clips // self.views]
+        step = self._step_of(vid, path)
+        starts = self.sampler.sample(length, span=clip_span(self.clip_length, step))
+        return vid, (starts or [])[:self.max_clips // self.views], step
+
+    def _sample(self, path: str, time_card=None):
+        """(video id, clip start frames, step) of ``path``; tags sampled requests
+        with what a numerics check needs to decode the same clips again."""
+        vid, starts, step = self.place(path)
         if time_card is not None and self.labels is not None:
             label = self.labels.label(path)
             if label is not None:
@@ -580,12 +622,14 @@ class R2P1DLoader(RunnerModel):
             # len(starts) == logits rows
             time_card.extra["clip_src"] = (int(vid), [int(s) for s in
                                                       expand_views(starts, self.views)[0]])
-        return vid, starts
+            if step != (1, 1):
+                time_card.extra["clip_step"] = step
+        return vid, starts, step
 
     def load(self, path: str, out: Optional[torch.Tensor] = None, time_card=None):
-        vid, starts = self._sample(path, time_card)
+        vid, starts, step = self._sample(path, time_card)
         return self.decoder.decode(vid, starts, out=None if out is None else
-                                   out[:len(starts) * self.views])
+                                   out[:len(starts) * self.views], step=step)
 
     def __call__(self, tensors, non_tensors, time_card):
         frames = self.load(non_tensors, time_card=time_card)
@@ -607,7 +651,7 @@ class R2P1DLoader(RunnerModel):
         SURVEY.md K31). The synthetic decoder renders a clip from (video,
         start frame) only, so the segments equal the split of one decode."""
         from ...control import segment_bounds
-        vid, starts = self._sample(non_tensors, time_card)
+        vid, starts, step = self._sample(non_tensors, time_card)
         if self.views > 1:      # the rows are split, not the clips: a segment names its views
             row_starts, row_views = expand_views(starts, self.views)
         rows = []
@@ -615,9 +659,9 @@ class R2P1DLoader(RunnerModel):
             a, b = segment_bounds(len(starts) * self.views, len(outs), k)
             if b > a and self.views > 1:
                 self.decoder.decode(vid, row_starts[a:b], out=out[0][:b - a],
-                                    views=row_views[a:b])
+                                    views=row_views[a:b], step=step)
             elif b > a:
-                self.decoder.decode(vid, starts[a:b], out=out[0][:b - a])
+                self.decoder.decode(vid, starts[a:b], out=out[0][:b - a], step=step)
             rows.append(b - a)
         time_card.num_clips = len(starts) * self.views
         return rows, None, time_card
@@ -647,13 +691,15 @@ class R2P1DSingleStep(RunnerModel):
                  decoder="synthetic", seed=None, model_seed=0, backend="auto",
                  bn_mode=None, ckpt_path=None, max_clips=DEFAULT_MAX_CLIPS, warmup=3,
                  use_graphs=True, autotune=True, dtype=None, decoder_args=None,
-                 clip_length=DEFAULT_CLIP_LENGTH, crop=None, filter=None, **unused):
+                 clip_length=DEFAULT_CLIP_LENGTH, crop=None, filter=None, frame_step=1,
+                 fps=None, placement="random", **unused):
         super().__init__(device)
         clip_length = check_clip_length(clip_length)
         self.loader = R2P1DLoader(device, num_clips_population, num_clips_weights,
                                   decoder=decoder, seed=seed, max_clips=max_clips,
                                   warmup=warmup, dtype=dtype, decoder_args=decoder_args,
-                                  clip_length=clip_length, crop=crop, filter=filter)
+                                  clip_length=clip_length, crop=crop, filter=filter,
+                                  frame_step=frame_step, fps=fps, placement=placement)
         self.runner = R2P1DRunner(device, 1, 5, num_classes,
                                   layer_sizes=layer_sizes, depth=depth, backend=backend,
                                   bn_mode=bn_mode, seed=model_seed, ckpt_path=ckpt_path,
@@ -675,14 +721,12 @@ class R2P1DSingleStep(RunnerModel):
         eng = self.runner.engine
         if isinstance(eng, GraphedEngine) and self.runner.device.type == "cuda":
             # decode straight into the bucket graph's input buffer
-            vid, length = self.loader.decoder.probe(non_tensors)
-            views = self.loader.views
-            starts = (self.loader.sampler.sample(length) or [])[:self.loader.max_clips // views]
-            nrows = len(starts) * views
+            vid, starts, step = self.loader.place(non_tensors)
+            nrows = len(starts) * self.loader.views
             time_card.num_clips = nrows
             if starts:
                 static_in, _ = eng.input_buffer(nrows)
-                self.loader.decoder.decode(vid, starts, out=static_in[:nrows])
+                self.loader.decoder.decode(vid, starts, out=static_in[:nrows], step=step)
                 y = eng.replay(nrows)
                 if eng.range_guard is not None:
                     self.runner._guard_calls.append((eng, y))
@@ -885,7 +929,8 @@ class R2P1DAggregator(RunnerModel):
                 from ...numerics import write_sample
                 self._checked += 1
                 write_sample(self._check_dir, tc.id, "aggregate", src[0], src[1], total,
-                             segments=self.aggregate, clip_length=self.clip_length)
+                             segments=self.aggregate, clip_length=self.clip_length,
+                             step=got[0].extra.get("clip_step", (1, 1)))
             done_cards.append(TimeCard.merge(got))
             outs.append(int(total.argmax()))
             if self._tracks(got[0]):

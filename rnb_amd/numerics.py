@@ -4,7 +4,7 @@ fp32 ``nn.Module`` and compare.
 A run samples videos when ``RNB_CHECK_DIR`` is set in the launcher's
 environment: the loader tags every ``RNB_CHECK_EVERY``-th video and every
 ``RNB_CHECK_EVERY_LARGE``-th 15-clip video with its decode source (video id,
-clip start frames), a final-step ``R2P1DRunner`` writes the per-clip logits of
+clip start frames, and the frame step when it is not 1), a final-step ``R2P1DRunner`` writes the per-clip logits of
 tagged whole videos, and a final ``R2P1DAggregator`` writes the re-joined
 (summed) logits of tagged segmented videos. Samples are kept per stratum (at
 most ``RNB_CHECK_MAX`` per stratum and process): ``large`` (15-clip videos),
@@ -43,14 +43,16 @@ def stratum_of(kind: str, clips: int, call_rows: int, large_clips: int = 15) -> 
 
 def write_sample(check_dir: str, card_id: int, kind: str, vid: int, starts, logits,
                  bn_mode: Optional[str] = None, dtype: Optional[str] = None,
-                 segments: int = 1, call_rows: int = 0, clip_length: int = 8) -> None:
+                 segments: int = 1, call_rows: int = 0, clip_length: int = 8,
+                 step=(1, 1)) -> None:
     starts = np.asarray(starts, dtype=np.int64)
     stratum = stratum_of(kind, len(starts), int(call_rows))
     path = os.path.join(check_dir, "%s_v%d_p%d.npz" % (kind, card_id, os.getpid()))
     np.savez(path, kind=kind, vid=int(vid), starts=starts,
              logits=np.asarray(logits, dtype=np.float32), bn_mode=str(bn_mode),
              dtype=str(dtype), segments=int(segments), call_rows=int(call_rows),
-             stratum=stratum, clip_length=int(clip_length))
+             stratum=stratum, clip_length=int(clip_length),
+             step=np.asarray([int(step[0]), int(step[1])], dtype=np.int64))
 
 
 def recheck(check_dir: str, depth: int, device=None, seed: int = 0,
@@ -87,7 +89,9 @@ def recheck(check_dir: str, depth: int, device=None, seed: int = 0,
     with torch.no_grad():
         for smp in samples:
             starts = [int(v) for v in smp["starts"]]
-            x = dec.decode(int(smp["vid"]), starts)
+            # samples written before clips had a step carry none: (1, 1)
+            step = tuple(int(v) for v in smp["step"]) if "step" in smp else (1, 1)
+            x = dec.decode(int(smp["vid"]), starts, step=step)
             got = smp["logits"]
             kind = str(smp["kind"])
             name = str(smp["stratum"]) if "stratum" in smp else \

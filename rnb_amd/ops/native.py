@@ -201,6 +201,10 @@ class Kernels:
                                           ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_void_p]
+        for fn in (lib.rnb_clipgen_video_step, lib.rnb_nv12gen_video_step):
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         lib.rnb_nv12gen.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_void_p]
@@ -883,6 +887,18 @@ class Kernels:
         arr = (ctypes.c_int * max(1, len(starts)))(*starts)
         _check(self.lib.rnb_nv12gen_video(out_ptr, int(vid), arr, len(starts), F, H, W,
                                           stream), "nv12gen_video")
+
+    def clipgen_video_step(self, out_ptr, vid, starts, F, H, W, step, stream):
+        arr = (ctypes.c_int * max(1, len(starts)))(*starts)
+        _check(self.lib.rnb_clipgen_video_step(out_ptr, int(vid), arr, len(starts), F, H, W,
+                                               int(step[0]), int(step[1]), stream),
+               "clipgen_video_step")
+
+    def nv12gen_video_step(self, out_ptr, vid, starts, F, H, W, step, stream):
+        arr = (ctypes.c_int * max(1, len(starts)))(*starts)
+        _check(self.lib.rnb_nv12gen_video_step(out_ptr, int(vid), arr, len(starts), F, H, W,
+                                               int(step[0]), int(step[1]), stream),
+               "nv12gen_video_step")
 
     def nv12gen(self, out_ptr, vids_ptr, starts_ptr, nclips, F, H, W, stream):
         _check(self.lib.rnb_nv12gen(out_ptr, vids_ptr, starts_ptr, nclips, F, H, W, stream),

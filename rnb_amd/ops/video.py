@@ -63,16 +63,33 @@ def clipgen_u8(vids: torch.Tensor, starts: torch.Tensor, F: int, H: int, W: int,
     return res.contiguous()
 
 
+def _clip_frame_offsets(F: int, step) -> torch.Tensor:
+    """``(f * p) // q`` for the F frames of a clip (``sampler.clip_frames``)."""
+    p, q = int(step[0]), int(step[1])
+    if p < 1 or q < 1:
+        raise ValueError("step (p, q) must be positive integers, got %r" % (step,))
+    return torch.tensor([(f * p) // q for f in range(F)], dtype=torch.int64)
+
+
 def clipgen_video(vid: int, starts, F: int, H: int, W: int, device,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, step=(1, 1)) -> torch.Tensor:
     """One video's synthetic clips (uint8 [n, F, H, W, 3]); the start frames
     travel as kernel arguments, so nothing is uploaded and the host never
-    waits (the per-video form of ``clipgen_u8``; same pixels)."""
+    waits (the per-video form of ``clipgen_u8``; same pixels). ``step`` =
+    ``(p, q)``: frame ``f`` of a clip is frame ``start + (f * p) // q`` of the
+    video (``sampler.clip_frames``)."""
     n = len(starts)
+    stepped = tuple(step) != (1, 1)
     if device.type == "cuda":
         from .native import kernels
         if out is None:
             out = torch.empty((n, F, H, W, 3), dtype=torch.uint8, device=device)
+        if stepped:          # the device-array form has no step: 32 clips per launch
+            stream = torch.cuda.current_stream(device).cuda_stream
+            for i in range(0, n, 32):
+                kernels().clipgen_video_step(out[i:].data_ptr(), vid, list(starts[i:i + 32]),
+                                             F, H, W, step, stream)
+            return out
         if n > 32:
             return clipgen_u8(torch.full((n,), vid, dtype=torch.int32, device=device),
                               torch.as_tensor(list(starts), dtype=torch.int32).to(device),
@@ -80,6 +97,16 @@ def clipgen_video(vid: int, starts, F: int, H: int, W: int, device,
         kernels().clipgen_video(out.data_ptr(), vid, list(starts), F, H, W,
                                 torch.cuda.current_stream(device).cuda_stream)
         return out
+    if stepped:
+        # every frame as a one-frame clip at its own source frame: same pixels
+        fr = (torch.as_tensor(list(starts), dtype=torch.int64).view(n, 1)
+              + _clip_frame_offsets(F, step).view(1, F)).reshape(-1)
+        res = clipgen_u8(torch.full((n * F,), vid, dtype=torch.int32), fr, 1, H, W)
+        res = res.view(n, F, H, W, 3)
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
     return clipgen_u8(torch.full((n,), vid, dtype=torch.int32),
                       torch.as_tensor(list(starts), dtype=torch.int32), F, H, W, out=out)
 
@@ -95,19 +122,28 @@ def nv12_frame_bytes(W: int, H: int) -> int:
 
 
 def nv12gen(vids, starts, F: int, H: int, W: int, device,
-            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+            out: Optional[torch.Tensor] = None, step=(1, 1)) -> torch.Tensor:
     """Synthetic decoder surfaces: uint8 [n*F, H*3/2, W] NV12 frames (Y rows,
     then interleaved UV rows), deterministic per (video, frame). ``vids`` may
-    be one id (start frames then go in kernel arguments) or a per-clip array."""
+    be one id (start frames then go in kernel arguments) or a per-clip array.
+    ``step`` = ``(p, q)`` (one id only): frame ``f`` of a clip is frame
+    ``start + (f * p) // q`` of the video (``sampler.clip_frames``)."""
     single = isinstance(vids, int)
     n = len(starts)
     shape = (n * F, H * 3 // 2, W)
+    stepped = tuple(step) != (1, 1)
+    if stepped and not single:
+        raise ValueError("nv12gen: a step goes with one video id, not a per-clip array")
     if device.type == "cuda":
         from .native import kernels
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=device)
         stream = torch.cuda.current_stream(device).cuda_stream
-        if single and n <= 32:
+        if stepped:          # the device-array form has no step: 32 clips per launch
+            for i in range(0, n, 32):
+                kernels().nv12gen_video_step(out[i * F:].data_ptr(), vids,
+                                             list(starts[i:i + 32]), F, H, W, step, stream)
+        elif single and n <= 32:
             kernels().nv12gen_video(out.data_ptr(), vids, list(starts), F, H, W, stream)
         else:
             v = torch.full((n,), vids, dtype=torch.int32, device=device) if single else \
@@ -122,7 +158,7 @@ def nv12gen(vids, starts, F: int, H: int, W: int, device,
         torch.as_tensor(vids, dtype=torch.int64).view(-1)
     st = torch.as_tensor(list(starts) if not isinstance(starts, torch.Tensor) else starts,
                          dtype=torch.int64).view(-1)
-    fr = (st.view(n, 1) + torch.arange(F).view(1, F)).reshape(-1)           # [n*F]
+    fr = (st.view(n, 1) + _clip_frame_offsets(F, step).view(1, F)).reshape(-1)   # [n*F]
     vv = v.view(n, 1).expand(n, F).reshape(-1)
     ypix = torch.arange(H * W, dtype=torch.int64).view(1, -1)
     y = _pixel_hash_torch(vv.view(-1, 1), fr.view(-1, 1), ypix, torch.zeros(1, dtype=torch.int64))

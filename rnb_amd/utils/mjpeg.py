@@ -321,14 +321,15 @@ def _need_native(what: str):
 
 def pack_scans(data, offsets, lengths, out: np.ndarray, width: int = 0, height: int = 0,
                name: str = "<mjpeg>", frame0: int = 0,
-               sampling: str = "420") -> Tuple[int, np.ndarray]:
+               sampling: str = "420", frames=None) -> Tuple[int, np.ndarray]:
     """Pack the scans of the frames at ``offsets`` / ``lengths`` of ``data``
     into scan records in the flat, 16-byte aligned uint8 array ``out``
     (``rnb_jpeg_pack_scans``: header parse, restart markers located, counted and
     checked, no Huffman work). ``width`` / ``height``: the size every frame must
     have (0: the first frame's). Returns (bytes written, int64 offsets
     [n + 1] of the records in ``out``). A refusal raises ``JpegError`` naming
-    ``name``, the frame (``frame0`` + its index) and the field. ``sampling``:
+    ``name``, the frame (``frame0`` + its index, or ``frames[index]`` where the
+    frames are not consecutive) and the field. ``sampling``:
     the stream's; it goes into the record's fourth header word, and a frame of
     another sampling is refused."""
     sampling_factors(sampling, "pack_scans")
@@ -338,7 +339,8 @@ def pack_scans(data, offsets, lengths, out: np.ndarray, width: int = 0, height: 
     if got < 0:
         field = lib.error_name(got)
         raise JpegError(field, "%s: frame %d is not read (field '%s': %s)"
-                        % (name, frame0 + extra, field, _REASONS.get(field, field)))
+                        % (name, frame0 + extra if frames is None else int(frames[extra]),
+                           field, _REASONS.get(field, field)))
     return got, extra
 
 

@@ -40,6 +40,11 @@
     with ``threads=4`` and with ``entropy="gpu", subseq_bytes=48`` on three
     antialiased views; the values alternate within every round.
 
+    ``--frame-step N`` or ``--fps R`` reports ``MjpegDecoder.decode(step=)``
+    instead: the request's clips at every N-th frame, or at ``R`` frames per
+    second of a 30 fps stream, with ``threads=4`` and with ``entropy="gpu"``
+    (host and sustained rows; ``--frame-step 1`` is consecutive frames).
+
     python scripts/mjpeg_decode_bench.py --out profiles/mjpeg_decode.txt
     python scripts/mjpeg_decode_bench.py --entropy gpu --restart-interval 22
     python scripts/mjpeg_decode_bench.py --entropy gpu --subseq-bytes 0,64,128,256,512
@@ -214,17 +219,18 @@ def kernels(dev, dtype, encoded, reps, rounds, lines, filter="bilinear"):
                  % (rec.numel(), n, rb, surf.numel(), n * W * H * 3 // 2))
 
 
-def decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines, label, **kw):
+def decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines, label, step=(1, 1),
+                 **kw):
     """Host time of decode, and the sustained rate with one final synchronise."""
     dec = MjpegDecoder(dev, dtype=dtype, **kw)
     vid, _ = dec.probe(path)
     for _ in range(5):
-        dec.decode(vid, starts, out=out)
+        dec.decode(vid, starts, out=out, step=step)
     torch.cuda.synchronize()
     call, total = [], []
     for _ in range(reqs):
         t0 = time.perf_counter()
-        dec.decode(vid, starts, out=out)
+        dec.decode(vid, starts, out=out, step=step)
         t1 = time.perf_counter()
         torch.cuda.synchronize()
         t2 = time.perf_counter()
@@ -241,7 +247,7 @@ def decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines, label, *
         before = dict(dec.stats)
         t0 = time.perf_counter()
         for _ in range(sustained):
-            dec.decode(vid, starts, out=out)
+            dec.decode(vid, starts, out=out, step=step)
         torch.cuda.synchronize()
         rates.append(sustained / (time.perf_counter() - t0))
     dec.drain()
@@ -287,6 +293,27 @@ def host(dev, dtype, encoded, reqs, lines, sustained=60, entropy="host", restart
                 decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines,
                              "entropy=gpu" if sub is None else "gpu S=%d" % sub,
                              entropy="gpu", subseq_bytes=sub, filter=filter)
+
+
+def step_host(dev, dtype, encoded, reqs, lines, sustained, filt, frame_step, fps):
+    """``--frame-step`` / ``--fps``: ``MjpegDecoder.decode(step=)`` on a 30 fps
+    stream, host entropy decode on 4 threads and the GPU's."""
+    from rnb_amd.models.r2p1d.sampler import clip_span, step_of
+    step = step_of(frame_step or 1, fps, (30, 1))
+    span = clip_span(F, step)
+    starts = [max(20, span) * c for c in range(CLIPS)]
+    frames = starts[-1] + span + 4
+    C = 4 if dtype == torch.float32 else 8
+    out = torch.empty((CLIPS, F, 112, 112, C), dtype=dtype, device=dev)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "v.mjpeg")
+        with open(path, "wb") as fp:
+            for i in range(frames):
+                fp.write(encoded[i % DISTINCT][0])
+        for label, kw in (("threads=4", dict(threads=4)), ("entropy=gpu", dict(entropy="gpu"))):
+            decoder_rows(dev, dtype, path, starts, out, reqs, sustained, lines,
+                         "%s step %d/%d" % (label, step[0], step[1]), step=step, filter=filt,
+                         source_fps=30, **kw)
 
 
 def views_host(dev, dtype, encoded, reqs, lines, sustained, short_side, nviews):
@@ -404,6 +431,10 @@ def main():
     ap.add_argument("--size", default=None, help="WxH of the synthetic frames (default 340x256)")
     ap.add_argument("--distinct", type=int, default=DISTINCT,
                     help="frames encoded; the stream repeats them")
+    ap.add_argument("--frame-step", type=int, default=None,
+                    help="report MjpegDecoder.decode(step=(N, 1)) instead (1: consecutive frames)")
+    ap.add_argument("--fps", default=None,
+                    help="report MjpegDecoder.decode at this rate of a 30 fps stream instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     SAMPLING = args.sampling
@@ -428,6 +459,19 @@ def main():
                     % (":".join(SAMPLING), W, H, torch.cuda.get_device_name(0)))
         reduce_report(dev, encoded, reduces, args.reps, args.rounds, args.requests,
                       args.sustained, lines)
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        if args.out:
+            with open(args.out, "w") as fp:
+                fp.write(text)
+        return
+    if args.frame_step is not None or args.fps is not None:
+        lines[0] = ("mjpeg decode path, sampling %s, frame step %s, fps %s, per 15-clip request "
+                    "at %dx%d -> 112x112 (%s)"
+                    % (":".join(SAMPLING), args.frame_step, args.fps, W, H,
+                       torch.cuda.get_device_name(0)))
+        step_host(dev, torch.float32, encoded, args.requests, lines, args.sustained, args.filter,
+                  args.frame_step, args.fps)
         text = "\n".join(lines) + "\n"
         print(text, end="")
         if args.out:

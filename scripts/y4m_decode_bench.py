@@ -24,6 +24,12 @@ the same rows with that box given as a per-row list ("boxed") and at
 ``clips * V`` rows with the views' boxes, then ``Y4mDecoder.decode`` (host call,
 call + sync, sustained requests/s, uploaded bytes per request) for 1 view and
 for ``V``.
+
+``--frame-step N`` or ``--fps R`` times ``Y4mDecoder.decode(step=)`` instead:
+the clips of the request at every N-th frame, or at ``R`` frames per second of
+a 30 fps file (host call, call + sync, sustained requests/s), and next to it
+the staging copies alone, one span per clip against F frames per clip. ``--size``,
+``--clips`` and ``--filter`` apply; ``--frame-step 1`` is the contiguous path.
 """
 import argparse
 import os
@@ -261,6 +267,79 @@ def views_host(dev, dtype, reqs, lines, w, h, clips, short_side, nviews):
                                 statistics.median(total), rate, clips * F * hdr.frame_stride))
 
 
+def step_host(dev, dtype, reqs, lines, w, h, clips, filt, frame_step, fps):
+    """``Y4mDecoder.decode(step=)`` on ``clips`` clips 20 * step frames apart in
+    a 30 fps ``w`` x ``h`` file (warm page cache), and its staging copies alone."""
+    from rnb_amd.models.r2p1d.sampler import clip_frames, clip_span, step_of
+    rng = np.random.default_rng(1)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "v.y4m")
+        step = step_of(frame_step or 1, fps, (30, 1))
+        span = clip_span(F, step)
+        starts = [max(20, span) * c for c in range(clips)]
+        frames = starts[-1] + span + 4
+        y4m.write_y4m(path, [(rng.integers(0, 256, (h, w), dtype=np.uint8),
+                              rng.integers(0, 256, chroma_shape(w, h), dtype=np.uint8),
+                              rng.integers(0, 256, chroma_shape(w, h), dtype=np.uint8))
+                             for _ in range(frames)], fps=(30, 1), sampling=SAMPLING)
+        with open(path, "rb") as fp:                       # warm the page cache
+            while fp.read(1 << 24):
+                pass
+        C = 4 if dtype == torch.float32 else 8
+        out = torch.empty((clips, F, 112, 112, C), dtype=dtype, device=dev)
+        dec = Y4mDecoder(dev, dtype=dtype, filter=filt)
+        vid, _ = dec.probe(path)
+        assert dec.source_fps_of(vid) == (30, 1)
+        for _ in range(5):
+            dec.decode(vid, starts, out=out, step=step)
+        torch.cuda.synchronize()
+        call, total = [], []
+        for _ in range(reqs):
+            t0 = time.perf_counter()
+            dec.decode(vid, starts, out=out, step=step)
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            call.append((t1 - t0) * 1e3)
+            total.append((t2 - t0) * 1e3)
+        t0 = time.perf_counter()
+        for _ in range(reqs):
+            dec.decode(vid, starts, out=out, step=step)
+        torch.cuda.synchronize()
+        rate = reqs / (time.perf_counter() - t0)
+        hdr = dec._videos[vid][1]
+        lines.append("Y4mDecoder.decode %s, step %d/%d (span %d) %s: host call median %.3f ms "
+                     "(min %.3f, max %.3f), call + sync median %.3f ms, sustained %.0f requests/s, "
+                     "%d requests of %d clips, %d bytes uploaded per request"
+                     % (filt, step[0], step[1], span, str(dtype).split(".")[1],
+                        statistics.median(call), min(call), max(call), statistics.median(total),
+                        rate, reqs, clips, clips * F * hdr.frame_stride))
+        # the staging copies alone (no upload, no launch): where a step's host time goes
+        _, data = dec._map(vid, path)
+        fs = hdr.frame_stride
+        pinned = torch.empty(clips * F * fs, dtype=torch.uint8, pin_memory=True).numpy()
+
+        def one_span():
+            for i, s in enumerate(starts):
+                a = hdr.frame_offset(s)
+                np.copyto(pinned[i * F * fs:(i + 1) * F * fs], data[a:a + F * fs])
+
+        def per_frame():
+            for i, s in enumerate(starts):
+                dst = pinned[i * F * fs:(i + 1) * F * fs].reshape(F, fs)
+                for f, fr in enumerate(clip_frames(s, F, step)):
+                    a = hdr.frame_offset(fr)
+                    np.copyto(dst[f], data[a:a + fs])
+        for what, fn in (("one span per clip", one_span), ("F frames per clip", per_frame)):
+            t = []
+            for _ in range(reqs + 5):
+                t0 = time.perf_counter()
+                fn()
+                t.append((time.perf_counter() - t0) * 1e3)
+            lines.append("staging copies alone, %s: median %.3f ms (min %.3f) per request of %d "
+                         "bytes" % (what, statistics.median(t[5:]), min(t[5:]), clips * F * fs))
+
+
 def host(dev, dtype, reqs, lines):
     rng = np.random.default_rng(1)
     frames = 300
@@ -314,6 +393,10 @@ def main():
     ap.add_argument("--short-side", type=float, default=None,
                     help="time crop={'short_side': S, 'views': V} (both filters) instead")
     ap.add_argument("--views", type=int, choices=(1, 3), default=1, help="with --short-side")
+    ap.add_argument("--frame-step", type=int, default=None,
+                    help="time Y4mDecoder.decode(step=(N, 1)) instead (1: the contiguous path)")
+    ap.add_argument("--fps", default=None,
+                    help="time Y4mDecoder.decode at this rate of a 30 fps file instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     global SAMPLING
@@ -321,7 +404,14 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("y4m_decode_bench: needs a GPU")
     dev = torch.device("cuda:0")
-    if args.short_side is not None:
+    if args.frame_step is not None or args.fps is not None:
+        w, h = (int(x) for x in args.size.lower().split("x"))
+        lines = ["y4m decode path, sampling %s, frame step %s, fps %s, per %d-clip request at "
+                 "%dx%d -> 112x112 (%s)" % (":".join(SAMPLING), args.frame_step, args.fps,
+                                            args.clips, w, h, torch.cuda.get_device_name(0))]
+        step_host(dev, torch.float32, args.requests, lines, w, h, args.clips, args.filter,
+                  args.frame_step, args.fps)
+    elif args.short_side is not None:
         w, h = (int(x) for x in args.size.lower().split("x"))
         lines = ["y4m decode path, sampling %s, short side %g, %d view(s), per %d-clip request at "
                  "%dx%d -> 112x112 (%s)" % (":".join(SAMPLING), args.short_side, args.views,
