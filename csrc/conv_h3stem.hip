@@ -164,17 +164,37 @@ struct ConvH3StemConfig {
 #define H3STEMCFG(NW, TP, TC, PATCH)                                                  \
   {NW, TP, TC, PATCH, conv_h3stem_kernel<NW, TP, TC, PATCH, false>,                   \
    conv_h3stem_kernel<NW, TP, TC, PATCH, true>}
-// LDS = PATCH x 16 B + 2 x TC x 2 KB; two blocks per CU
+// LDS = PATCH x 16 B + 2 x TC x 2 KB; two blocks per CU. The TC 3 variants
+// (48 channels per block) serve stems of at most 48 output channels -- the
+// torchvision layout's 3 -> 45 (48) -- with half the MFMAs, accumulators and
+// weight LDS of a 96-channel block; their 13-tile variant spends the freed
+// accumulators on pixels (14 rows of 56: a 56-row frame in 4 whole bands).
 static const ConvH3StemConfig kH3StemConfigs[] = {
     H3STEMCFG(4, 4, 6, 1536),   // 256 px (4 rows of 56) x 96 ch: the 3 -> 83 (96) stem
     H3STEMCFG(4, 2, 6, 1088),   // 128 px (2 rows of 56) x 96 ch
     H3STEMCFG(4, 7, 6, 2496),   // 448 px (8 rows of 56) x 96 ch
+    H3STEMCFG(4, 4, 3, 1536),   // 256 px x 48 ch: the 3 -> 45 (48) stem
+    H3STEMCFG(4, 2, 3, 1088),   // 128 px x 48 ch
+    H3STEMCFG(4, 7, 3, 2496),   // 448 px x 48 ch
+    H3STEMCFG(4, 13, 3, 3904),  // 832 px (14 rows of 56) x 48 ch
 };
 
 extern "C" {
 
 int rnb_conv_h3stem_num_variants() {
   return (int)(sizeof(kH3StemConfigs) / sizeof(kH3StemConfigs[0]));
+}
+
+// output channels per block of a variant (0: no such variant)
+int rnb_conv_h3stem_ctile(int variant) {
+  if (variant < 0 || variant >= rnb_conv_h3stem_num_variants()) return 0;
+  return kH3StemConfigs[variant].tc * 16;
+}
+
+// output pixels per block of a variant (0: no such variant)
+int rnb_conv_h3stem_pixels(int variant) {
+  if (variant < 0 || variant >= rnb_conv_h3stem_num_variants()) return 0;
+  return kH3StemConfigs[variant].nw * kH3StemConfigs[variant].tp * 16;
 }
 
 // output rows per band of a variant for an Ho x Wo output (0: cannot run it)

@@ -18,7 +18,10 @@ rnb_amd keeps every key and rule of the reference and adds a few optional keys:
 * step/group ``transport``: ``"auto"`` (default), ``"ipc"``, ``"host"`` or
   ``"rccl"`` -- how tensors cross this step's output edges (parallel/);
 * step ``slot_dtype``: override the slot dtype advertised by the model;
-* top-level ``defaults``: kwargs merged into every step (e.g. ``"depth": 34``).
+* top-level ``defaults``: kwargs merged into every step (e.g. ``"depth": 34``);
+* ``arch`` (``"reference"`` or ``"torchvision"``), ``midplanes`` (``"block"`` or
+  ``"conv"``) and ``bn_eps``, in ``defaults`` or per step / queue group: the
+  network layout of the model steps (models/r2p1d/network.py).
 
 Validation errors raise ``ConfigError`` instead of calling ``sys.exit()`` so
 that tests can exercise them; the CLI turns them into a clean message.
@@ -207,6 +210,7 @@ def parse_pipeline(config: Dict[str, Any]) -> PipelineSpec:
             gkw = dict(step_kwargs)
             gkw.update({k: v for k, v in group.items()
                         if k not in RESERVED_KEYWORDS})
+            _check_arch_keys(gkw, "step %d group %d" % (step_idx, gi))
             transport = group.get("transport", step.get("transport", "auto"))
             _require(transport in ("auto", "ipc", "host", "rccl"),
                      "step %d group %d: unknown transport %r"
@@ -238,6 +242,30 @@ def parse_pipeline(config: Dict[str, Any]) -> PipelineSpec:
                         iterator_kwargs=config.get("video_path_iterator_kwargs",
                                                    {}),
                         raw=config)
+
+
+ARCHS = ("reference", "torchvision")
+MIDPLANES_RULES = ("block", "conv")
+
+
+def _check_arch_keys(kwargs: Dict[str, Any], where: str) -> None:
+    """``arch`` / ``midplanes`` / ``bn_eps`` of a step's model kwargs (the
+    values models/r2p1d/network.py takes); the error names the key."""
+    arch = kwargs.get("arch")
+    if arch is not None and (not isinstance(arch, str) or arch not in ARCHS):
+        raise ConfigError("%s: arch must be one of %s, got %r"
+                          % (where, ", ".join(repr(a) for a in ARCHS), arch))
+    mid = kwargs.get("midplanes")
+    if mid is not None and (not isinstance(mid, str) or mid not in MIDPLANES_RULES):
+        raise ConfigError("%s: midplanes must be one of %s, got %r"
+                          % (where, ", ".join(repr(a) for a in MIDPLANES_RULES), mid))
+    eps = kwargs.get("bn_eps")
+    if eps is not None and (isinstance(eps, bool) or not isinstance(eps, (int, float))
+                            or not 0.0 < float(eps) < 1.0):
+        raise ConfigError("%s: bn_eps must be a float in (0, 1), got %r" % (where, eps))
+    if (mid is not None or eps is not None) and arch != "torchvision":
+        raise ConfigError("%s: %s belongs to \"arch\": \"torchvision\", got arch %r"
+                          % (where, "midplanes" if mid is not None else "bn_eps", arch))
 
 
 def _check_clip_lengths(steps: List[StepSpec]) -> None:

@@ -48,7 +48,7 @@ from ...ops.conv_f32 import (F32_ALIGN, WINOT_MIN_T, ConvLayerF32, RangeGuard, f
 from ...ops.video import (Head, IN_CHANNELS_P, ndhwc_to_ncdhw, ncdhw_to_ndhwc,
                           packed_input_shape)
 from .network import (DEFAULT_CLIP_LENGTH, LAYER_CHANNELS, LAYER_INPUT_CTHW,
-                      LAYER_OUTPUT_CTHW, R2Plus1DLayerWrapper, SpatioTemporalConv,
+                      LAYER_OUTPUT_CTHW, TV_STEM_MID, R2Plus1DLayerWrapper, SpatioTemporalConv,
                       check_clip_length, intermediate_channels, layer_geometry)
 
 DEFAULT_BUCKETS = (1, 2, 3, 4, 5, 6, 8, 10, 12, 15, 16, 20, 24, 30, 32, 40, 45, 48,
@@ -113,11 +113,16 @@ BN_MAX_ELEMS = 0x7FFFFFFF * 4
 
 
 def activation_elems_per_clip(start_idx: int, end_idx: int, dtype=torch.float32,
-                              clip_length: int = DEFAULT_CLIP_LENGTH) -> int:
+                              clip_length: int = DEFAULT_CLIP_LENGTH,
+                              arch: str = "reference") -> int:
     """Elements per clip of the largest activation layers [start_idx, end_idx]
     hold: the boundary tensors of the geometry table and each layer's largest
     (2+1)D intermediate (the first spatial conv's output: the layer's input
-    frame count at its output H x W, channels padded as the engine pads them)."""
+    frame count at its output H x W, channels padded as the engine pads them).
+    ``arch="torchvision"``: the stem's intermediate has 45 channels; a block's
+    mid-channel counts are at most the reference rule's (per conv), which
+    bounds both ``midplanes`` rules, and the 1x1x1 shortcut's output has the
+    layer's output shape."""
     inp, out = layer_geometry(clip_length)
     f32 = dtype == torch.float32
     align = F32_ALIGN if f32 else CH_ALIGN
@@ -130,6 +135,8 @@ def activation_elems_per_clip(start_idx: int, end_idx: int, dtype=torch.float32,
         ho, wo = (h // 2, w // 2) if idx != 2 else (h, w)
         kernel = (3, 7, 7) if idx == 1 else (3, 3, 3)
         mids = [intermediate_channels(cin, cout, kernel)]
+        if idx == 1 and arch == "torchvision":
+            mids = [TV_STEM_MID]
         if idx > 1:
             mids.append(intermediate_channels(cout, cout, kernel))
         # fp32 pads a temporal Winograd conv's input to 16 channels (_stconv)
@@ -142,24 +149,24 @@ def activation_elems_per_clip(start_idx: int, end_idx: int, dtype=torch.float32,
 
 
 def max_clips_limit(start_idx: int, end_idx: int, dtype=torch.float32,
-                    clip_length: int = DEFAULT_CLIP_LENGTH) -> int:
+                    clip_length: int = DEFAULT_CLIP_LENGTH, arch: str = "reference") -> int:
     """Largest ``max_clips`` whose calls every kernel of the layer range can
     index. Rows per clip grow with the clip length, so the bound shrinks with
     it. The fp32 conv launches are split by clips (ConvLayerF32.chunk_clips),
     so at fp32 the per-call bound is the BatchNorm kernels' element limit; the
     bf16 conv launchers take a whole call, so at bf16 it is their byte limit."""
-    per = activation_elems_per_clip(start_idx, end_idx, dtype, clip_length)
+    per = activation_elems_per_clip(start_idx, end_idx, dtype, clip_length, arch)
     if dtype == torch.float32:
         return BN_MAX_ELEMS // per
     return CONV_MAX_BYTES // (2 * per)
 
 
 def check_max_clips(max_clips: int, start_idx: int, end_idx: int, dtype=torch.float32,
-                    clip_length: int = DEFAULT_CLIP_LENGTH) -> int:
+                    clip_length: int = DEFAULT_CLIP_LENGTH, arch: str = "reference") -> int:
     """``max_clips`` if calls of that many clips fit the kernels' per-launch
     limits, else ValueError -- raised at construction, so that no launcher
     error surfaces while a graph bucket is captured."""
-    fit = max_clips_limit(start_idx, end_idx, dtype, clip_length)
+    fit = max_clips_limit(start_idx, end_idx, dtype, clip_length, arch)
     if int(max_clips) > fit:
         raise ValueError("max_clips %d is too large at clip_length %d for layers %d..%d (%s): "
                          "the largest activation passes the kernels' per-launch limit; the "
@@ -206,6 +213,8 @@ class R2P1DEngine:
         # conv1 spatial on the pair-packed input (ops/conv.StemConv, bf16 only)
         self.pack_stem = os.environ.get("RNB_STEM_PACK", "1") != "0" and not self.f32
         self.start_idx, self.end_idx = net.start_idx, net.end_idx
+        # "reference" (R2Plus1DLayerWrapper) or "torchvision" (TVVideoResNet)
+        self.arch = getattr(net, "arch", "reference")
         self.num_classes = getattr(net, "num_classes", 400)
         self.ops: List[PlanOp] = []
         self.head: Optional[Head] = None
@@ -216,9 +225,13 @@ class R2P1DEngine:
             self.module = net.to(device)
             self.module.train(bn_mode == "batch")
         else:
-            self._build(net.res2plus1d)
+            if self.arch == "torchvision":
+                self._build_tv(net)
+            else:
+                self._build(net.res2plus1d)
+            self._analyse()
             if self.end_idx == 5:
-                self.head = Head(net.linear, device)
+                self.head = Head(net.fc if self.arch == "torchvision" else net.linear, device)
         # h3 range guard (fp32 hip engines whose convs may pick h3 configs):
         # the launches of this engine write its flag on a non-finite output
         self.range_guard = (RangeGuard() if backend == "hip" and self.f32 and h3_enabled()
@@ -293,25 +306,28 @@ class R2P1DEngine:
         layer.nominal_geom = nominal
         return layer
 
-    def _stconv(self, st: SpatioTemporalConv, src: str, post_bn, relu: bool,
-                res: Optional[str], name: str) -> str:
+    def _stconv(self, sc: torch.nn.Conv3d, bn, tc: torch.nn.Conv3d, src: str, post_bn,
+                relu: bool, res: Optional[str], name: str) -> str:
+        """One (2+1)D conv: spatial conv ``sc`` + ``bn`` + ReLU, then temporal
+        conv ``tc`` + ``post_bn`` (+ residual ``res``) (+ ReLU)."""
         mid = self._name()
         # fp32: a stride-1 3x1x1 temporal conv over >= 4 frames runs as the
-        # temporal Winograd kernel, which takes 16-channel chunks -- store the
-        # mid activation padded to 16 channels (the stem's 83 -> 96; the pad
-        # channels are exact zeros: zero weights and bias, BN gamma/beta 0)
-        tc = st.temporal_conv
-        T = self._thw[src][0]
+        # temporal Winograd kernel, over >= 2 frames as the h3t frame-band
+        # kernel; both take 16-channel chunks, as do the Winograd and h3
+        # kernels' output-channel units of the spatial conv before it -- store
+        # the mid activation padded to 16 channels (the stem's 83 -> 96, the
+        # torchvision layout's 45 -> 48, 230 -> 240, 460 -> 464, 921 -> 928;
+        # the pad channels are exact zeros: zero weights and bias, BN
+        # gamma/beta 0). Every such conv of the reference tree but the stem's
+        # has a multiple of 16 already, and the stem always sees >= 8 frames.
         pad = 0
         if (self.f32 and tuple(tc.kernel_size) == (3, 1, 1) and tuple(tc.stride) == (1, 1, 1)
                 and tuple(tc.padding) == (1, 0, 0) and tc.in_channels % 16
-                and T >= WINOT_MIN_T and os.environ.get("RNB_PAD_MID16", "1") != "0"):
+                and os.environ.get("RNB_PAD_MID16", "1") != "0"):
             pad = (tc.in_channels + 15) // 16 * 16
-        self._append(st.spatial_conv, st.bn, True, None, name + ".spatial", src, mid,
-                     cout_pad=pad)
+        self._append(sc, bn, True, None, name + ".spatial", src, mid, cout_pad=pad)
         dst = self._name()
-        self._append(st.temporal_conv, post_bn, relu, res, name + ".temporal", mid, dst,
-                     cin_pad=pad)
+        self._append(tc, post_bn, relu, res, name + ".temporal", mid, dst, cin_pad=pad)
         sp, tp = self.ops[-2], self.ops[-1]
         if (not self.f32 and sp.bn is None and tp.bn is None
                 and FusedSTConv.eligible(sp.layer, tp.layer)):
@@ -336,25 +352,62 @@ class R2P1DEngine:
 
     def _block(self, blk, src: str, name: str) -> str:
         if blk.downsample:
-            res = self._stconv(blk.downsampleconv, src, blk.downsamplebn, False, None,
-                               name + ".downsample")
+            ds = blk.downsampleconv
+            res = self._stconv(ds.spatial_conv, ds.bn, ds.temporal_conv, src, blk.downsamplebn,
+                               False, None, name + ".downsample")
         else:
             res = src
-        h = self._stconv(blk.conv1, src, blk.bn1, True, None, name + ".conv1")
-        return self._stconv(blk.conv2, h, blk.bn2, True, res, name + ".conv2")
+        c1, c2 = blk.conv1, blk.conv2
+        h = self._stconv(c1.spatial_conv, c1.bn, c1.temporal_conv, src, blk.bn1, True, None,
+                         name + ".conv1")
+        return self._stconv(c2.spatial_conv, c2.bn, c2.temporal_conv, h, blk.bn2, True, res,
+                            name + ".conv2")
+
+    def _block_tv(self, blk, src: str, name: str) -> str:
+        """torchvision ``BasicBlock``: the shortcut is one 1x1x1 stride-(2, 2, 2)
+        conv + BN, whose output is the residual of conv2's temporal conv."""
+        if blk.downsample is not None:
+            res = self._name()
+            self._append(blk.downsample[0], blk.downsample[1], False, None,
+                         name + ".downsample", src, res)
+        else:
+            res = src
+        (c1, bn1), (c2, bn2) = blk.conv1[:2], blk.conv2[:2]
+        h = self._stconv(c1[0], c1[1], c1[3], src, bn1, True, None, name + ".conv1")
+        return self._stconv(c2[0], c2[1], c2[3], h, bn2, True, res, name + ".conv2")
+
+    def _build_tv(self, net):
+        cur = "x"
+        self._thw = {"x": tuple(self.layer_in[self.start_idx][1:])}
+        for idx in range(self.start_idx, self.end_idx + 1):
+            if idx == 1:
+                s = net.stem
+                cur = self._stconv(s[0], s[1], s[3], cur, s[4], True, None, "stem")
+            else:
+                for j, blk in enumerate(getattr(net, "layer%d" % (idx - 1))):
+                    cur = self._block_tv(blk, cur, "layer%d.%d" % (idx - 1, j))
+            if self.layer_out[idx] is not None and self._thw[cur] != tuple(self.layer_out[idx][1:]):
+                raise ValueError("layer %d leaves %s, the boundary table says %s"
+                                 % (idx, self._thw[cur], tuple(self.layer_out[idx][1:])))
+        self.out_name = cur
 
     def _build(self, body):
         cur = "x"
         self._thw = {"x": tuple(self.layer_in[self.start_idx][1:])}
         for idx in range(self.start_idx, self.end_idx + 1):
             if idx == 1:
-                cur = self._stconv(body.conv1, cur, None, False, None, "conv1")
+                c1 = body.conv1
+                cur = self._stconv(c1.spatial_conv, c1.bn, c1.temporal_conv, cur, None, False,
+                                   None, "conv1")
             else:
                 layer = getattr(body, "conv%d" % idx)
                 cur = self._block(layer.block1, cur, "conv%d.block1" % idx)
                 for j, blk in enumerate(layer.blocks):
                     cur = self._block(blk, cur, "conv%d.blocks.%d" % (idx, j))
         self.out_name = cur
+
+    def _analyse(self):
+        """Liveness and the defer-BN-on-load analysis of the built plan."""
         # liveness: buffers no later op reads are dropped right after their
         # last reader, so a forward (and a captured graph) holds only the
         # live activations, not all ~70 of them (R(2+1)D-34 fp32 at 128

@@ -50,9 +50,11 @@ from ...video_path_provider import (DirectoryLabels, DirectoryVideoPathIterator,
 from .decoder import make_decoder
 from .engine import (GraphedEngine, R2P1DEngine, boundary_channels_p, boundary_shape,
                      check_max_clips, parse_bucket_step)
-from .network import (DEFAULT_CLIP_LENGTH, LAYER_INPUT_CTHW, R2Plus1DLayerWrapper,
-                      check_clip_length, init_random_, load_reference_state_dict,
-                      normalize_layer_sizes)
+from .network import (DEFAULT_BN_EPS, DEFAULT_CLIP_LENGTH, LAYER_INPUT_CTHW,
+                      R2Plus1DLayerWrapper, TVVideoResNet, check_arch, check_bn_eps,
+                      check_clip_length, check_midplanes, init_random_,
+                      load_reference_state_dict, load_torchvision_state_dict,
+                      normalize_layer_sizes, tv_state_mids)
 from .sampler import PLACEMENTS, R2P1DSampler, check_frame_step, clip_span, parse_rate, step_of
 
 DEFAULT_MAX_CLIPS = 15
@@ -77,15 +79,19 @@ def _dtype(d):
     return _as_dtype(d if d is not None else DEFAULT_DTYPE)
 
 
-def default_bn_mode(bn_mode, dtype) -> str:
+def default_bn_mode(bn_mode, dtype, arch=None) -> str:
     """BatchNorm numerics of the runner plugins when a config does not say.
     The reference never calls ``.eval()`` (its runner only wraps the forward
     in ``torch.no_grad()``, reference runner.py:45), so every BatchNorm
     normalises with the statistics of the video being served: 'batch'
     (per-video segments, graphed at fp32). bf16 batch BN runs eagerly, so
     bf16 defaults to the folded 'eval' numerics. Configs choose either with
-    ``"bn_mode"`` (per step or in ``defaults``)."""
+    ``"bn_mode"`` (per step or in ``defaults``). ``arch="torchvision"``
+    defaults to 'eval' at both dtypes: published weights are served on their
+    running statistics ('batch' stays available, graphed at fp32)."""
     if bn_mode is None:
+        if check_arch(arch) == "torchvision":
+            return "eval"
         return "batch" if _dtype(dtype) == torch.float32 else "eval"
     if bn_mode not in ("eval", "batch"):
         raise ValueError("bn_mode must be 'eval' or 'batch', got %r" % (bn_mode,))
@@ -108,14 +114,39 @@ def _resolve_backend(backend: str, device: torch.device) -> str:
 
 def build_network(start_index: int, end_index: int, num_classes: int = 400,
                   layer_sizes=None, depth: Optional[int] = None, seed: int = 0,
-                  ckpt_path: Optional[str] = None) -> R2Plus1DLayerWrapper:
+                  ckpt_path: Optional[str] = None, arch: Optional[str] = None,
+                  midplanes: Optional[str] = None, bn_eps: Optional[float] = None):
+    """The module tree of layers [start_index, end_index], seeded at random or
+    loaded from ``ckpt_path``. ``arch="reference"`` (default): the reference's
+    tree and checkpoint format. ``arch="torchvision"``: torchvision's
+    ``VideoResNet`` layout (``r2plus1d_18``, IG65M ``r2plus1d_34``); the
+    mid-channel counts come from the checkpoint's tensor shapes when there is
+    one, else from ``midplanes`` ("block", torchvision's rule, or "conv");
+    ``bn_eps`` is the BatchNorms' eps (a state dict does not carry it)."""
+    arch = check_arch(arch)
+    midplanes, bn_eps = check_midplanes(midplanes), check_bn_eps(bn_eps)
     sizes = normalize_layer_sizes(start_index, end_index, layer_sizes, depth)
-    net = R2Plus1DLayerWrapper(start_index, end_index, num_classes, sizes)
-    init_random_(net, seed)
+    if arch == "reference":
+        if midplanes is not None or bn_eps is not None:
+            raise ValueError("midplanes / bn_eps belong to arch='torchvision'")
+        net = R2Plus1DLayerWrapper(start_index, end_index, num_classes, sizes)
+        init_random_(net, seed)
+        if ckpt_path:
+            ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
+            state = ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
+            load_reference_state_dict(net, state)
+        return net.eval()
+    state = None
     if ckpt_path:
         ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
         state = ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
-        load_reference_state_dict(net, state)
+    net = TVVideoResNet(start_index, end_index, num_classes, sizes,
+                        midplanes=midplanes or "block",
+                        bn_eps=DEFAULT_BN_EPS if bn_eps is None else bn_eps,
+                        mids=tv_state_mids(state) if isinstance(state, dict) else None)
+    init_random_(net, seed)
+    if state is not None:
+        load_torchvision_state_dict(net, state)
     return net.eval()
 
 
@@ -123,15 +154,16 @@ def build_engine(device: torch.device, start_index=1, end_index=5, num_classes=4
                  layer_sizes=None, depth=None, backend="auto", bn_mode="eval", seed=0,
                  ckpt_path=None, max_clips=DEFAULT_MAX_CLIPS, use_graphs=True,
                  autotune=True, dtype=None, buckets=None,
-                 clip_length=DEFAULT_CLIP_LENGTH):
+                 clip_length=DEFAULT_CLIP_LENGTH, arch=None, midplanes=None, bn_eps=None):
     clip_length = check_clip_length(clip_length)
+    arch = check_arch(arch)
     backend = _resolve_backend(backend, device)
     if backend == "hip":
         # before any weight is built: a call of max_clips clips must fit the
         # kernels' per-launch limits at this clip length
-        check_max_clips(max_clips, start_index, end_index, _dtype(dtype), clip_length)
+        check_max_clips(max_clips, start_index, end_index, _dtype(dtype), clip_length, arch)
     net = build_network(start_index, end_index, num_classes, layer_sizes, depth, seed,
-                        ckpt_path)
+                        ckpt_path, arch, midplanes, bn_eps)
     eng = R2P1DEngine(net, device, backend=backend, bn_mode=bn_mode, dtype=_dtype(dtype),
                       clip_length=clip_length)
     # batch-statistics BN is graphed for fp32 (per-video segments from a
@@ -165,9 +197,12 @@ class R2P1DRunner(RunnerModel):
                  bn_mode=None, seed=0, ckpt_path=None, max_clips=DEFAULT_MAX_CLIPS,
                  warmup=3, use_graphs=True, autotune=True, dtype=None,
                  max_batch_videos=1, batch_wait_ms=0.0, bucket_step=None, lanes=1,
-                 stream_priority=0, clip_length=DEFAULT_CLIP_LENGTH, **unused):
+                 stream_priority=0, clip_length=DEFAULT_CLIP_LENGTH, arch=None,
+                 midplanes=None, bn_eps=None, **unused):
         super().__init__(device)
         self.clip_length = clip_length = check_clip_length(clip_length)
+        self.arch = arch = check_arch(arch)
+        midplanes, bn_eps = check_midplanes(midplanes), check_bn_eps(bn_eps)
         if start_index < 1:
             raise ValueError("Wrong layer index for the starting layer! The start_index "
                              "(%d) should be more than or equal to 1." % start_index)
@@ -177,7 +212,7 @@ class R2P1DRunner(RunnerModel):
         self.start_index, self.end_index = start_index, end_index
         self.max_clips = int(max_clips)
         self.dtype = _dtype(dtype)
-        self.bn_mode = bn_mode = default_bn_mode(bn_mode, self.dtype)
+        self.bn_mode = bn_mode = default_bn_mode(bn_mode, self.dtype, arch)
         self.max_batch_videos = int(max_batch_videos)
         self.batch_wait_s = float(batch_wait_ms) / 1000.0
         # "geo": geometric spacing + bucket-aligned gathering (gather_fit)
@@ -185,7 +220,7 @@ class R2P1DRunner(RunnerModel):
         self.engine = build_engine(device, start_index, end_index, num_classes,
                                    layer_sizes, depth, backend, bn_mode, seed, ckpt_path,
                                    self.max_clips, use_graphs, autotune, self.dtype, buckets,
-                                   clip_length)
+                                   clip_length, arch, midplanes, bn_eps)
         # lanes > 1: that many graphed engines (own weights copy, BN buffers and
         # graph pool each; the same seed / checkpoint, so identical outputs) on
         # their own streams, calls rotating over them. One-video calls leave
@@ -200,7 +235,7 @@ class R2P1DRunner(RunnerModel):
             self._lane_engines.append(build_engine(
                 device, start_index, end_index, num_classes, layer_sizes, depth, backend,
                 bn_mode, seed, ckpt_path, self.max_clips, use_graphs, autotune, self.dtype,
-                buckets, clip_length))
+                buckets, clip_length, arch, midplanes, bn_eps))
         # lane streams at DEFAULT priority, not the runner's (runner.py passes
         # the queue group's, e.g. the high-priority 15-clip replica's): the
         # round-4 advice asked for the runner's; measured interleaved, it costs
@@ -692,7 +727,8 @@ class R2P1DSingleStep(RunnerModel):
                  bn_mode=None, ckpt_path=None, max_clips=DEFAULT_MAX_CLIPS, warmup=3,
                  use_graphs=True, autotune=True, dtype=None, decoder_args=None,
                  clip_length=DEFAULT_CLIP_LENGTH, crop=None, filter=None, frame_step=1,
-                 fps=None, placement="random", **unused):
+                 fps=None, placement="random", arch=None, midplanes=None, bn_eps=None,
+                 **unused):
         super().__init__(device)
         clip_length = check_clip_length(clip_length)
         self.loader = R2P1DLoader(device, num_clips_population, num_clips_weights,
@@ -705,7 +741,8 @@ class R2P1DSingleStep(RunnerModel):
                                   bn_mode=bn_mode, seed=model_seed, ckpt_path=ckpt_path,
                                   max_clips=max_clips, warmup=warmup,
                                   use_graphs=use_graphs, autotune=autotune, dtype=dtype,
-                                  clip_length=clip_length)
+                                  clip_length=clip_length, arch=arch, midplanes=midplanes,
+                                  bn_eps=bn_eps)
 
     @property
     def range_guarded(self) -> bool:

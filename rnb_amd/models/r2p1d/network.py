@@ -21,6 +21,16 @@ Architecture:
 
 ``R2Plus1DLayerNet`` builds any contiguous range of layers 1..5 (the
 layer-partitioned pipeline of model.py:20-84 / network.py:9-60).
+
+``arch="torchvision"`` (``TVVideoResNet``) is the other R(2+1)D people hold
+weights for: torchvision's ``VideoResNet`` with ``R2Plus1dStem``,
+``BasicBlock`` and ``Conv2Plus1D`` (``r2plus1d_18``, the IG65M
+``r2plus1d_34``). It is a different network -- a 45-channel stem followed by
+BN + ReLU, bias-free convs, a plain 1x1x1 stride-(2, 2, 2) conv + BN shortcut,
+one mid-channel count per block (or per conv: ``midplanes``) -- with the keys
+``stem.*``, ``layerN.M.*`` and ``fc.*`` (``load_torchvision_state_dict``).
+The layer ranges keep their meaning: index 1 is ``stem``, index k is
+``layer(k-1)``, and ``fc`` comes with index 5.
 """
 from __future__ import annotations
 
@@ -298,3 +308,217 @@ def load_reference_state_dict(model: R2Plus1DLayerWrapper, state_dict,
         keep.update({k: v for k, v in state_dict.items()
                      if k.startswith("linear.")})
     return model.load_state_dict(keep, strict=strict)
+
+
+# ---------------------------------------------------------------------------
+# torchvision layout (VideoResNet: R2Plus1dStem, BasicBlock, Conv2Plus1D)
+# ---------------------------------------------------------------------------
+ARCHS = ("reference", "torchvision")
+MIDPLANES_RULES = ("block", "conv")
+TV_STEM_MID = 45
+DEFAULT_BN_EPS = 1e-5
+
+
+def check_arch(arch, key: str = "arch") -> str:
+    """``arch`` (None = "reference"); ValueError (naming ``key``) otherwise."""
+    if arch is None:
+        return "reference"
+    if not isinstance(arch, str) or arch not in ARCHS:
+        raise ValueError("%s must be one of %s, got %r"
+                         % (key, ", ".join(repr(a) for a in ARCHS), arch))
+    return arch
+
+
+def check_midplanes(midplanes, key: str = "midplanes") -> Optional[str]:
+    """``midplanes`` ("block", "conv" or None = from the checkpoint, else
+    "block"); ValueError (naming ``key``) otherwise."""
+    if midplanes is None:
+        return None
+    if not isinstance(midplanes, str) or midplanes not in MIDPLANES_RULES:
+        raise ValueError("%s must be one of %s, got %r"
+                         % (key, ", ".join(repr(a) for a in MIDPLANES_RULES), midplanes))
+    return midplanes
+
+
+def check_bn_eps(bn_eps, key: str = "bn_eps") -> Optional[float]:
+    """``bn_eps`` as a positive float (None = the layout's 1e-5); ValueError
+    (naming ``key``) otherwise."""
+    if bn_eps is None:
+        return None
+    if isinstance(bn_eps, bool) or not isinstance(bn_eps, (int, float)) \
+            or not (0.0 < float(bn_eps) < 1.0):
+        raise ValueError("%s must be a float in (0, 1), got %r" % (key, bn_eps))
+    return float(bn_eps)
+
+
+def tv_midplanes(in_planes: int, planes: int) -> int:
+    """torchvision's ``Conv2Plus1D`` mid-channel count."""
+    return (in_planes * planes * 3 * 3 * 3) // (in_planes * 3 * 3 + 3 * planes)
+
+
+def tv_block_mids(layer_sizes: Dict[int, int], rule: str = "block") -> Dict[str, int]:
+    """``{"layerN.M.conv1": mid, "layerN.M.conv2": mid}`` for the residual
+    layers of ``layer_sizes`` (keyed 2..5). ``rule="block"`` is torchvision's:
+    one value per block, from the block's input and output planes, used by
+    both convs. ``rule="conv"`` recomputes it per conv from that conv's own
+    input and output planes (the reference's rule); the two differ only in the
+    second conv of a downsampling block (230 / 288, 460 / 576, 921 / 1152)."""
+    if rule not in MIDPLANES_RULES:
+        raise ValueError("midplanes must be 'block' or 'conv', got %r" % (rule,))
+    mids = {}
+    for idx, size in layer_sizes.items():
+        cin, planes = LAYER_CHANNELS[idx]
+        for j in range(size):
+            inp = cin if j == 0 else planes
+            name = "layer%d.%d" % (idx - 1, j)
+            mids[name + ".conv1"] = tv_midplanes(inp, planes)
+            mids[name + ".conv2"] = tv_midplanes(inp if rule == "block" else planes, planes)
+    return mids
+
+
+def tv_state_mids(state_dict) -> Dict[str, int]:
+    """The mid-channel count of every (2+1)D conv a torchvision-layout state
+    dict holds, from the shape of its spatial conv's weight."""
+    mids = {}
+    for k, v in state_dict.items():
+        parts = k.split(".")
+        if (len(parts) == 6 and parts[0].startswith("layer") and parts[2] in ("conv1", "conv2")
+                and parts[3:] == ["0", "0", "weight"] and hasattr(v, "shape") and len(v.shape) == 5):
+            mids[".".join(parts[:3])] = int(v.shape[0])
+    return mids
+
+
+def _conv2plus1d(in_planes, out_planes, mid, stride, eps):
+    return nn.Sequential(
+        nn.Conv3d(in_planes, mid, (1, 3, 3), stride=(1, stride, stride), padding=(0, 1, 1),
+                  bias=False),
+        nn.BatchNorm3d(mid, eps=eps),
+        nn.ReLU(),
+        nn.Conv3d(mid, out_planes, (3, 1, 1), stride=(stride, 1, 1), padding=(1, 0, 0),
+                  bias=False))
+
+
+class TVBasicBlock(nn.Module):
+    """torchvision's video ``BasicBlock`` over ``Conv2Plus1D``."""
+
+    def __init__(self, in_planes, planes, mid1, mid2, stride=1, eps=DEFAULT_BN_EPS):
+        super().__init__()
+        self.conv1 = nn.Sequential(_conv2plus1d(in_planes, planes, mid1, stride, eps),
+                                   nn.BatchNorm3d(planes, eps=eps), nn.ReLU())
+        self.conv2 = nn.Sequential(_conv2plus1d(planes, planes, mid2, 1, eps),
+                                   nn.BatchNorm3d(planes, eps=eps))
+        self.relu = nn.ReLU()
+        self.downsample = None
+        if stride != 1 or in_planes != planes:
+            self.downsample = nn.Sequential(
+                nn.Conv3d(in_planes, planes, 1, stride=(stride, stride, stride), bias=False),
+                nn.BatchNorm3d(planes, eps=eps))
+
+    def forward(self, x):
+        out = self.conv2(self.conv1(x))
+        res = x if self.downsample is None else self.downsample(x)
+        return self.relu(out + res)
+
+
+class TVVideoResNet(nn.Module):
+    """Layers [start_idx, end_idx] of torchvision's R(2+1)D ``VideoResNet``;
+    the state-dict keys of the built range are torchvision's own. ``mids``
+    names a (2+1)D conv's mid-channel count (``tv_block_mids`` /
+    ``tv_state_mids``); convs it does not name follow ``midplanes``."""
+
+    arch = "torchvision"
+
+    def __init__(self, start_idx, end_idx, num_classes, layer_sizes: Dict[int, int],
+                 midplanes: str = "block", bn_eps: float = DEFAULT_BN_EPS,
+                 mids: Optional[Dict[str, int]] = None):
+        super().__init__()
+        if not 1 <= start_idx <= end_idx <= 5:
+            raise ValueError("layer range must satisfy 1 <= start <= end <= 5, "
+                             "got %d..%d" % (start_idx, end_idx))
+        self.start_idx, self.end_idx = start_idx, end_idx
+        self.num_classes = num_classes
+        self.bn_eps = float(bn_eps)
+        table = tv_block_mids({i: layer_sizes[i] for i in range(max(2, start_idx), end_idx + 1)},
+                              midplanes)
+        table.update({k: int(v) for k, v in (mids or {}).items() if k in table})
+        self.mids = table
+        for idx in range(start_idx, end_idx + 1):
+            if idx == 1:
+                self.stem = nn.Sequential(
+                    nn.Conv3d(3, TV_STEM_MID, (1, 7, 7), stride=(1, 2, 2), padding=(0, 3, 3),
+                              bias=False),
+                    nn.BatchNorm3d(TV_STEM_MID, eps=bn_eps), nn.ReLU(),
+                    nn.Conv3d(TV_STEM_MID, 64, (3, 1, 1), padding=(1, 0, 0), bias=False),
+                    nn.BatchNorm3d(64, eps=bn_eps), nn.ReLU())
+                continue
+            cin, planes = LAYER_CHANNELS[idx]
+            blocks = []
+            for j in range(layer_sizes[idx]):
+                name = "layer%d.%d" % (idx - 1, j)
+                blocks.append(TVBasicBlock(cin if j == 0 else planes, planes,
+                                           table[name + ".conv1"], table[name + ".conv2"],
+                                           stride=2 if (j == 0 and idx > 2) else 1, eps=bn_eps))
+            setattr(self, "layer%d" % (idx - 1), nn.Sequential(*blocks))
+        if end_idx == 5:
+            self.avgpool = nn.AdaptiveAvgPool3d(1)
+            self.fc = nn.Linear(512, num_classes)
+
+    def key_prefixes(self) -> List[str]:
+        """State-dict key prefixes of the built range."""
+        out = ["stem." if i == 1 else "layer%d." % (i - 1)
+               for i in range(self.start_idx, self.end_idx + 1)]
+        return out + (["fc."] if self.end_idx == 5 else [])
+
+    def forward(self, x):
+        for idx in range(self.start_idx, self.end_idx + 1):
+            x = self.stem(x) if idx == 1 else getattr(self, "layer%d" % (idx - 1))(x)
+        if self.end_idx == 5:
+            x = self.fc(self.avgpool(x).flatten(1))
+        return x
+
+
+def _unwrap_state(state):
+    if isinstance(state, dict) and "state_dict" in state and isinstance(state["state_dict"], dict):
+        return state["state_dict"]
+    return state
+
+
+def load_torchvision_state_dict(model: TVVideoResNet, state, strict: bool = True):
+    """Load a torchvision-layout R(2+1)D state dict (raw, or wrapped as
+    ``{"state_dict": ...}``) restricted to the range ``model`` builds;
+    ``num_batches_tracked`` entries are accepted. Raises a ValueError naming
+    the first missing key, the first unexpected key (within the built range's
+    prefixes) or the first key whose shape differs, with both shapes."""
+    state = _unwrap_state(state)
+    if not isinstance(state, dict):
+        raise ValueError("expected a state dict, got %s" % type(state).__name__)
+    if getattr(model, "arch", "reference") != "torchvision":
+        raise ValueError("load_torchvision_state_dict needs a model built with "
+                         "arch='torchvision'")
+    ref_keys = [k for k in state if k.startswith(("res2plus1d.", "linear."))]
+    if ref_keys and not any(k.startswith(("stem.", "layer", "fc.")) for k in state):
+        raise ValueError("the checkpoint holds reference-format keys (first: %r): load it with "
+                         "arch='reference', not arch='torchvision'" % ref_keys[0])
+    prefixes = tuple(model.key_prefixes())
+    keep = {k: v for k, v in state.items() if k.startswith(prefixes)}
+    own = model.state_dict()
+    if strict:
+        for k in own:
+            if k not in keep and not k.endswith("num_batches_tracked"):
+                raise ValueError("torchvision checkpoint: missing key %r (layers %d..%d)"
+                                 % (k, model.start_idx, model.end_idx))
+        for k in keep:
+            if k not in own:
+                raise ValueError("torchvision checkpoint: unexpected key %r (layers %d..%d; "
+                                 "another depth or layout?)"
+                                 % (k, model.start_idx, model.end_idx))
+    for k, v in keep.items():
+        if k in own and tuple(v.shape) != tuple(own[k].shape):
+            if k == "fc.weight" and tuple(v.shape[1:]) == tuple(own[k].shape[1:]):
+                raise ValueError("torchvision checkpoint: fc.weight has %d rows but the model "
+                                 "was built with num_classes %d: set num_classes to %d"
+                                 % (v.shape[0], own[k].shape[0], v.shape[0]))
+            raise ValueError("torchvision checkpoint: shape mismatch at %r: checkpoint %s, "
+                             "model %s" % (k, tuple(v.shape), tuple(own[k].shape)))
+    keep = {k: v for k, v in keep.items() if k in own}
+    return model.load_state_dict(keep, strict=False)

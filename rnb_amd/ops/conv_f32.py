@@ -155,8 +155,9 @@ H3S_PIXELS = (256, 128, 64, 128, 128)
 # stem h3 kernel (csrc/conv_h3stem.hip conv_h3stem_kernel): 1x7x7 stride (1, 2, 2)
 # pad (0, 3, 3) with Cin_p 4 and K-permuted weights (h3stem_buffers), variant
 # H3STEM_BASE + v of rnb_conv_h3stem_launch; output pixels per block per variant
+# (variants 0-2: 96 output channels per block, 3-6: 48; kernels().conv_h3stem_ctile)
 H3STEM_BASE = 1430
-H3STEM_PIXELS = (256, 128, 448)
+H3STEM_PIXELS = (256, 128, 448, 256, 128, 448, 832)
 # pixel-major persistent temporal h3 kernel (csrc/conv_h3p.hip conv_h3p_kernel):
 # 3x1x1 stride 1 pad (1, 0, 0) at T 8 with Cin_p <= 160 and Cout_p <= 64, the
 # h3t weights; id H3P_BASE + v launches H3P_BPC[v] persistent blocks per CU
@@ -1017,6 +1018,23 @@ class ConvLayerF32:
                 and tuple(g.padding) == (0, 3, 3) and g.cin_p == 4)
 
     def h3stem_fits(self, variant: int, x_shape, efficient: bool = True) -> bool:
+        """Whether the stem kernel's variant ``variant`` is offered for the
+        shape: its band fits the frame (``_h3stem_band_fits``), and its channel
+        tile suits the conv -- a conv of at most 48 (padded) output channels
+        takes the 48-channel variants, and the 96-channel ones only where no
+        48-channel variant fits; a wider conv takes the 96-channel ones."""
+        from .native import kernels
+        k = kernels()
+        if not self._h3stem_band_fits(variant, x_shape, efficient):
+            return False
+        narrow = k.conv_h3stem_ctile(variant) <= 48
+        if self.geom.cout_p > 48:
+            return not narrow
+        return narrow or not any(
+            k.conv_h3stem_ctile(v) <= 48 and self._h3stem_band_fits(v, x_shape, efficient)
+            for v in range(k.h3stem_variants))
+
+    def _h3stem_band_fits(self, variant: int, x_shape, efficient: bool = True) -> bool:
         if x_shape is None:
             return True
         from .native import kernels
@@ -1025,7 +1043,7 @@ class ConvLayerF32:
         rows = kernels().conv_h3stem_rows(variant, Ho, Wo)
         if rows < 1:
             return False
-        return not efficient or 2 * rows * Wo >= H3STEM_PIXELS[variant]
+        return not efficient or 2 * rows * Wo >= kernels().conv_h3stem_pixels(variant)
 
     def h3stem_buffers(self):
         """h3 split weights of the stem kernel's K order: step dy (a kernel

@@ -454,6 +454,10 @@ class Kernels:
         lib.rnb_conv_h3stem_launch.restype = ctypes.c_int
         lib.rnb_conv_h3stem_rows.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
         lib.rnb_conv_h3stem_rows.restype = ctypes.c_int
+        lib.rnb_conv_h3stem_ctile.argtypes = [ctypes.c_int]
+        lib.rnb_conv_h3stem_ctile.restype = ctypes.c_int
+        lib.rnb_conv_h3stem_pixels.argtypes = [ctypes.c_int]
+        lib.rnb_conv_h3stem_pixels.restype = ctypes.c_int
         lib.rnb_conv_h3p_launch.argtypes = [ctypes.POINTER(ConvParams), ctypes.c_int,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_int, ctypes.c_float, ctypes.c_float,
@@ -691,6 +695,14 @@ class Kernels:
 
     def conv_h3stem_rows(self, variant: int, Ho: int, Wo: int) -> int:
         return int(self.lib.rnb_conv_h3stem_rows(variant, Ho, Wo))
+
+    def conv_h3stem_ctile(self, variant: int) -> int:
+        """Output channels per block of h3stem variant ``variant`` (48 or 96)."""
+        return int(self.lib.rnb_conv_h3stem_ctile(variant))
+
+    def conv_h3stem_pixels(self, variant: int) -> int:
+        """Output pixels per block of h3stem variant ``variant``."""
+        return int(self.lib.rnb_conv_h3stem_pixels(variant))
 
     def conv_h3s_rows(self, variant: int, Ho: int, Wo: int) -> int:
         """Output rows per band of h3s variant ``variant`` (0: cannot run)."""
