@@ -151,6 +151,63 @@ int rnb_spin(void* stream, long long cycles) {
   return (int)hipGetLastError();
 }
 
+// Slot flags in IPC device memory: GPU-side ordering between processes where
+// the runtime has no interprocess events (hipIpcGetEventHandle pins the
+// event's shared memory with hipHostRegister, which some machines refuse).
+// A flag holds a per-slot sequence number; "set" publishes everything enqueued
+// on the stream before it, "wait" holds the stream until the flag reaches
+// ``value`` (wrap-safe compare). Both are one-thread kernels. A wait is only
+// enqueued after its matching set is on the other process's stream, so it ends
+// unless that process dies first; for that case the wait also watches
+// ``abort`` (host-coherent memory of the waiting process, may be null) and
+// gives up once the host has set it (pipeline abort: the data is discarded).
+__global__ void rnb_flag_set_kernel(unsigned* flag, unsigned value) {
+  __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__global__ void rnb_flag_wait_kernel(unsigned* flag, unsigned value, unsigned* abort) {
+  while ((int)(__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) - value) < 0) {
+    if (abort != nullptr &&
+        __hip_atomic_load(abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0)
+      return;
+    __builtin_amdgcn_s_sleep(16);
+  }
+}
+
+int rnb_flag_set(void* stream, void* flag, unsigned value) {
+  hipLaunchKernelGGL(rnb_flag_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream,
+                     (unsigned*)flag, value);
+  return (int)hipGetLastError();
+}
+
+int rnb_flag_wait(void* stream, void* flag, unsigned value, void* abort) {
+  hipLaunchKernelGGL(rnb_flag_wait_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream,
+                     (unsigned*)flag, value, (unsigned*)abort);
+  return (int)hipGetLastError();
+}
+
+// zero device memory and wait for it (slot flags, before their handle is published)
+int rnb_memset_zero(void* ptr, size_t bytes) {
+  const hipError_t e = hipMemset(ptr, 0, bytes);
+  if (e != hipSuccess) return (int)e;
+  return (int)hipDeviceSynchronize();
+}
+
+// 1 when this process can export an interprocess event, 0 when the runtime
+// has none (hipIpcGetEventHandle answers invalid value / not supported; the
+// error is cleared), < 0: -(any other error of the create or the export)
+int rnb_ipc_events_supported() {
+  hipEvent_t e;
+  hipError_t r = hipEventCreateWithFlags(&e, hipEventInterprocess | hipEventDisableTiming);
+  if (r != hipSuccess) return -(int)r;
+  hipIpcEventHandle_t h;
+  r = hipIpcGetEventHandle(&h, e);
+  (void)hipEventDestroy(e);
+  (void)hipGetLastError();
+  if (r == hipSuccess) return 1;
+  return (r == hipErrorInvalidValue || r == hipErrorNotSupported) ? 0 : -(int)r;
+}
+
 int rnb_can_access_peer(int dev, int peer, int* out) {
   return (int)hipDeviceCanAccessPeer(out, dev, peer);
 }

@@ -1243,6 +1243,11 @@ class Runtime:
         lib.rnb_stream_create_cumask.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int,
                                                  ctypes.POINTER(vp)]
         lib.rnb_spin.argtypes = [vp, ctypes.c_longlong]
+        lib.rnb_flag_set.argtypes = [vp, vp, ctypes.c_uint]
+        lib.rnb_flag_wait.argtypes = [vp, vp, ctypes.c_uint, vp]
+        lib.rnb_memset_zero.argtypes = [vp, sz]
+        self._ipc_events = None
+        self._abort_word = None     # (host, device) address of this process's abort word
         self.handle_size = lib.rnb_ipc_handle_size()
         self.event_handle_size = lib.rnb_ipc_event_handle_size()
 
@@ -1349,6 +1354,40 @@ class Runtime:
         """hipEventDestroy: frees an event this process created, or closes an
         interprocess event it opened with ``event_open_handle``."""
         _check(self.lib.rnb_event_destroy(ev), "hipEventDestroy")
+
+    def ipc_events_supported(self) -> bool:
+        """Whether this machine's runtime exports interprocess events
+        (hipIpcGetEventHandle; it needs hipHostRegister, which some machines
+        refuse). Asked once per process, on the current device."""
+        if self._ipc_events is None:
+            rc = int(self.lib.rnb_ipc_events_supported())
+            if rc < 0:
+                _check(-rc, "interprocess event probe (hipEventCreateWithFlags / "
+                            "hipIpcGetEventHandle)")
+            self._ipc_events = rc == 1
+        return self._ipc_events
+
+    def flag_set(self, stream: int, flag: int, value: int) -> None:
+        """Store ``value`` to the 32-bit slot flag at device address ``flag``
+        after the work enqueued on ``stream`` so far."""
+        _check(self.lib.rnb_flag_set(stream, flag, value & 0xFFFFFFFF), "flag set kernel")
+
+    def flag_wait(self, stream: int, flag: int, value: int) -> None:
+        """Hold ``stream`` until the slot flag at ``flag`` has reached ``value``
+        (or ``abort_flag_waits`` was called in this process)."""
+        if self._abort_word is None:
+            self._abort_word = self.host_alloc_mapped(64)
+        _check(self.lib.rnb_flag_wait(stream, flag, value & 0xFFFFFFFF, self._abort_word[1]),
+               "flag wait kernel")
+
+    def abort_flag_waits(self) -> None:
+        """Make every ``flag_wait`` of this process, queued or later, give up
+        (pipeline abort: a peer that died never sets its flags)."""
+        if self._abort_word is not None:
+            ctypes.c_uint32.from_address(self._abort_word[0]).value = 1
+
+    def memset_zero(self, ptr: int, nbytes: int) -> None:
+        _check(self.lib.rnb_memset_zero(ptr, nbytes), "hipMemset")
 
     def memcpy_async(self, dst: int, src: int, nbytes: int, stream: int) -> None:
         _check(self.lib.rnb_memcpy_async(dst, src, nbytes, stream), "hipMemcpyAsync")

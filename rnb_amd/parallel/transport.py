@@ -212,7 +212,10 @@ class HostRing(RingBase):
 
 
 EVENT_HANDLE_BYTES = 64     # sizeof(hipIpcEventHandle_t); checked at attach
-ORDER_ENV = "RNB_RING_ORDER"  # "event" (default): GPU-side ordering; "host": stream syncs
+# "event" (default): GPU-side ordering, by interprocess events where the
+# runtime has them and by slot flags otherwise; "flag": slot flags always;
+# "host": stream syncs
+ORDER_ENV = "RNB_RING_ORDER"
 
 
 class _CudaArray:
@@ -285,6 +288,21 @@ class IpcRing(RingBase):
     will wait on; the other side re-opens the handle when the epoch changed.
     A refused wait still falls back to the host (``_wait_ipc_event``).
 
+    Slot flags. Where the runtime cannot export an interprocess event
+    (``hipIpcGetEventHandle`` pins the event's shared memory with
+    hipHostRegister, which some machines refuse; ``ipc_events_supported``) the
+    same two dependencies go through two 32-bit flags per slot in one more
+    small IPC allocation of the producer: "written" and "released" hold the
+    slot's generation. The producer's stream stores the new generation to
+    "written" after the slot's data (``flag_set``) and the consumer's stream
+    waits for it before the pull (``flag_wait``); the consumer's stream stores
+    it to "released" after the pull and the producer's stream waits for that
+    before it writes the slot again. Nothing blocks the host here either, and
+    there are no events to rotate or retire. The producer decides at attach
+    and names its choice in the descriptor; a consumer follows it from its
+    first pull on. A flag wait gives up when the waiting process calls
+    ``abort_gpu_waits`` (pipeline abort: a peer that died sets no flag).
+
     Event lifecycle (bounded; the reference keeps a fixed set of per-slot
     events, control.py:19-46). A superseded event -- a "written" or
     "released" event its owner replaced, or a handle a peer re-opened for a
@@ -352,6 +370,12 @@ class IpcRing(RingBase):
         self._dev = None
         self._views = None
         self._token = None
+        # "event" or "flag" (gpu_ordered only): the producer decides at attach,
+        # a consumer reads the producer's choice from the descriptor (_open)
+        self._sync = None
+        self._flags = None         # producer: the slot flags' allocation
+        self._flags_open: Dict[Tuple, int] = {}     # consumer: opened flag allocations
+        self._pulled_from = None   # consumer: producer token of the last pull
 
     def set_consumers(self, consumers) -> None:
         """Declare the consumer instances (before the processes are spawned)."""
@@ -380,11 +404,27 @@ class IpcRing(RingBase):
         st["_cid"] = None
         st["_views"] = None
         st["_token"] = None
+        st["_sync"] = None
+        st["_flags"] = None
+        st["_flags_open"] = {}
+        st["_pulled_from"] = None
         return st
 
     @property
     def gpu_ordered(self) -> bool:
-        return self.order == "event"
+        return self.order in ("event", "flag")
+
+    def _decide_sync(self) -> None:
+        """Interprocess events, or slot flags where this machine has none."""
+        from ..ops import native
+        if self.order == "event" and native.runtime().ipc_events_supported():
+            self._sync = "event"
+        else:
+            self._sync = "flag"
+
+    def _flag(self, base: int, released: bool, idx: int) -> int:
+        """Address of slot ``idx``'s "written" / "released" flag."""
+        return base + 4 * ((self.num_slots if released else 0) + idx)
 
     # ---- producer ---------------------------------------------------------
     def producer_attach(self, device):
@@ -401,6 +441,12 @@ class IpcRing(RingBase):
                        for o in self.tensor_offsets] for i in range(self.num_slots)]
         wh = ()
         if self.gpu_ordered:
+            self._decide_sync()
+        if self._sync == "flag":
+            self._flags = rt.ipc_malloc(8 * self.num_slots)
+            rt.memset_zero(self._flags, 8 * self.num_slots)
+            wh = (rt.ipc_get_handle(self._flags),)
+        elif self._sync == "event":
             if rt.event_handle_size > EVENT_HANDLE_BYTES:
                 raise RuntimeError("hipIpcEventHandle_t is %d bytes (> %d)"
                                    % (rt.event_handle_size, EVENT_HANDLE_BYTES))
@@ -408,7 +454,7 @@ class IpcRing(RingBase):
             self._wrec = [0] * self.num_slots
             for i in range(self.num_slots):
                 self._new_written_event(i)
-        self._desc = (self.name, os.getpid(), device.index, handle, wh)
+        self._desc = (self.name, os.getpid(), device.index, handle, wh, self._sync)
         import pickle
         blob = pickle.dumps(self._desc, protocol=pickle.HIGHEST_PROTOCOL)
         if len(blob) > self._desc_cap:
@@ -507,6 +553,12 @@ class IpcRing(RingBase):
         if cid < 0:
             return
         stream = stream or torch.cuda.current_stream(self._dev)
+        if self._sync == "flag":
+            from ..ops import native
+            native.runtime().flag_wait(stream.cuda_stream, self._flag(self._flags, True, idx),
+                                       self.gen[idx])
+            self.gpu_waits += 1
+            return
         ev, old = self._release_event(cid, idx)
         self._wait_ipc_event(stream, ev, idx)
         self._retire(old, stream)
@@ -538,7 +590,11 @@ class IpcRing(RingBase):
         was enqueued on ``stream``)."""
         from ..ops import native
         stream = stream or torch.cuda.current_stream(self._dev)
-        if self.gpu_ordered:
+        if self._sync == "flag":
+            # the generation that _publish below gives the slot
+            native.runtime().flag_set(stream.cuda_stream, self._flag(self._flags, False, idx),
+                                      self.gen[idx] + 1)
+        elif self.gpu_ordered:
             old = None
             if self._wrec[idx] >= EVENT_ROTATE:
                 old = self._new_written_event(idx)
@@ -614,7 +670,11 @@ class IpcRing(RingBase):
                      for o in self.tensor_offsets] for i in range(self.num_slots)]
             self._opened[key] = ptrs
             self._opened_base[key] = base
-            if self.gpu_ordered:
+            if self._cid is not None:
+                self._sync = desc[5]              # order the way the producer does
+            if self._sync == "flag":
+                self._flags_open[key] = rt.ipc_open_handle(desc[4][0])
+            elif self._sync == "event":
                 self._wopen[key] = [None] * self.num_slots    # opened on first pull
         return ptrs
 
@@ -653,7 +713,13 @@ class IpcRing(RingBase):
         gpu = dev.type == "cuda"
         if gpu:
             stream = torch.cuda.current_stream(dev)
-            if self.gpu_ordered:
+            if self._sync == "flag":
+                self._pulled_from = tuple(descriptor[:2])
+                rt.flag_wait(stream.cuda_stream,
+                             self._flag(self._flags_open[self._pulled_from], False, idx),
+                             self.gen[idx])
+                self.gpu_waits += 1
+            elif self._sync == "event":
                 ev, old = self._written_event(tuple(descriptor[:2]), idx)
                 self._wait_ipc_event(stream, ev, idx)
                 self._retire(old, stream)
@@ -673,7 +739,15 @@ class IpcRing(RingBase):
         return out
 
     def release(self, idx: int) -> None:
-        if self.gpu_ordered and self._rev is not None:
+        if self._sync == "flag":
+            if self._pulled_from is not None:
+                from ..ops import native
+                stream = torch.cuda.current_stream(self.consumer_device)
+                native.runtime().flag_set(
+                    stream.cuda_stream,
+                    self._flag(self._flags_open[self._pulled_from], True, idx), self.gen[idx])
+                self.released_by[idx] = self._cid
+        elif self._sync == "event" and self._rev is not None:
             from ..ops import native
             rt = native.runtime()
             old = None
@@ -729,6 +803,13 @@ class IpcRing(RingBase):
             self._rev = [None] * self.num_slots if self._rev is not None else None
             self._rel_open = {}
             self._wopen = {}
+        if self._flags_open:
+            dev = getattr(self, "consumer_device", None)
+            if dev is not None and dev.type == "cuda":
+                torch.cuda.synchronize(dev)
+            for base in self._flags_open.values():
+                rt.ipc_close_handle(base)
+            self._flags_open = {}
         for bases in self._opened_base.values():
             for base in bases:
                 rt.ipc_close_handle(base)
@@ -740,7 +821,17 @@ class IpcRing(RingBase):
             for base in self._base:
                 rt.free(base)
             self._base = None
+            if self._flags is not None:
+                rt.free(self._flags)
+                self._flags = None
             self._ptrs = None
+
+
+def abort_gpu_waits() -> None:
+    """Pipeline abort: the flag waits queued on this process's streams give up,
+    so that synchronising them returns even if a peer died before its set."""
+    from ..ops import native
+    native.runtime().abort_flag_waits()
 
 
 def make_ring(ctx, shapes, dtypes, num_slots, producer_gpu, consumers_cpu,

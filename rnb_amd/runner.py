@@ -157,6 +157,16 @@ def _runner_body(input_queue, output_queues, queue_selector_path, print_summary,
     if use_gpu:
         torch.cuda.set_device(g_idx)
         device = torch.device("cuda:%d" % g_idx)
+        # the host-side tensor work of a GPU stage is small (weight packing at
+        # setup): with the ambient thread count (OMP_NUM_THREADS, or one per
+        # core) the stage processes of a GPU oversubscribe the CPUs between
+        # them (bench.py's 5 processes on a 16-CPU host with
+        # OMP_NUM_THREADS=16: 33.6 and 35.3 s of setup in two runs, 12.7 and
+        # 12.6 s with 2 threads each). The cap is an eighth of the CPUs this
+        # process may use, at least 2: a many-core host keeps its threads
+        cap = os.environ.get("RNB_GPU_HOST_THREADS")
+        cap = int(cap) if cap else max(2, len(os.sched_getaffinity(0)) // 8)
+        torch.set_num_threads(max(1, min(torch.get_num_threads(), cap)))
         # stages whose GPU work gates everyone else (decoding) ask for a
         # high-priority stream (RunnerModel.stream_priority, lower = higher)
         from .utils.class_utils import load_class as _lc
@@ -864,6 +874,11 @@ def _runner_body(input_queue, output_queues, queue_selector_path, print_summary,
         # stream: drain them before fin_bar, after which producers free their
         # slots, then close the handles this consumer opened on input rings
         if stream is not None:
+            if termination_flag.value in (TerminationFlag.CHILD_FAILED,
+                                          TerminationFlag.BARRIER_TIMEOUT):
+                # a peer that died never sets its slot flags
+                from .parallel.transport import abort_gpu_waits
+                abort_gpu_waits()
             stream.synchronize()
         for ring in _rings(shared_input_rings):
             if hasattr(ring, "close"):
