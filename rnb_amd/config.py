@@ -20,8 +20,9 @@ rnb_amd keeps every key and rule of the reference and adds a few optional keys:
 * step ``slot_dtype``: override the slot dtype advertised by the model;
 * top-level ``defaults``: kwargs merged into every step (e.g. ``"depth": 34``);
 * ``arch`` (``"reference"`` or ``"torchvision"``), ``midplanes`` (``"block"`` or
-  ``"conv"``) and ``bn_eps``, in ``defaults`` or per step / queue group: the
-  network layout of the model steps (models/r2p1d/network.py).
+  ``"conv"``), ``bn_eps`` and ``tv_block`` (``"2plus1d"`` or ``"3d"`` =
+  ``r3d_18``), in ``defaults`` or per step / queue group: the network layout
+  of the model steps (models/r2p1d/network.py).
 
 Validation errors raise ``ConfigError`` instead of calling ``sys.exit()`` so
 that tests can exercise them; the CLI turns them into a clean message.
@@ -246,6 +247,7 @@ def parse_pipeline(config: Dict[str, Any]) -> PipelineSpec:
 
 ARCHS = ("reference", "torchvision")
 MIDPLANES_RULES = ("block", "conv")
+TV_BLOCKS = ("2plus1d", "3d")
 
 
 def _check_arch_keys(kwargs: Dict[str, Any], where: str) -> None:
@@ -263,9 +265,17 @@ def _check_arch_keys(kwargs: Dict[str, Any], where: str) -> None:
     if eps is not None and (isinstance(eps, bool) or not isinstance(eps, (int, float))
                             or not 0.0 < float(eps) < 1.0):
         raise ConfigError("%s: bn_eps must be a float in (0, 1), got %r" % (where, eps))
-    if (mid is not None or eps is not None) and arch != "torchvision":
+    blk = kwargs.get("tv_block")
+    if blk is not None and (not isinstance(blk, str) or blk not in TV_BLOCKS):
+        raise ConfigError("%s: tv_block must be one of %s, got %r"
+                          % (where, ", ".join(repr(a) for a in TV_BLOCKS), blk))
+    if (mid is not None or eps is not None or blk is not None) and arch != "torchvision":
         raise ConfigError("%s: %s belongs to \"arch\": \"torchvision\", got arch %r"
-                          % (where, "midplanes" if mid is not None else "bn_eps", arch))
+                          % (where, "midplanes" if mid is not None else
+                             "bn_eps" if eps is not None else "tv_block", arch))
+    if blk == "3d" and mid is not None:
+        raise ConfigError("%s: midplanes belongs to \"tv_block\": \"2plus1d\", got tv_block %r"
+                          % (where, blk))
 
 
 def _check_clip_lengths(steps: List[StepSpec]) -> None:

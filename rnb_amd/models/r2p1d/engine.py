@@ -114,7 +114,7 @@ BN_MAX_ELEMS = 0x7FFFFFFF * 4
 
 def activation_elems_per_clip(start_idx: int, end_idx: int, dtype=torch.float32,
                               clip_length: int = DEFAULT_CLIP_LENGTH,
-                              arch: str = "reference") -> int:
+                              arch: str = "reference", tv_block: str = "2plus1d") -> int:
     """Elements per clip of the largest activation layers [start_idx, end_idx]
     hold: the boundary tensors of the geometry table and each layer's largest
     (2+1)D intermediate (the first spatial conv's output: the layer's input
@@ -122,7 +122,9 @@ def activation_elems_per_clip(start_idx: int, end_idx: int, dtype=torch.float32,
     ``arch="torchvision"``: the stem's intermediate has 45 channels; a block's
     mid-channel counts are at most the reference rule's (per conv), which
     bounds both ``midplanes`` rules, and the 1x1x1 shortcut's output has the
-    layer's output shape."""
+    layer's output shape. ``tv_block="3d"`` (r3d_18) has no intermediates:
+    every conv's output has its layer's output shape (the stem's 64 channels,
+    a block's first conv and shortcut the block's output)."""
     inp, out = layer_geometry(clip_length)
     f32 = dtype == torch.float32
     align = F32_ALIGN if f32 else CH_ALIGN
@@ -141,7 +143,8 @@ def activation_elems_per_clip(start_idx: int, end_idx: int, dtype=torch.float32,
             mids.append(intermediate_channels(cout, cout, kernel))
         # fp32 pads a temporal Winograd conv's input to 16 channels (_stconv)
         midp = max(pad_to(m, 16 if f32 else align) for m in mids)
-        worst = max(worst, t * ho * wo * midp)
+        if not (arch == "torchvision" and tv_block == "3d"):
+            worst = max(worst, t * ho * wo * midp)
         if out[idx] is not None:
             co, to, ho2, wo2 = out[idx]
             worst = max(worst, to * ho2 * wo2 * pad_to(co, align))
@@ -149,24 +152,26 @@ def activation_elems_per_clip(start_idx: int, end_idx: int, dtype=torch.float32,
 
 
 def max_clips_limit(start_idx: int, end_idx: int, dtype=torch.float32,
-                    clip_length: int = DEFAULT_CLIP_LENGTH, arch: str = "reference") -> int:
+                    clip_length: int = DEFAULT_CLIP_LENGTH, arch: str = "reference",
+                    tv_block: str = "2plus1d") -> int:
     """Largest ``max_clips`` whose calls every kernel of the layer range can
     index. Rows per clip grow with the clip length, so the bound shrinks with
     it. The fp32 conv launches are split by clips (ConvLayerF32.chunk_clips),
     so at fp32 the per-call bound is the BatchNorm kernels' element limit; the
     bf16 conv launchers take a whole call, so at bf16 it is their byte limit."""
-    per = activation_elems_per_clip(start_idx, end_idx, dtype, clip_length, arch)
+    per = activation_elems_per_clip(start_idx, end_idx, dtype, clip_length, arch, tv_block)
     if dtype == torch.float32:
         return BN_MAX_ELEMS // per
     return CONV_MAX_BYTES // (2 * per)
 
 
 def check_max_clips(max_clips: int, start_idx: int, end_idx: int, dtype=torch.float32,
-                    clip_length: int = DEFAULT_CLIP_LENGTH, arch: str = "reference") -> int:
+                    clip_length: int = DEFAULT_CLIP_LENGTH, arch: str = "reference",
+                    tv_block: str = "2plus1d") -> int:
     """``max_clips`` if calls of that many clips fit the kernels' per-launch
     limits, else ValueError -- raised at construction, so that no launcher
     error surfaces while a graph bucket is captured."""
-    fit = max_clips_limit(start_idx, end_idx, dtype, clip_length, arch)
+    fit = max_clips_limit(start_idx, end_idx, dtype, clip_length, arch, tv_block)
     if int(max_clips) > fit:
         raise ValueError("max_clips %d is too large at clip_length %d for layers %d..%d (%s): "
                          "the largest activation passes the kernels' per-launch limit; the "
@@ -215,6 +220,8 @@ class R2P1DEngine:
         self.start_idx, self.end_idx = net.start_idx, net.end_idx
         # "reference" (R2Plus1DLayerWrapper) or "torchvision" (TVVideoResNet)
         self.arch = getattr(net, "arch", "reference")
+        # torchvision layout: "2plus1d" (r2plus1d_*) or "3d" (r3d_18)
+        self.tv_block = getattr(net, "tv_block", "2plus1d")
         self.num_classes = getattr(net, "num_classes", 400)
         self.ops: List[PlanOp] = []
         self.head: Optional[Head] = None
@@ -376,16 +383,35 @@ class R2P1DEngine:
         h = self._stconv(c1[0], c1[1], c1[3], src, bn1, True, None, name + ".conv1")
         return self._stconv(c2[0], c2[1], c2[3], h, bn2, True, res, name + ".conv2")
 
+    def _block_tv3d(self, blk, src: str, name: str) -> str:
+        """torchvision ``BasicBlock`` over ``Conv3DSimple`` (r3d_18): two 3x3x3
+        convs, the shortcut as in ``_block_tv``."""
+        if blk.downsample is not None:
+            res = self._name()
+            self._append(blk.downsample[0], blk.downsample[1], False, None,
+                         name + ".downsample", src, res)
+        else:
+            res = src
+        h, dst = self._name(), self._name()
+        self._append(blk.conv1[0], blk.conv1[1], True, None, name + ".conv1", src, h)
+        self._append(blk.conv2[0], blk.conv2[1], True, res, name + ".conv2", h, dst)
+        return dst
+
     def _build_tv(self, net):
         cur = "x"
         self._thw = {"x": tuple(self.layer_in[self.start_idx][1:])}
+        v3d = self.tv_block == "3d"
         for idx in range(self.start_idx, self.end_idx + 1):
-            if idx == 1:
+            if idx == 1 and v3d:
+                s, cur, src = net.stem, self._name(), cur
+                self._append(s[0], s[1], True, None, "stem", src, cur)
+            elif idx == 1:
                 s = net.stem
                 cur = self._stconv(s[0], s[1], s[3], cur, s[4], True, None, "stem")
             else:
+                block = self._block_tv3d if v3d else self._block_tv
                 for j, blk in enumerate(getattr(net, "layer%d" % (idx - 1))):
-                    cur = self._block_tv(blk, cur, "layer%d.%d" % (idx - 1, j))
+                    cur = block(blk, cur, "layer%d.%d" % (idx - 1, j))
             if self.layer_out[idx] is not None and self._thw[cur] != tuple(self.layer_out[idx][1:]):
                 raise ValueError("layer %d leaves %s, the boundary table says %s"
                                  % (idx, self._thw[cur], tuple(self.layer_out[idx][1:])))

@@ -52,9 +52,9 @@ from .engine import (GraphedEngine, R2P1DEngine, boundary_channels_p, boundary_s
                      check_max_clips, parse_bucket_step)
 from .network import (DEFAULT_BN_EPS, DEFAULT_CLIP_LENGTH, LAYER_INPUT_CTHW,
                       R2Plus1DLayerWrapper, TVVideoResNet, check_arch, check_bn_eps,
-                      check_clip_length, check_midplanes, init_random_,
+                      check_clip_length, check_midplanes, check_tv_block, init_random_,
                       load_reference_state_dict, load_torchvision_state_dict,
-                      normalize_layer_sizes, tv_state_mids)
+                      normalize_layer_sizes, tv_state_block, tv_state_mids)
 from .sampler import PLACEMENTS, R2P1DSampler, check_frame_step, clip_span, parse_rate, step_of
 
 DEFAULT_MAX_CLIPS = 15
@@ -115,20 +115,27 @@ def _resolve_backend(backend: str, device: torch.device) -> str:
 def build_network(start_index: int, end_index: int, num_classes: int = 400,
                   layer_sizes=None, depth: Optional[int] = None, seed: int = 0,
                   ckpt_path: Optional[str] = None, arch: Optional[str] = None,
-                  midplanes: Optional[str] = None, bn_eps: Optional[float] = None):
+                  midplanes: Optional[str] = None, bn_eps: Optional[float] = None,
+                  tv_block: Optional[str] = None):
     """The module tree of layers [start_index, end_index], seeded at random or
     loaded from ``ckpt_path``. ``arch="reference"`` (default): the reference's
     tree and checkpoint format. ``arch="torchvision"``: torchvision's
     ``VideoResNet`` layout (``r2plus1d_18``, IG65M ``r2plus1d_34``); the
     mid-channel counts come from the checkpoint's tensor shapes when there is
     one, else from ``midplanes`` ("block", torchvision's rule, or "conv");
-    ``bn_eps`` is the BatchNorms' eps (a state dict does not carry it)."""
+    ``bn_eps`` is the BatchNorms' eps (a state dict does not carry it).
+    ``tv_block`` ("2plus1d" or "3d" = ``r3d_18``) comes from the checkpoint's
+    stem when there is one, else defaults to "2plus1d"; a value the file
+    contradicts raises."""
     arch = check_arch(arch)
     midplanes, bn_eps = check_midplanes(midplanes), check_bn_eps(bn_eps)
+    tv_block = check_tv_block(tv_block)
     sizes = normalize_layer_sizes(start_index, end_index, layer_sizes, depth)
     if arch == "reference":
         if midplanes is not None or bn_eps is not None:
             raise ValueError("midplanes / bn_eps belong to arch='torchvision'")
+        if tv_block is not None:
+            raise ValueError("tv_block belongs to arch='torchvision'")
         net = R2Plus1DLayerWrapper(start_index, end_index, num_classes, sizes)
         init_random_(net, seed)
         if ckpt_path:
@@ -140,10 +147,19 @@ def build_network(start_index: int, end_index: int, num_classes: int = 400,
     if ckpt_path:
         ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
         state = ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
+    found = tv_state_block(state)
+    if tv_block is not None and found is not None and found != tv_block:
+        raise ValueError("tv_block %r contradicts the checkpoint, whose stem.0.weight %s is "
+                         "tv_block %r's" % (tv_block, tuple(state["stem.0.weight"].shape), found))
+    tv_block = tv_block or found or "2plus1d"
+    if tv_block == "3d" and midplanes is not None:
+        raise ValueError("midplanes belongs to tv_block='2plus1d', got %r with tv_block='3d'"
+                         % (midplanes,))
     net = TVVideoResNet(start_index, end_index, num_classes, sizes,
-                        midplanes=midplanes or "block",
+                        midplanes=midplanes,
                         bn_eps=DEFAULT_BN_EPS if bn_eps is None else bn_eps,
-                        mids=tv_state_mids(state) if isinstance(state, dict) else None)
+                        mids=tv_state_mids(state) if isinstance(state, dict) else None,
+                        tv_block=tv_block)
     init_random_(net, seed)
     if state is not None:
         load_torchvision_state_dict(net, state)
@@ -154,16 +170,20 @@ def build_engine(device: torch.device, start_index=1, end_index=5, num_classes=4
                  layer_sizes=None, depth=None, backend="auto", bn_mode="eval", seed=0,
                  ckpt_path=None, max_clips=DEFAULT_MAX_CLIPS, use_graphs=True,
                  autotune=True, dtype=None, buckets=None,
-                 clip_length=DEFAULT_CLIP_LENGTH, arch=None, midplanes=None, bn_eps=None):
+                 clip_length=DEFAULT_CLIP_LENGTH, arch=None, midplanes=None, bn_eps=None,
+                 tv_block=None):
     clip_length = check_clip_length(clip_length)
     arch = check_arch(arch)
+    tv_block = check_tv_block(tv_block)
     backend = _resolve_backend(backend, device)
     if backend == "hip":
         # before any weight is built: a call of max_clips clips must fit the
-        # kernels' per-launch limits at this clip length
-        check_max_clips(max_clips, start_index, end_index, _dtype(dtype), clip_length, arch)
+        # kernels' per-launch limits at this clip length (a tree chosen from the
+        # checkpoint is bounded as "2plus1d", whose activations are the larger)
+        check_max_clips(max_clips, start_index, end_index, _dtype(dtype), clip_length, arch,
+                        tv_block or "2plus1d")
     net = build_network(start_index, end_index, num_classes, layer_sizes, depth, seed,
-                        ckpt_path, arch, midplanes, bn_eps)
+                        ckpt_path, arch, midplanes, bn_eps, tv_block)
     eng = R2P1DEngine(net, device, backend=backend, bn_mode=bn_mode, dtype=_dtype(dtype),
                       clip_length=clip_length)
     # batch-statistics BN is graphed for fp32 (per-video segments from a
@@ -198,11 +218,12 @@ class R2P1DRunner(RunnerModel):
                  warmup=3, use_graphs=True, autotune=True, dtype=None,
                  max_batch_videos=1, batch_wait_ms=0.0, bucket_step=None, lanes=1,
                  stream_priority=0, clip_length=DEFAULT_CLIP_LENGTH, arch=None,
-                 midplanes=None, bn_eps=None, **unused):
+                 midplanes=None, bn_eps=None, tv_block=None, **unused):
         super().__init__(device)
         self.clip_length = clip_length = check_clip_length(clip_length)
         self.arch = arch = check_arch(arch)
         midplanes, bn_eps = check_midplanes(midplanes), check_bn_eps(bn_eps)
+        self.tv_block = tv_block = check_tv_block(tv_block)
         if start_index < 1:
             raise ValueError("Wrong layer index for the starting layer! The start_index "
                              "(%d) should be more than or equal to 1." % start_index)
@@ -220,7 +241,7 @@ class R2P1DRunner(RunnerModel):
         self.engine = build_engine(device, start_index, end_index, num_classes,
                                    layer_sizes, depth, backend, bn_mode, seed, ckpt_path,
                                    self.max_clips, use_graphs, autotune, self.dtype, buckets,
-                                   clip_length, arch, midplanes, bn_eps)
+                                   clip_length, arch, midplanes, bn_eps, tv_block)
         # lanes > 1: that many graphed engines (own weights copy, BN buffers and
         # graph pool each; the same seed / checkpoint, so identical outputs) on
         # their own streams, calls rotating over them. One-video calls leave
@@ -235,7 +256,7 @@ class R2P1DRunner(RunnerModel):
             self._lane_engines.append(build_engine(
                 device, start_index, end_index, num_classes, layer_sizes, depth, backend,
                 bn_mode, seed, ckpt_path, self.max_clips, use_graphs, autotune, self.dtype,
-                buckets, clip_length, arch, midplanes, bn_eps))
+                buckets, clip_length, arch, midplanes, bn_eps, tv_block))
         # lane streams at DEFAULT priority, not the runner's (runner.py passes
         # the queue group's, e.g. the high-priority 15-clip replica's): the
         # round-4 advice asked for the runner's; measured interleaved, it costs
@@ -728,7 +749,7 @@ class R2P1DSingleStep(RunnerModel):
                  use_graphs=True, autotune=True, dtype=None, decoder_args=None,
                  clip_length=DEFAULT_CLIP_LENGTH, crop=None, filter=None, frame_step=1,
                  fps=None, placement="random", arch=None, midplanes=None, bn_eps=None,
-                 **unused):
+                 tv_block=None, **unused):
         super().__init__(device)
         clip_length = check_clip_length(clip_length)
         self.loader = R2P1DLoader(device, num_clips_population, num_clips_weights,
@@ -742,7 +763,7 @@ class R2P1DSingleStep(RunnerModel):
                                   max_clips=max_clips, warmup=warmup,
                                   use_graphs=use_graphs, autotune=autotune, dtype=dtype,
                                   clip_length=clip_length, arch=arch, midplanes=midplanes,
-                                  bn_eps=bn_eps)
+                                  bn_eps=bn_eps, tv_block=tv_block)
 
     @property
     def range_guarded(self) -> bool:

@@ -315,6 +315,7 @@ def load_reference_state_dict(model: R2Plus1DLayerWrapper, state_dict,
 # ---------------------------------------------------------------------------
 ARCHS = ("reference", "torchvision")
 MIDPLANES_RULES = ("block", "conv")
+TV_BLOCKS = ("2plus1d", "3d")
 TV_STEM_MID = 45
 DEFAULT_BN_EPS = 1e-5
 
@@ -338,6 +339,27 @@ def check_midplanes(midplanes, key: str = "midplanes") -> Optional[str]:
         raise ValueError("%s must be one of %s, got %r"
                          % (key, ", ".join(repr(a) for a in MIDPLANES_RULES), midplanes))
     return midplanes
+
+
+def check_tv_block(tv_block, key: str = "tv_block") -> Optional[str]:
+    """``tv_block`` ("2plus1d" = r2plus1d_*, "3d" = r3d_18, or None = from the
+    checkpoint, else "2plus1d"); ValueError (naming ``key``) otherwise."""
+    if tv_block is None:
+        return None
+    if not isinstance(tv_block, str) or tv_block not in TV_BLOCKS:
+        raise ValueError("%s must be one of %s, got %r"
+                         % (key, ", ".join(repr(a) for a in TV_BLOCKS), tv_block))
+    return tv_block
+
+
+def tv_state_block(state_dict) -> Optional[str]:
+    """The block type a torchvision-layout state dict was saved from, read from
+    its stem conv: 5-D with a temporal extent of 3 (3x7x7) is ``r3d_18``'s
+    ("3d"), 1x7x7 the (2+1)D stem's; None when it holds no stem."""
+    w = state_dict.get("stem.0.weight") if isinstance(state_dict, dict) else None
+    if w is None or not hasattr(w, "shape") or len(w.shape) != 5:
+        return None
+    return "3d" if int(w.shape[2]) == 3 else "2plus1d"
 
 
 def check_bn_eps(bn_eps, key: str = "bn_eps") -> Optional[float]:
@@ -420,17 +442,47 @@ class TVBasicBlock(nn.Module):
         return self.relu(out + res)
 
 
+class TVBasicBlock3D(nn.Module):
+    """torchvision's video ``BasicBlock`` over ``Conv3DSimple`` (r3d_18): two
+    3x3x3 convs, the first with stride (s, s, s)."""
+
+    def __init__(self, in_planes, planes, stride=1, eps=DEFAULT_BN_EPS):
+        super().__init__()
+        self.conv1 = nn.Sequential(
+            nn.Conv3d(in_planes, planes, 3, stride=(stride, stride, stride), padding=1,
+                      bias=False),
+            nn.BatchNorm3d(planes, eps=eps), nn.ReLU())
+        self.conv2 = nn.Sequential(
+            nn.Conv3d(planes, planes, 3, stride=1, padding=1, bias=False),
+            nn.BatchNorm3d(planes, eps=eps))
+        self.relu = nn.ReLU()
+        self.downsample = None
+        if stride != 1 or in_planes != planes:
+            self.downsample = nn.Sequential(
+                nn.Conv3d(in_planes, planes, 1, stride=(stride, stride, stride), bias=False),
+                nn.BatchNorm3d(planes, eps=eps))
+
+    def forward(self, x):
+        out = self.conv2(self.conv1(x))
+        res = x if self.downsample is None else self.downsample(x)
+        return self.relu(out + res)
+
+
 class TVVideoResNet(nn.Module):
-    """Layers [start_idx, end_idx] of torchvision's R(2+1)D ``VideoResNet``;
-    the state-dict keys of the built range are torchvision's own. ``mids``
+    """Layers [start_idx, end_idx] of torchvision's ``VideoResNet``; the
+    state-dict keys of the built range are torchvision's own.
+    ``tv_block="2plus1d"`` is R(2+1)D (``r2plus1d_18``, IG65M-34): ``mids``
     names a (2+1)D conv's mid-channel count (``tv_block_mids`` /
-    ``tv_state_mids``); convs it does not name follow ``midplanes``."""
+    ``tv_state_mids``); convs it does not name follow ``midplanes`` (None =
+    "block"). ``tv_block="3d"`` is ``r3d_18``: a 3x7x7 stem and blocks of two
+    3x3x3 convs, with the same boundary geometry; ``midplanes`` does not apply
+    to it."""
 
     arch = "torchvision"
 
     def __init__(self, start_idx, end_idx, num_classes, layer_sizes: Dict[int, int],
-                 midplanes: str = "block", bn_eps: float = DEFAULT_BN_EPS,
-                 mids: Optional[Dict[str, int]] = None):
+                 midplanes: Optional[str] = None, bn_eps: float = DEFAULT_BN_EPS,
+                 mids: Optional[Dict[str, int]] = None, tv_block: str = "2plus1d"):
         super().__init__()
         if not 1 <= start_idx <= end_idx <= 5:
             raise ValueError("layer range must satisfy 1 <= start <= end <= 5, "
@@ -438,6 +490,29 @@ class TVVideoResNet(nn.Module):
         self.start_idx, self.end_idx = start_idx, end_idx
         self.num_classes = num_classes
         self.bn_eps = float(bn_eps)
+        self.tv_block = check_tv_block(tv_block) or "2plus1d"
+        if self.tv_block == "3d":
+            if midplanes is not None:
+                raise ValueError("midplanes belongs to tv_block='2plus1d': the 3x3x3 convs of "
+                                 "tv_block='3d' have no mid channels, got %r" % (midplanes,))
+            self.mids = {}
+            for idx in range(start_idx, end_idx + 1):
+                if idx == 1:
+                    self.stem = nn.Sequential(
+                        nn.Conv3d(3, 64, (3, 7, 7), stride=(1, 2, 2), padding=(1, 3, 3),
+                                  bias=False),
+                        nn.BatchNorm3d(64, eps=bn_eps), nn.ReLU())
+                    continue
+                cin, planes = LAYER_CHANNELS[idx]
+                setattr(self, "layer%d" % (idx - 1), nn.Sequential(*[
+                    TVBasicBlock3D(cin if j == 0 else planes, planes,
+                                   stride=2 if (j == 0 and idx > 2) else 1, eps=bn_eps)
+                    for j in range(layer_sizes[idx])]))
+            if end_idx == 5:
+                self.avgpool = nn.AdaptiveAvgPool3d(1)
+                self.fc = nn.Linear(512, num_classes)
+            return
+        midplanes = midplanes or "block"
         table = tv_block_mids({i: layer_sizes[i] for i in range(max(2, start_idx), end_idx + 1)},
                               midplanes)
         table.update({k: int(v) for k, v in (mids or {}).items() if k in table})
@@ -484,7 +559,7 @@ def _unwrap_state(state):
 
 
 def load_torchvision_state_dict(model: TVVideoResNet, state, strict: bool = True):
-    """Load a torchvision-layout R(2+1)D state dict (raw, or wrapped as
+    """Load a torchvision-layout R(2+1)D or r3d_18 state dict (raw, or wrapped as
     ``{"state_dict": ...}``) restricted to the range ``model`` builds;
     ``num_batches_tracked`` entries are accepted. Raises a ValueError naming
     the first missing key, the first unexpected key (within the built range's

@@ -171,6 +171,15 @@ H3W_BASE = 1460
 # V = B^T d B is up to 4x the input: split after scaling by 2^4 keeps inputs
 # up to 2^10 in the fp16 range, as the direct kernels' 2^6
 H3W_IN_LOG2 = 4
+# volume-band h3 kernel (csrc/conv_h3v.hip conv_h3v_kernel): 3x3x3 stride 1 pad 1
+# with Cin_p % 32 == 0 and T >= 2, the h3 direct weights, variant H3V_BASE + v of
+# rnb_conv_h3v_launch
+H3V_BASE = 1480
+# measured out of the autotune set (profiles/r3d_h3v.txt): on 56 x 56 frames the
+# family loses to the h3 direct configs at 128 and at 16 clips (3.06 vs 2.18 ms,
+# 0.37 vs 0.30 ms), and variant 0, built for them, is the best variant nowhere
+H3V_MAX_W = 28
+H3V_UNOFFERED = (0,)
 # activations are split after scaling by 2^H3_IN_LOG2: fp16 lo parts stay
 # normal for |a| >= 2^-9 and inputs up to 2^10 stay in the fp16 range
 H3_IN_LOG2 = 6
@@ -183,7 +192,17 @@ def is_h3(cid: int) -> bool:
     return ((H3D_BASE <= cid < H3D_BASE + len(kernels().h3_configs))
             or H3K_BASE <= cid < H3K_BASE + len(H3K_CONFIGS) or is_h3r(cid)
             or is_h3t(cid) or is_h3u(cid) or is_h3s(cid) or is_h3stem(cid) or is_h3p(cid)
-            or is_h3w(cid))
+            or is_h3w(cid) or is_h3v(cid))
+
+
+def is_h3v(cid: int) -> bool:
+    from .native import kernels
+    return H3V_BASE <= cid < H3V_BASE + kernels().h3v_variants
+
+
+def h3v_enabled() -> bool:
+    """RNB_H3V=0 leaves the volume-band h3 kernel out of the autotune set."""
+    return os.environ.get("RNB_H3V", "1") != "0"
 
 
 def is_h3w(cid: int) -> bool:
@@ -757,6 +776,9 @@ class ConvLayerF32:
             if self.h3stem_ok(x_shape):
                 c += [H3STEM_BASE + i for i in range(kernels().h3stem_variants)
                       if self.h3stem_fits(i, x_shape)]
+            if self.h3v_ok(x_shape) and h3v_enabled():
+                c += [H3V_BASE + i for i in range(kernels().h3v_variants)
+                      if self.h3v_fits(i, x_shape)]
             if self.h3t_ok(x_shape):
                 c += [H3T_BASE + i for i in range(kernels().h3t_variants)
                       if self.h3t_fits(i, x_shape)]
@@ -1010,6 +1032,41 @@ class ConvLayerF32:
             return False
         return not efficient or 2 * rows * W >= kernels().conv_h3r_pixels(variant)
 
+    def h3v_ok(self, x_shape=None) -> bool:
+        """The volume-band h3 kernel takes 3x3x3 stride-1 pad-1 convs over
+        32-channel chunks of clips of at least 2 frames."""
+        g = self.geom
+        return (tuple(g.kernel) == (3, 3, 3) and tuple(g.stride) == (1, 1, 1)
+                and tuple(g.padding) == (1, 1, 1) and g.cin_p % 32 == 0
+                and (x_shape is None or x_shape[1] >= 2))
+
+    def h3v_fits(self, variant: int, x_shape, efficient: bool = True) -> bool:
+        """Whether variant ``variant`` has a box for clips of T x H x W (the
+        launch's rule, rnb_conv_h3v_box), and (when ``efficient``) its box uses
+        at least half of the block's pixels and the shape and variant are not
+        among those measured slower than the generic h3 configs everywhere
+        (``H3V_MAX_W``, ``H3V_UNOFFERED``)."""
+        if x_shape is None:
+            return True
+        from .native import kernels
+        _, T, H, W, _ = x_shape
+        tf, rows = kernels().conv_h3v_box(variant, T, H, W)
+        if rows < 1:
+            return False
+        if not efficient:
+            return True
+        if W > H3V_MAX_W or variant in H3V_UNOFFERED:
+            return False
+        return 2 * tf * rows * W >= kernels().conv_h3v_pixels(variant)
+
+    def h3v_buffers(self):
+        """(split weights, bias, in_scale, out_scale) of the volume-band kernel:
+        it streams weight step tap * Cin_p / 32 + chunk with taps in (dt, dh,
+        dw) order, the K order of the h3 direct kernel (Cin_p % 32 == 0), so
+        these are ``h3d_buffers()``: scale ``h3_weight_scale_log2``, input
+        scale 2^H3_IN_LOG2."""
+        return self.h3d_buffers()
+
     def h3stem_ok(self, x_shape=None) -> bool:
         """The stem h3 kernel takes 1x7x7 stride-(1, 2, 2) pad-(0, 3, 3) convs of
         a 4-channel (3 + pad) input."""
@@ -1083,7 +1140,7 @@ class ConvLayerF32:
 
     def affine_ok(self, cid: int, x_shape) -> bool:
         """Whether config ``cid`` can apply the input's BN + ReLU on load."""
-        if is_h3s(cid) or is_h3stem(cid):
+        if is_h3s(cid) or is_h3stem(cid) or is_h3v(cid):
             return False
         if (cid in WINO_TEMPORAL or is_h3r(cid) or is_h3t(cid) or is_h3u(cid)
                 or is_h3p(cid) or is_h3w(cid)):
@@ -1188,6 +1245,16 @@ class ConvLayerF32:
                                out_stats[0].shape[2])
                 else:
                     k.conv_h3s(p, cid - H3S_BASE, stream.cuda_stream, s_in, s_out)
+            elif is_h3v(cid):
+                if in_affine is not None:
+                    raise ValueError("%s: the volume-band kernel takes no input BN" % self.name)
+                _, _, s_in, s_out = self.h3v_buffers()
+                if out_stats is not None:
+                    k.conv_h3v(p, cid - H3V_BASE, stream.cuda_stream, s_in, s_out,
+                               out_stats[0].data_ptr(), out_stats[1].data_ptr() + 4 * n0,
+                               out_stats[0].shape[2])
+                else:
+                    k.conv_h3v(p, cid - H3V_BASE, stream.cuda_stream, s_in, s_out)
             elif is_h3r(cid):
                 _, _, s_in, s_out = self.h3d_buffers()
                 aff = ((in_affine[0].data_ptr(), in_affine[1].data_ptr() + 4 * n0)
@@ -1322,7 +1389,7 @@ class ConvLayerF32:
         shift rows itself from the producer's sums (``kernels().bn_aff_arm``)."""
         cid = self.config_for(x_shape)
         if not is_h3(cid) or is_h3w(cid) or is_h3t(cid) or is_h3u(cid) or is_h3p(cid) \
-                or is_h3stem(cid) or is_h3s(cid) or is_h3r(cid):
+                or is_h3stem(cid) or is_h3s(cid) or is_h3r(cid) or is_h3v(cid):
             return False
         return self.affine_ok(cid, x_shape)
 

@@ -16,7 +16,7 @@ import ctypes
 import os
 import struct
 import threading
-from typing import Optional
+from typing import Optional, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 NATIVE_DIR = os.path.join(os.path.dirname(_HERE), "_native")
@@ -414,6 +414,18 @@ class Kernels:
         lib.rnb_conv_h3r_stack_small.restype = None
         lib.rnb_conv_h3r_occupancy.argtypes = [ctypes.c_int] * 2
         lib.rnb_conv_h3r_occupancy.restype = ctypes.c_int
+        lib.rnb_conv_h3v_launch.argtypes = [ctypes.POINTER(ConvParams), ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_int, ctypes.c_float, ctypes.c_float]
+        lib.rnb_conv_h3v_launch.restype = ctypes.c_int
+        lib.rnb_conv_h3v_box.argtypes = [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int)]
+        lib.rnb_conv_h3v_box.restype = ctypes.c_int
+        lib.rnb_conv_h3v_pixels.argtypes = [ctypes.c_int]
+        lib.rnb_conv_h3v_pixels.restype = ctypes.c_int
+        lib.rnb_conv_h3v_blocks.argtypes = [ctypes.c_int] * 6
+        lib.rnb_conv_h3v_blocks.restype = ctypes.c_longlong
+        lib.rnb_conv_h3v_occupancy.argtypes = [ctypes.c_int]
+        lib.rnb_conv_h3v_occupancy.restype = ctypes.c_int
         lib.rnb_conv_h3t_launch.argtypes = lib.rnb_conv_h3r_launch.argtypes
         lib.rnb_conv_h3t_launch.restype = ctypes.c_int
         lib.rnb_conv_h3t_pixels.argtypes = [ctypes.c_int, ctypes.c_int]
@@ -504,6 +516,7 @@ class Kernels:
         self.x6r_variants = lib.rnb_conv_x6r_num_variants()
         self.h3r_variants = lib.rnb_conv_h3r_num_variants()
         self.h3t_variants = lib.rnb_conv_h3t_num_variants()
+        self.h3v_variants = lib.rnb_conv_h3v_num_variants()
         self.h3w_variants = lib.rnb_conv_h3w_num_variants()
         self.h3u_variants = self.exp.rnb_conv_h3u_num_variants() if self.exp else 0
         self.h3s_variants = self.exp.rnb_conv_h3s_num_variants() if self.exp else 0
@@ -620,6 +633,34 @@ class Kernels:
         """Blocks per CU of the variant's kernel (``stacked``: the form whose
         bands cross frames); needs a GPU."""
         return self.lib.rnb_conv_h3r_occupancy(variant, 1 if stacked else 0)
+
+    def conv_h3v(self, params: ConvParams, variant: int, stream: int, in_scale: float,
+                 out_scale: float, sums: int = 0, clip_seg: int = 0, stats_c: int = 0) -> None:
+        """h3 volume-band conv (3x3x3 stride 1 pad 1, Cin_p % 32 == 0, T >= 2);
+        the arguments as ``conv_h3`` without the input BN."""
+        _check(self.lib.rnb_conv_h3v_launch(ctypes.byref(params), variant, stream,
+                                            sums or None, clip_seg or None, stats_c, in_scale,
+                                            out_scale),
+               "conv_h3v (variant %d)" % variant)
+
+    def conv_h3v_box(self, variant: int, T: int, H: int, W: int) -> Tuple[int, int]:
+        """(output frames, output rows) of volume-band variant ``variant``'s box
+        on T x H x W clips, (0, 0) where it cannot run them: the launch's rule."""
+        tf = ctypes.c_int(0)
+        rows = self.lib.rnb_conv_h3v_box(variant, T, H, W, ctypes.byref(tf))
+        return (tf.value, rows) if rows > 0 else (0, 0)
+
+    def conv_h3v_pixels(self, variant: int) -> int:
+        """Output pixels per block of volume-band variant ``variant``."""
+        return self.lib.rnb_conv_h3v_pixels(variant)
+
+    def conv_h3v_blocks(self, variant: int, N: int, T: int, H: int, W: int, cout_p: int) -> int:
+        """Grid size of a volume-band launch (0: the variant cannot run the shape)."""
+        return self.lib.rnb_conv_h3v_blocks(variant, N, T, H, W, cout_p)
+
+    def conv_h3v_occupancy(self, variant: int) -> int:
+        """Blocks per CU of the variant's kernel; needs a GPU."""
+        return self.lib.rnb_conv_h3v_occupancy(variant)
 
     def conv_h3t(self, params: ConvParams, variant: int, stream: int, in_scale: float,
                  out_scale: float, sums: int = 0, clip_seg: int = 0, stats_c: int = 0,
