@@ -16,6 +16,7 @@ CPU execution path.
 from __future__ import annotations
 
 import math
+import os
 import threading
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
@@ -31,10 +32,32 @@ TEMPORAL = 101      # config id of the register-direct 3x1x1 kernel (conv_tempor
 HALO4 = 102         # halo kernel with 64-pixel waves (4 MFMA pixel sub-tiles per wave)
 HALO4B = 103        # 64-pixel waves over 448-pixel tiles (7 waves, 1 block per CU)
 HALOWS = 104        # weight-stationary halo kernel (conv_halo_ws.hip: Cin 64, Cout 128..144)
+VOL = 105           # volume-halo 3x3x3 stride-1 kernel (conv_vol.hip), 224-pixel boxes
+VOLS = 106          # volume-halo kernel with 128-pixel boxes (7 x 7 frames whole, 2 blocks / CU)
+VOLN = 107          # VOL with a 64-channel tile (offered to convs of up to 64 output channels)
 SPECIAL_NAMES = {HALO: "halo", TEMPORAL: "temporal", HALO4: "halo4", HALO4B: "halo4b",
-                 HALOWS: "halows"}
+                 HALOWS: "halows", VOL: "vol", VOLS: "vols", VOLN: "voln"}
 HALO_VARIANT = {HALO: 2, HALO4: 4, HALO4B: 5, HALOWS: 6}   # variant of rnb_halo_launch_v
+VOL_VARIANT = {VOL: 0, VOLS: 1, VOLN: 2}                   # variant of rnb_vol_launch
 LDS_LIMIT = 160 * 1024
+KTAB_MAX = 640      # K_pad / 8 limit of the 3-stage conv_igemm configs (conv_igemm.hip)
+
+
+# The volume-halo ids are a conv's default (special_candidates()[0]) on frames
+# up to this width; wider frames get them as autotune candidates only.
+# Measured at 128 clips against the best generic config (profiles/
+# r3d_vol_bf16.txt): 128->128 on 4x28x28 vol 0.339 ms against 0.370; 256->256 on
+# 2x14x14 vols 0.150, vol 0.154 against 0.175; 512->512 on 2x7x7 vols 0.145
+# against 0.178 (vol 0.236); 64->64 on 8x56x56 voln 1.228, vol 1.594 against
+# 0.856. At 16 clips the 14- and 7-wide launches fill half the CUs or fewer
+# and lose by 3 to 10 %, which autotune decides per shape.
+VOL_DEFAULT_MAX_W = 28
+VOLS_FIRST_MAX_W = 14      # up to this width the 128-pixel-box variant is the first
+
+
+def vol_enabled() -> bool:
+    """RNB_VOL=0 leaves the volume-halo kernel family out."""
+    return os.environ.get("RNB_VOL", "1") != "0"
 
 
 _NUM_CUS: Dict[int, int] = {}
@@ -157,6 +180,7 @@ class ConvLayer:
         self.use_halo = True      # allow the halo-tiled kernel for 1x3x3 stride-1 convs
         self.use_temporal = True  # allow the register-direct kernel for 3x1x1 stride-1 convs
         self.use_halo_ws = True   # allow the weight-stationary halo kernel (conv2 spatial)
+        self.use_vol = vol_enabled()   # allow the volume-halo kernel for 3x3x3 stride-1 convs
 
     # ------------------------------------------------------------------
     def out_shape(self, x_shape) -> Tuple[int, int, int, int, int]:
@@ -266,10 +290,36 @@ class ConvLayer:
         nb = kernels().halo_lds_bytes(N * T, H, W, g.cin_p, HALO_VARIANT[HALOWS])
         return 0 < nb <= LDS_LIMIT
 
+    def vol_candidates(self, x_shape):
+        """Volume-halo ids (conv_vol.hip) that can run this input: 3x3x3 /
+        stride 1 / pad 1 with Cin_p % 64 == 0 over T >= 2 frames, for every
+        variant whose box and patch fit (rnb_vol_box, LDS_LIMIT)."""
+        g = self.geom
+        if not (g.kernel == (3, 3, 3) and g.stride == (1, 1, 1) and g.padding == (1, 1, 1)
+                and g.cin_p >= 64 and g.cin_p % 64 == 0 and self.use_vol):
+            return []
+        N, T, H, W, _ = x_shape
+        key = ("vol", T, H, W)
+        ids = self._config.get(key)
+        if ids is None:
+            from .native import kernels
+            ids = tuple(cid for cid, v in VOL_VARIANT.items()
+                        if 0 < kernels().vol_lds_bytes(v, T, H, W, g.cin_p) <= LDS_LIMIT
+                        and (cid != VOLN or g.cout_p <= 64))
+            self._config[key] = ids
+        return list(ids)
+
+    def vol_eligible(self, x_shape) -> bool:
+        return bool(self.vol_candidates(x_shape))
+
     def special_candidates(self, x_shape):
         """Shape-specialised kernels (config ids >= 100) that can run this input.
         The first entry is the default when the layer is not autotuned."""
         out = []
+        if x_shape[3] <= VOL_DEFAULT_MAX_W:
+            # elsewhere the family is an autotune candidate only (autotune)
+            first = VOLS if x_shape[3] <= VOLS_FIRST_MAX_W else VOL
+            out += sorted(self.vol_candidates(x_shape), key=lambda c: c != first)
         if self.halo_ws_eligible(x_shape):
             out.append(HALOWS)
         if self.halo_eligible(x_shape):
@@ -300,6 +350,24 @@ class ConvLayer:
         p.w_rows = self.wmat.shape[0]
         return p
 
+    def vol_params(self, x, y, residual):
+        from .native import VolParams
+        g = self.geom
+        N, T, H, W, C = x.shape
+        if C != g.cin_p:
+            raise ValueError("%s: input has %d channels, expected %d" % (self.name, C, g.cin_p))
+        p = VolParams()
+        p.x, p.w, p.bias = x.data_ptr(), self.wmat.data_ptr(), self.bias.data_ptr()
+        p.res = residual.data_ptr() if residual is not None else None
+        p.y = y.data_ptr()
+        p.N, p.T, p.H, p.W, p.Cin = N, T, H, W, C
+        p.Cout_p, p.y_stride = g.cout_p, y.shape[-1]
+        p.res_stride = residual.shape[-1] if residual is not None else 0
+        p.K_pad, p.M = g.k_pad, N * T * H * W
+        p.relu = 1 if self.relu else 0
+        p.w_rows = self.wmat.shape[0]
+        return p
+
     def halo_params(self, x, y, residual):
         from .native import HaloParams
         g = self.geom
@@ -316,11 +384,22 @@ class ConvLayer:
         p.w_rows = self.wmat.shape[0]
         return p
 
+    def generic_candidates(self):
+        """conv_igemm config ids that can run this layer: the 3-stage kernels
+        hold the K-chunk table in LDS (KTAB_MAX entries; r3d_18's 3x3x3 convs
+        over 256 and 512 channels pass it)."""
+        from .native import kernels
+        big = self.geom.k_pad // 8 > KTAB_MAX
+        return [cid for cid, st in enumerate(kernels().stages) if not (big and st == 3)]
+
     def heuristic_config(self, M: int) -> int:
         from .native import kernels
         best, best_cost = 0, None
         cp = self.geom.cout_p
+        runnable = set(self.generic_candidates())
         for cid, (pt, ct) in enumerate(kernels().configs):
+            if cid not in runnable:
+                continue
             nblk = math.ceil(M / pt) * math.ceil(cp / ct)
             work = math.ceil(M / pt) * pt * math.ceil(cp / ct) * ct
             # per-element overhead of small tiles (operand re-reads) and the
@@ -348,12 +427,11 @@ class ConvLayer:
     def autotune(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None,
                  reps: int = 5) -> int:
         """Time every tile config on this input shape; keep the fastest."""
-        from .native import kernels
-        kern = kernels()
         y = torch.empty(self.out_shape(x.shape), dtype=torch.bfloat16, device=x.device)
         stream = torch.cuda.current_stream(x.device)
         best, best_t = None, None
-        cands = list(range(len(kern.configs))) + self.special_candidates(x.shape)
+        cands = self.generic_candidates() + self.special_candidates(x.shape)
+        cands += [c for c in self.vol_candidates(x.shape) if c not in cands]
         for cid in cands:
             p = self.params(x, y, residual)
             self._launch(p, cid, x, y, residual, stream)    # warm
@@ -375,6 +453,12 @@ class ConvLayer:
         if cid in HALO_VARIANT:
             kernels().halo(self.halo_params(x, y, residual), stream.cuda_stream,
                            variant=HALO_VARIANT[cid])
+        elif cid in VOL_VARIANT:
+            if (self.geom.kernel, self.geom.stride, self.geom.padding) != \
+                    ((3, 3, 3), (1, 1, 1), (1, 1, 1)) or y.shape[:4] != x.shape[:4]:
+                raise ValueError("%s: config %d serves 3x3x3 stride-1 pad-1 convs" %
+                                 (self.name, cid))
+            kernels().vol(self.vol_params(x, y, residual), VOL_VARIANT[cid], stream.cuda_stream)
         elif cid == TEMPORAL:
             kernels().temporal(self.temporal_params(x, y, residual), num_cus(x.device), 0,
                                stream.cuda_stream)

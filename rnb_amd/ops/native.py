@@ -132,6 +132,20 @@ class HaloParams(ctypes.Structure):
     ]
 
 
+class VolParams(ctypes.Structure):
+    """Mirror of ``struct VolParams`` in csrc/conv_vol.hip."""
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+        ("res", ctypes.c_void_p), ("y", ctypes.c_void_p),
+        ("N", ctypes.c_int), ("T", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+        ("Cin", ctypes.c_int), ("Cout_p", ctypes.c_int), ("y_stride", ctypes.c_int),
+        ("res_stride", ctypes.c_int), ("K_pad", ctypes.c_int), ("M", ctypes.c_int),
+        ("relu", ctypes.c_int), ("w_rows", ctypes.c_int), ("n_ctiles", ctypes.c_int),
+        ("R", ctypes.c_int), ("bands", ctypes.c_int), ("tpairs", ctypes.c_int),
+        ("np", ctypes.c_int), ("x_bytes", ctypes.c_uint32),
+    ]
+
+
 class Conv21Params(ctypes.Structure):
     """Mirror of ``struct Conv21Params`` in csrc/conv21.hip."""
     _fields_ = [
@@ -345,6 +359,13 @@ class Kernels:
                                           ctypes.c_void_p]
         lib.rnb_halo_launch_v.restype = ctypes.c_int
         lib.rnb_halo_lds_bytes_v.argtypes = [ctypes.c_int] * 5
+        lib.rnb_vol_launch.argtypes = [ctypes.POINTER(VolParams), ctypes.c_int, ctypes.c_void_p]
+        lib.rnb_vol_launch.restype = ctypes.c_int
+        lib.rnb_vol_box.argtypes = [ctypes.c_int] * 4
+        lib.rnb_vol_lds_bytes.argtypes = [ctypes.c_int] * 5
+        lib.rnb_vol_occupancy.argtypes = [ctypes.c_int] * 2
+        if lib.rnb_vol_params_size() != ctypes.sizeof(VolParams):
+            raise NativeUnavailable("VolParams layout mismatch: rebuild")
         lib.rnb_temporal_launch.argtypes = [ctypes.POINTER(TemporalParams), ctypes.c_int,
                                             ctypes.c_int, ctypes.c_void_p]
         lib.rnb_temporal_launch.restype = ctypes.c_int
@@ -816,6 +837,24 @@ class Kernels:
         """variant (csrc/conv_halo.hip kHalo): 2 = 32-pixel waves, 4 = 64-pixel
         waves, 5 = 64-pixel waves over 448-pixel tiles."""
         _check(self.lib.rnb_halo_launch_v(ctypes.byref(params), variant, stream), "conv_halo")
+
+    def vol(self, params: VolParams, variant: int, stream: int) -> None:
+        """bf16 volume-halo 3x3x3 stride-1 conv (csrc/conv_vol.hip kVol): variant
+        0 = 224-pixel boxes, 7 waves; 1 = 128-pixel boxes, 4 waves; 2 = variant 0
+        with a 64-channel tile."""
+        _check(self.lib.rnb_vol_launch(ctypes.byref(params), variant, stream),
+               "conv_vol (variant %d)" % variant)
+
+    def vol_box(self, variant: int, T: int, H: int, W: int) -> int:
+        """Output rows of the variant's box on T x H x W clips (0: cannot run)."""
+        return self.lib.rnb_vol_box(variant, T, H, W)
+
+    def vol_lds_bytes(self, variant: int, T: int, H: int, W: int, cin: int) -> int:
+        return self.lib.rnb_vol_lds_bytes(variant, T, H, W, cin)
+
+    def vol_occupancy(self, variant: int, lds: int) -> int:
+        """Blocks per CU of the variant's kernel at ``lds`` bytes; needs a GPU."""
+        return self.lib.rnb_vol_occupancy(variant, lds)
 
     def temporal(self, params: TemporalParams, num_cus: int, blocks_per_cu: int,
                  stream: int) -> None:
