@@ -35,8 +35,9 @@ HALOWS = 104        # weight-stationary halo kernel (conv_halo_ws.hip: Cin 64, C
 VOL = 105           # volume-halo 3x3x3 stride-1 kernel (conv_vol.hip), 224-pixel boxes
 VOLS = 106          # volume-halo kernel with 128-pixel boxes (7 x 7 frames whole, 2 blocks / CU)
 VOLN = 107          # VOL with a 64-channel tile (offered to convs of up to 64 output channels)
+STEM3D = 108        # patch-staged 3x7x7 stride-(1,2,2) kernel over <= 4 channels (conv_stem3d.hip)
 SPECIAL_NAMES = {HALO: "halo", TEMPORAL: "temporal", HALO4: "halo4", HALO4B: "halo4b",
-                 HALOWS: "halows", VOL: "vol", VOLS: "vols", VOLN: "voln"}
+                 HALOWS: "halows", VOL: "vol", VOLS: "vols", VOLN: "voln", STEM3D: "stem3d"}
 HALO_VARIANT = {HALO: 2, HALO4: 4, HALO4B: 5, HALOWS: 6}   # variant of rnb_halo_launch_v
 VOL_VARIANT = {VOL: 0, VOLS: 1, VOLN: 2}                   # variant of rnb_vol_launch
 LDS_LIMIT = 160 * 1024
@@ -58,6 +59,11 @@ VOLS_FIRST_MAX_W = 14      # up to this width the 128-pixel-box variant is the f
 def vol_enabled() -> bool:
     """RNB_VOL=0 leaves the volume-halo kernel family out."""
     return os.environ.get("RNB_VOL", "1") != "0"
+
+
+def stem3d_enabled() -> bool:
+    """RNB_STEM3D=0 leaves the patch-staged 3x7x7 stem kernel out."""
+    return os.environ.get("RNB_STEM3D", "1") != "0"
 
 
 _NUM_CUS: Dict[int, int] = {}
@@ -181,6 +187,9 @@ class ConvLayer:
         self.use_temporal = True  # allow the register-direct kernel for 3x1x1 stride-1 convs
         self.use_halo_ws = True   # allow the weight-stationary halo kernel (conv2 spatial)
         self.use_vol = vol_enabled()   # allow the volume-halo kernel for 3x3x3 stride-1 convs
+        self.use_stem3d = stem3d_enabled()   # allow the patch-staged kernel for 3x7x7 stems
+        self.stem3d_grid = 0      # blocks of the stem3d kernel's persistent grid (0: one per CU)
+        self._stem3d_w: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------
     def out_shape(self, x_shape) -> Tuple[int, int, int, int, int]:
@@ -312,10 +321,59 @@ class ConvLayer:
     def vol_eligible(self, x_shape) -> bool:
         return bool(self.vol_candidates(x_shape))
 
+    def stem3d_candidates(self, x_shape):
+        """[STEM3D] if conv_stem3d.hip can run this input: 3x7x7 / stride
+        (1,2,2) / pad (1,3,3) over at most 4 input channels to Cout_p <= 64, a
+        multiple of 16, with a box whose patch fits LDS next to the weights."""
+        g = self.geom
+        if not (g.kernel == (3, 7, 7) and g.stride == (1, 2, 2) and g.padding == (1, 3, 3)
+                and g.cin <= 4 and g.cin_p == 8 and g.cout_p <= 64 and g.cout_p % 16 == 0
+                and self.use_stem3d):
+            return []
+        N, T, H, W, _ = x_shape
+        key = ("stem3d", T, H, W)
+        ok = self._config.get(key)
+        if ok is None:
+            from .native import kernels
+            ok = self._config[key] = 0 < kernels().stem3d_lds_bytes(T, H, W, g.cout_p) <= LDS_LIMIT
+        return [STEM3D] if ok else []
+
+    def stem3d_weight(self) -> torch.Tensor:
+        """The weight as conv_stem3d.hip reads it, built from ``wmat`` on first
+        use: [Cout_p rows in wmat's paired order][21 (dt, dy) steps][32] bf16,
+        k = 4 * dx + c within a step, zero for dx = 7 and c = 3 when cin = 3."""
+        if self._stem3d_w is None:
+            g = self.geom
+            w = self.wmat[:g.cout_p, :g.k_total].reshape(g.cout_p, 21, 7, g.cin_p)[..., :4]
+            self._stem3d_w = F.pad(w, (0, 0, 0, 1)).reshape(g.cout_p, 21, 32).contiguous()
+        return self._stem3d_w
+
+    def stem3d_params(self, x, y, residual):
+        from .native import Stem3dParams
+        g = self.geom
+        N, T, H, W, C = x.shape
+        if C != g.cin_p:
+            raise ValueError("%s: input has %d channels, expected %d" % (self.name, C, g.cin_p))
+        p = Stem3dParams()
+        p.x, p.w, p.bias = x.data_ptr(), self.stem3d_weight().data_ptr(), self.bias.data_ptr()
+        p.res = residual.data_ptr() if residual is not None else None
+        p.y = y.data_ptr()
+        p.N, p.T, p.H, p.W = N, T, H, W
+        p.Ho, p.Wo = y.shape[2], y.shape[3]
+        p.Cout_p, p.y_stride = g.cout_p, y.shape[-1]
+        p.res_stride = residual.shape[-1] if residual is not None else 0
+        p.M = N * T * p.Ho * p.Wo
+        p.relu = 1 if self.relu else 0
+        p.grid = self.stem3d_grid or num_cus(x.device)
+        return p
+
     def special_candidates(self, x_shape):
         """Shape-specialised kernels (config ids >= 100) that can run this input.
         The first entry is the default when the layer is not autotuned."""
-        out = []
+        # first, so a 3x7x7 stem's default: at 128 clips of 8x112x112 its worst
+        # round (0.332 ms) beats the best generic config's best (0.546 ms;
+        # profiles/r3d_stem3d_bf16.txt)
+        out = self.stem3d_candidates(x_shape)
         if x_shape[3] <= VOL_DEFAULT_MAX_W:
             # elsewhere the family is an autotune candidate only (autotune)
             first = VOLS if x_shape[3] <= VOLS_FIRST_MAX_W else VOL
@@ -431,7 +489,8 @@ class ConvLayer:
         stream = torch.cuda.current_stream(x.device)
         best, best_t = None, None
         cands = self.generic_candidates() + self.special_candidates(x.shape)
-        cands += [c for c in self.vol_candidates(x.shape) if c not in cands]
+        cands += [c for c in self.vol_candidates(x.shape) + self.stem3d_candidates(x.shape)
+                  if c not in cands]
         for cid in cands:
             p = self.params(x, y, residual)
             self._launch(p, cid, x, y, residual, stream)    # warm
@@ -459,6 +518,12 @@ class ConvLayer:
                 raise ValueError("%s: config %d serves 3x3x3 stride-1 pad-1 convs" %
                                  (self.name, cid))
             kernels().vol(self.vol_params(x, y, residual), VOL_VARIANT[cid], stream.cuda_stream)
+        elif cid == STEM3D:
+            if (self.geom.kernel, self.geom.stride, self.geom.padding) != \
+                    ((3, 7, 7), (1, 2, 2), (1, 3, 3)) or self.geom.cin > 4:
+                raise ValueError("%s: config %d serves 3x7x7 stride-(1,2,2) pad-(1,3,3) convs "
+                                 "over at most 4 channels" % (self.name, cid))
+            kernels().stem3d(self.stem3d_params(x, y, residual), stream.cuda_stream)
         elif cid == TEMPORAL:
             kernels().temporal(self.temporal_params(x, y, residual), num_cus(x.device), 0,
                                stream.cuda_stream)

@@ -146,6 +146,22 @@ class VolParams(ctypes.Structure):
     ]
 
 
+class Stem3dParams(ctypes.Structure):
+    """Mirror of ``struct Stem3dParams`` in csrc/conv_stem3d.hip (the launcher
+    fills in R .. x_bytes)."""
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+        ("res", ctypes.c_void_p), ("y", ctypes.c_void_p),
+        ("N", ctypes.c_int), ("T", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+        ("Ho", ctypes.c_int), ("Wo", ctypes.c_int), ("Cout_p", ctypes.c_int),
+        ("y_stride", ctypes.c_int), ("res_stride", ctypes.c_int), ("M", ctypes.c_int),
+        ("relu", ctypes.c_int), ("grid", ctypes.c_int), ("R", ctypes.c_int),
+        ("bands", ctypes.c_int), ("tboxes", ctypes.c_int), ("nboxes", ctypes.c_int),
+        ("Q", ctypes.c_int), ("PR", ctypes.c_int), ("CW", ctypes.c_int),
+        ("units", ctypes.c_int), ("x_bytes", ctypes.c_uint32),
+    ]
+
+
 class Conv21Params(ctypes.Structure):
     """Mirror of ``struct Conv21Params`` in csrc/conv21.hip."""
     _fields_ = [
@@ -366,6 +382,13 @@ class Kernels:
         lib.rnb_vol_occupancy.argtypes = [ctypes.c_int] * 2
         if lib.rnb_vol_params_size() != ctypes.sizeof(VolParams):
             raise NativeUnavailable("VolParams layout mismatch: rebuild")
+        lib.rnb_stem3d_launch.argtypes = [ctypes.POINTER(Stem3dParams), ctypes.c_void_p]
+        lib.rnb_stem3d_launch.restype = ctypes.c_int
+        lib.rnb_stem3d_box.argtypes = [ctypes.c_int] * 4
+        lib.rnb_stem3d_lds_bytes.argtypes = [ctypes.c_int] * 4
+        lib.rnb_stem3d_occupancy.argtypes = [ctypes.c_int] * 2
+        if lib.rnb_stem3d_params_size() != ctypes.sizeof(Stem3dParams):
+            raise NativeUnavailable("Stem3dParams layout mismatch: rebuild")
         lib.rnb_temporal_launch.argtypes = [ctypes.POINTER(TemporalParams), ctypes.c_int,
                                             ctypes.c_int, ctypes.c_void_p]
         lib.rnb_temporal_launch.restype = ctypes.c_int
@@ -855,6 +878,23 @@ class Kernels:
     def vol_occupancy(self, variant: int, lds: int) -> int:
         """Blocks per CU of the variant's kernel at ``lds`` bytes; needs a GPU."""
         return self.lib.rnb_vol_occupancy(variant, lds)
+
+    def stem3d(self, params: Stem3dParams, stream: int) -> None:
+        """bf16 patch-staged 3x7x7 stride-(1,2,2) pad-(1,3,3) conv over up to 4
+        input channels (csrc/conv_stem3d.hip); ``params.grid`` blocks walk the boxes."""
+        _check(self.lib.rnb_stem3d_launch(ctypes.byref(params), stream), "conv_stem3d")
+
+    def stem3d_box(self, T: int, H: int, W: int, cout_p: int) -> int:
+        """Output rows of a box on T x H x W clips (0: cannot run)."""
+        return self.lib.rnb_stem3d_box(T, H, W, cout_p)
+
+    def stem3d_lds_bytes(self, T: int, H: int, W: int, cout_p: int) -> int:
+        """LDS bytes of a launch on T x H x W clips (0: cannot run)."""
+        return self.lib.rnb_stem3d_lds_bytes(T, H, W, cout_p)
+
+    def stem3d_occupancy(self, cout_p: int, lds: int) -> int:
+        """Blocks per CU of the kernel at ``lds`` bytes; needs a GPU."""
+        return self.lib.rnb_stem3d_occupancy(cout_p, lds)
 
     def temporal(self, params: TemporalParams, num_cus: int, blocks_per_cu: int,
                  stream: int) -> None:
