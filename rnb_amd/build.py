@@ -31,7 +31,7 @@ LIBRARIES = {
                            "conv_x6.hip", "conv_h3.hip", "conv_h3stem.hip", "conv_h3p.hip",
                            "conv_h3w.hip", "conv_h3v.hip", "jpeg_ops.hip", "jpeg_huff.hip",
                            "score_ops.hip", "conv_vol.hip", "conv_stem3d.hip",
-                           "conv_vol2.hip"],
+                           "conv_vol2.hip", "conv_sp2.hip"],
                           [], []),
     "librnb_runtime.so": (["runtime.cpp"], [], []),
     # host-only C++ (no HIP headers): the MJPEG entropy decoder

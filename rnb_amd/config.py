@@ -20,8 +20,8 @@ rnb_amd keeps every key and rule of the reference and adds a few optional keys:
 * step ``slot_dtype``: override the slot dtype advertised by the model;
 * top-level ``defaults``: kwargs merged into every step (e.g. ``"depth": 34``);
 * ``arch`` (``"reference"`` or ``"torchvision"``), ``midplanes`` (``"block"`` or
-  ``"conv"``), ``bn_eps`` and ``tv_block`` (``"2plus1d"`` or ``"3d"`` =
-  ``r3d_18``), in ``defaults`` or per step / queue group: the network layout
+  ``"conv"``), ``bn_eps`` and ``tv_block`` (``"2plus1d"``, ``"3d"`` =
+  ``r3d_18`` or ``"mc3"`` = ``mc3_18``, whole-model steps only), in ``defaults`` or per step / queue group: the network layout
   of the model steps (models/r2p1d/network.py).
 
 Validation errors raise ``ConfigError`` instead of calling ``sys.exit()`` so
@@ -247,7 +247,7 @@ def parse_pipeline(config: Dict[str, Any]) -> PipelineSpec:
 
 ARCHS = ("reference", "torchvision")
 MIDPLANES_RULES = ("block", "conv")
-TV_BLOCKS = ("2plus1d", "3d")
+TV_BLOCKS = ("2plus1d", "3d", "mc3")
 
 
 def _check_arch_keys(kwargs: Dict[str, Any], where: str) -> None:
@@ -273,9 +273,13 @@ def _check_arch_keys(kwargs: Dict[str, Any], where: str) -> None:
         raise ConfigError("%s: %s belongs to \"arch\": \"torchvision\", got arch %r"
                           % (where, "midplanes" if mid is not None else
                              "bn_eps" if eps is not None else "tv_block", arch))
-    if blk == "3d" and mid is not None:
+    if blk in ("3d", "mc3") and mid is not None:
         raise ConfigError("%s: midplanes belongs to \"tv_block\": \"2plus1d\", got tv_block %r"
                           % (where, blk))
+    rng = (kwargs.get("start_index", 1), kwargs.get("end_index", 5))
+    if blk == "mc3" and rng != (1, 5):
+        raise ConfigError("%s: tv_block \"mc3\" serves layers 1..5 in one step only, got "
+                          "start_index %r, end_index %r" % ((where,) + rng))
 
 
 def _check_clip_lengths(steps: List[StepSpec]) -> None:

@@ -124,8 +124,11 @@ def activation_elems_per_clip(start_idx: int, end_idx: int, dtype=torch.float32,
     bounds both ``midplanes`` rules, and the 1x1x1 shortcut's output has the
     layer's output shape. ``tv_block="3d"`` (r3d_18) has no intermediates:
     every conv's output has its layer's output shape (the stem's 64 channels,
-    a block's first conv and shortcut the block's output)."""
-    inp, out = layer_geometry(clip_length)
+    a block's first conv and shortcut the block's output); so has
+    ``tv_block="mc3"`` (mc3_18), whose layer outputs keep the clip's frame
+    count."""
+    flat = arch == "torchvision" and tv_block in ("3d", "mc3")
+    inp, out = layer_geometry(clip_length, tv_block if arch == "torchvision" else None)
     f32 = dtype == torch.float32
     align = F32_ALIGN if f32 else CH_ALIGN
     worst = 0
@@ -143,7 +146,7 @@ def activation_elems_per_clip(start_idx: int, end_idx: int, dtype=torch.float32,
             mids.append(intermediate_channels(cout, cout, kernel))
         # fp32 pads a temporal Winograd conv's input to 16 channels (_stconv)
         midp = max(pad_to(m, 16 if f32 else align) for m in mids)
-        if not (arch == "torchvision" and tv_block == "3d"):
+        if not flat:
             worst = max(worst, t * ho * wo * midp)
         if out[idx] is not None:
             co, to, ho2, wo2 = out[idx]
@@ -199,7 +202,9 @@ class R2P1DEngine:
                  backend: str = "hip", bn_mode: str = "eval", dtype=torch.bfloat16,
                  clip_length: int = DEFAULT_CLIP_LENGTH):
         self.clip_length = check_clip_length(clip_length)
-        self.layer_in, self.layer_out = layer_geometry(self.clip_length)
+        # torchvision layout: "2plus1d" (r2plus1d_*), "3d" (r3d_18) or "mc3" (mc3_18)
+        self.tv_block = getattr(net, "tv_block", "2plus1d")
+        self.layer_in, self.layer_out = layer_geometry(self.clip_length, self.tv_block)
         if backend not in ("hip", "torch", "module"):
             raise ValueError("unknown backend %r" % backend)
         if bn_mode not in ("eval", "batch"):
@@ -220,8 +225,6 @@ class R2P1DEngine:
         self.start_idx, self.end_idx = net.start_idx, net.end_idx
         # "reference" (R2Plus1DLayerWrapper) or "torchvision" (TVVideoResNet)
         self.arch = getattr(net, "arch", "reference")
-        # torchvision layout: "2plus1d" (r2plus1d_*) or "3d" (r3d_18)
-        self.tv_block = getattr(net, "tv_block", "2plus1d")
         self.num_classes = getattr(net, "num_classes", 400)
         self.ops: List[PlanOp] = []
         self.head: Optional[Head] = None
@@ -384,8 +387,9 @@ class R2P1DEngine:
         return self._stconv(c2[0], c2[1], c2[3], h, bn2, True, res, name + ".conv2")
 
     def _block_tv3d(self, blk, src: str, name: str) -> str:
-        """torchvision ``BasicBlock`` over ``Conv3DSimple`` (r3d_18): two 3x3x3
-        convs, the shortcut as in ``_block_tv``."""
+        """torchvision ``BasicBlock`` over ``Conv3DSimple`` (r3d_18) or
+        ``Conv3DNoTemporal`` (mc3_18's 1x3x3 convs): two convs, one op each, the
+        shortcut as in ``_block_tv``."""
         if blk.downsample is not None:
             res = self._name()
             self._append(blk.downsample[0], blk.downsample[1], False, None,
@@ -400,7 +404,7 @@ class R2P1DEngine:
     def _build_tv(self, net):
         cur = "x"
         self._thw = {"x": tuple(self.layer_in[self.start_idx][1:])}
-        v3d = self.tv_block == "3d"
+        v3d = self.tv_block in ("3d", "mc3")
         for idx in range(self.start_idx, self.end_idx + 1):
             if idx == 1 and v3d:
                 s, cur, src = net.stem, self._name(), cur

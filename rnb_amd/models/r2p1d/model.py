@@ -52,9 +52,9 @@ from .engine import (GraphedEngine, R2P1DEngine, boundary_channels_p, boundary_s
                      check_max_clips, parse_bucket_step)
 from .network import (DEFAULT_BN_EPS, DEFAULT_CLIP_LENGTH, LAYER_INPUT_CTHW,
                       R2Plus1DLayerWrapper, TVVideoResNet, check_arch, check_bn_eps,
-                      check_clip_length, check_midplanes, check_tv_block, init_random_,
-                      load_reference_state_dict, load_torchvision_state_dict,
-                      normalize_layer_sizes, tv_state_block, tv_state_mids)
+                      check_clip_length, check_mc3_range, check_midplanes, check_tv_block,
+                      init_random_, load_reference_state_dict, load_torchvision_state_dict,
+                      normalize_layer_sizes, tv_state_block_key, tv_state_mids)
 from .sampler import PLACEMENTS, R2P1DSampler, check_frame_step, clip_span, parse_rate, step_of
 
 DEFAULT_MAX_CLIPS = 15
@@ -124,9 +124,10 @@ def build_network(start_index: int, end_index: int, num_classes: int = 400,
     mid-channel counts come from the checkpoint's tensor shapes when there is
     one, else from ``midplanes`` ("block", torchvision's rule, or "conv");
     ``bn_eps`` is the BatchNorms' eps (a state dict does not carry it).
-    ``tv_block`` ("2plus1d" or "3d" = ``r3d_18``) comes from the checkpoint's
-    stem when there is one, else defaults to "2plus1d"; a value the file
-    contradicts raises."""
+    ``tv_block`` ("2plus1d", "3d" = ``r3d_18`` or "mc3" = ``mc3_18``) comes
+    from the checkpoint when there is one (its stem, then the temporal extent
+    of ``layer2.0.conv1.0.weight``), else defaults to "2plus1d"; a value the
+    file contradicts raises, and so does "mc3" with a range other than 1..5."""
     arch = check_arch(arch)
     midplanes, bn_eps = check_midplanes(midplanes), check_bn_eps(bn_eps)
     tv_block = check_tv_block(tv_block)
@@ -147,14 +148,17 @@ def build_network(start_index: int, end_index: int, num_classes: int = 400,
     if ckpt_path:
         ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
         state = ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
-    found = tv_state_block(state)
+    found, key = tv_state_block_key(state)
     if tv_block is not None and found is not None and found != tv_block:
-        raise ValueError("tv_block %r contradicts the checkpoint, whose stem.0.weight %s is "
-                         "tv_block %r's" % (tv_block, tuple(state["stem.0.weight"].shape), found))
+        if tv_block == "2plus1d":       # the stem alone tells (2+1)D from the other two
+            key = "stem.0.weight"
+        raise ValueError("tv_block %r contradicts the checkpoint, whose %s %s is "
+                         "tv_block %r's" % (tv_block, key, tuple(state[key].shape), found))
     tv_block = tv_block or found or "2plus1d"
-    if tv_block == "3d" and midplanes is not None:
-        raise ValueError("midplanes belongs to tv_block='2plus1d', got %r with tv_block='3d'"
-                         % (midplanes,))
+    check_mc3_range(tv_block, start_index, end_index)
+    if tv_block in ("3d", "mc3") and midplanes is not None:
+        raise ValueError("midplanes belongs to tv_block='2plus1d', got %r with tv_block=%r"
+                         % (midplanes, tv_block))
     net = TVVideoResNet(start_index, end_index, num_classes, sizes,
                         midplanes=midplanes,
                         bn_eps=DEFAULT_BN_EPS if bn_eps is None else bn_eps,
@@ -175,6 +179,7 @@ def build_engine(device: torch.device, start_index=1, end_index=5, num_classes=4
     clip_length = check_clip_length(clip_length)
     arch = check_arch(arch)
     tv_block = check_tv_block(tv_block)
+    check_mc3_range(tv_block, start_index, end_index)
     backend = _resolve_backend(backend, device)
     if backend == "hip":
         # before any weight is built: a call of max_clips clips must fit the
@@ -224,6 +229,7 @@ class R2P1DRunner(RunnerModel):
         self.arch = arch = check_arch(arch)
         midplanes, bn_eps = check_midplanes(midplanes), check_bn_eps(bn_eps)
         self.tv_block = tv_block = check_tv_block(tv_block)
+        check_mc3_range(tv_block, start_index, end_index)
         if start_index < 1:
             raise ValueError("Wrong layer index for the starting layer! The start_index "
                              "(%d) should be more than or equal to 1." % start_index)

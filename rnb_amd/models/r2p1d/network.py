@@ -68,14 +68,15 @@ def check_clip_length(clip_length, key: str = "clip_length") -> int:
     return int(clip_length)
 
 
-def layer_geometry(clip_length: int = DEFAULT_CLIP_LENGTH):
+def layer_geometry(clip_length: int = DEFAULT_CLIP_LENGTH, tv_block: Optional[str] = None):
     """(LAYER_INPUT_CTHW, LAYER_OUTPUT_CTHW) for ``clip_length`` x 112 x 112
     clips: T is unchanged through conv1 and conv2 and ``(T - 1) // 2 + 1``
     after each of conv3, conv4 and conv5 (their first block's stride-2
-    temporal conv, k 3, pad 1); H x W as at 8 frames."""
+    temporal conv, k 3, pad 1); H x W as at 8 frames. ``tv_block="mc3"``
+    (mc3_18) strides those layers in space only: T is the clip's throughout."""
     t = check_clip_length(clip_length)
-    t3 = (t - 1) // 2 + 1
-    t4 = (t3 - 1) // 2 + 1
+    t3 = t if tv_block == "mc3" else (t - 1) // 2 + 1
+    t4 = t if tv_block == "mc3" else (t3 - 1) // 2 + 1
     inp = {1: (3, t, 112, 112), 2: (64, t, 56, 56), 3: (64, t, 56, 56),
            4: (128, t3, 28, 28), 5: (256, t4, 14, 14)}
     out = {1: (64, t, 56, 56), 2: (64, t, 56, 56), 3: (128, t3, 28, 28),
@@ -315,7 +316,7 @@ def load_reference_state_dict(model: R2Plus1DLayerWrapper, state_dict,
 # ---------------------------------------------------------------------------
 ARCHS = ("reference", "torchvision")
 MIDPLANES_RULES = ("block", "conv")
-TV_BLOCKS = ("2plus1d", "3d")
+TV_BLOCKS = ("2plus1d", "3d", "mc3")
 TV_STEM_MID = 45
 DEFAULT_BN_EPS = 1e-5
 
@@ -342,8 +343,9 @@ def check_midplanes(midplanes, key: str = "midplanes") -> Optional[str]:
 
 
 def check_tv_block(tv_block, key: str = "tv_block") -> Optional[str]:
-    """``tv_block`` ("2plus1d" = r2plus1d_*, "3d" = r3d_18, or None = from the
-    checkpoint, else "2plus1d"); ValueError (naming ``key``) otherwise."""
+    """``tv_block`` ("2plus1d" = r2plus1d_*, "3d" = r3d_18, "mc3" = mc3_18, or
+    None = from the checkpoint, else "2plus1d"); ValueError (naming ``key``)
+    otherwise."""
     if tv_block is None:
         return None
     if not isinstance(tv_block, str) or tv_block not in TV_BLOCKS:
@@ -352,14 +354,39 @@ def check_tv_block(tv_block, key: str = "tv_block") -> Optional[str]:
     return tv_block
 
 
-def tv_state_block(state_dict) -> Optional[str]:
-    """The block type a torchvision-layout state dict was saved from, read from
-    its stem conv: 5-D with a temporal extent of 3 (3x7x7) is ``r3d_18``'s
-    ("3d"), 1x7x7 the (2+1)D stem's; None when it holds no stem."""
+MC3_KEY = "layer2.0.conv1.0.weight"     # 1x3x3 in mc3_18, 3x3x3 in r3d_18
+
+
+def tv_state_block_key(state_dict):
+    """(block type, deciding key) of a torchvision-layout state dict. The stem
+    conv, 5-D, decides first: 1x7x7 is the (2+1)D stem's ("2plus1d"). A 3x7x7
+    stem is ``r3d_18``'s and ``mc3_18``'s; there the temporal extent of
+    ``layer2.0.conv1.0.weight`` decides (1 = "mc3", 3 = "3d"), and a file
+    without that key is "3d". (None, None) when it holds no stem."""
     w = state_dict.get("stem.0.weight") if isinstance(state_dict, dict) else None
     if w is None or not hasattr(w, "shape") or len(w.shape) != 5:
-        return None
-    return "3d" if int(w.shape[2]) == 3 else "2plus1d"
+        return None, None
+    if int(w.shape[2]) != 3:
+        return "2plus1d", "stem.0.weight"
+    w2 = state_dict.get(MC3_KEY)
+    if w2 is not None and hasattr(w2, "shape") and len(w2.shape) == 5 and int(w2.shape[2]) == 1:
+        return "mc3", MC3_KEY
+    return "3d", (MC3_KEY if w2 is not None else "stem.0.weight")
+
+
+def tv_state_block(state_dict) -> Optional[str]:
+    """The block type a torchvision-layout state dict was saved from
+    (``tv_state_block_key``); None when it holds no stem."""
+    return tv_state_block_key(state_dict)[0]
+
+
+def check_mc3_range(tv_block, start_index, end_index) -> None:
+    """``tv_block="mc3"`` serves the whole model only: the boundary helpers
+    between stages (``boundary_shape``, ring sizing) know the temporal extents
+    of the other two trees. ValueError naming ``tv_block`` otherwise."""
+    if tv_block == "mc3" and (int(start_index), int(end_index)) != (1, 5):
+        raise ValueError("tv_block 'mc3' serves layers 1..5 in one stage only, got %d..%d: "
+                         "split-stage mc3_18 is not supported" % (start_index, end_index))
 
 
 def check_bn_eps(bn_eps, key: str = "bn_eps") -> Optional[float]:
@@ -444,22 +471,25 @@ class TVBasicBlock(nn.Module):
 
 class TVBasicBlock3D(nn.Module):
     """torchvision's video ``BasicBlock`` over ``Conv3DSimple`` (r3d_18): two
-    3x3x3 convs, the first with stride (s, s, s)."""
+    3x3x3 convs, the first with stride (s, s, s). ``flat``: over
+    ``Conv3DNoTemporal`` (layer2..4 of mc3_18): two 1x3x3 convs, pad (0, 1, 1),
+    the first and the shortcut with stride (1, s, s)."""
 
-    def __init__(self, in_planes, planes, stride=1, eps=DEFAULT_BN_EPS):
+    def __init__(self, in_planes, planes, stride=1, eps=DEFAULT_BN_EPS, flat=False):
         super().__init__()
+        k, pad = ((1, 3, 3), (0, 1, 1)) if flat else (3, 1)
+        s3 = (1 if flat else stride, stride, stride)
         self.conv1 = nn.Sequential(
-            nn.Conv3d(in_planes, planes, 3, stride=(stride, stride, stride), padding=1,
-                      bias=False),
+            nn.Conv3d(in_planes, planes, k, stride=s3, padding=pad, bias=False),
             nn.BatchNorm3d(planes, eps=eps), nn.ReLU())
         self.conv2 = nn.Sequential(
-            nn.Conv3d(planes, planes, 3, stride=1, padding=1, bias=False),
+            nn.Conv3d(planes, planes, k, stride=1, padding=pad, bias=False),
             nn.BatchNorm3d(planes, eps=eps))
         self.relu = nn.ReLU()
         self.downsample = None
         if stride != 1 or in_planes != planes:
             self.downsample = nn.Sequential(
-                nn.Conv3d(in_planes, planes, 1, stride=(stride, stride, stride), bias=False),
+                nn.Conv3d(in_planes, planes, 1, stride=s3, bias=False),
                 nn.BatchNorm3d(planes, eps=eps))
 
     def forward(self, x):
@@ -476,7 +506,9 @@ class TVVideoResNet(nn.Module):
     ``tv_state_mids``); convs it does not name follow ``midplanes`` (None =
     "block"). ``tv_block="3d"`` is ``r3d_18``: a 3x7x7 stem and blocks of two
     3x3x3 convs, with the same boundary geometry; ``midplanes`` does not apply
-    to it."""
+    to it. ``tv_block="mc3"`` is ``mc3_18``: r3d_18's stem and ``layer1``, then
+    blocks of two 1x3x3 convs whose stride is spatial only, so every layer
+    keeps the clip's frame count; it builds the whole range 1..5 only."""
 
     arch = "torchvision"
 
@@ -491,10 +523,12 @@ class TVVideoResNet(nn.Module):
         self.num_classes = num_classes
         self.bn_eps = float(bn_eps)
         self.tv_block = check_tv_block(tv_block) or "2plus1d"
-        if self.tv_block == "3d":
+        check_mc3_range(self.tv_block, start_idx, end_idx)
+        if self.tv_block in ("3d", "mc3"):
             if midplanes is not None:
-                raise ValueError("midplanes belongs to tv_block='2plus1d': the 3x3x3 convs of "
-                                 "tv_block='3d' have no mid channels, got %r" % (midplanes,))
+                raise ValueError("midplanes belongs to tv_block='2plus1d': the convs of "
+                                 "tv_block=%r have no mid channels, got %r"
+                                 % (self.tv_block, midplanes))
             self.mids = {}
             for idx in range(start_idx, end_idx + 1):
                 if idx == 1:
@@ -506,7 +540,8 @@ class TVVideoResNet(nn.Module):
                 cin, planes = LAYER_CHANNELS[idx]
                 setattr(self, "layer%d" % (idx - 1), nn.Sequential(*[
                     TVBasicBlock3D(cin if j == 0 else planes, planes,
-                                   stride=2 if (j == 0 and idx > 2) else 1, eps=bn_eps)
+                                   stride=2 if (j == 0 and idx > 2) else 1, eps=bn_eps,
+                                   flat=self.tv_block == "mc3" and idx > 2)
                     for j in range(layer_sizes[idx])]))
             if end_idx == 5:
                 self.avgpool = nn.AdaptiveAvgPool3d(1)
@@ -559,7 +594,7 @@ def _unwrap_state(state):
 
 
 def load_torchvision_state_dict(model: TVVideoResNet, state, strict: bool = True):
-    """Load a torchvision-layout R(2+1)D or r3d_18 state dict (raw, or wrapped as
+    """Load a torchvision-layout R(2+1)D, r3d_18 or mc3_18 state dict (raw, or wrapped as
     ``{"state_dict": ...}``) restricted to the range ``model`` builds;
     ``num_batches_tracked`` entries are accepted. Raises a ValueError naming
     the first missing key, the first unexpected key (within the built range's

@@ -37,12 +37,14 @@ VOLS = 106          # volume-halo kernel with 128-pixel boxes (7 x 7 frames whol
 VOLN = 107          # VOL with a 64-channel tile (offered to convs of up to 64 output channels)
 STEM3D = 108        # patch-staged 3x7x7 stride-(1,2,2) kernel over <= 4 channels (conv_stem3d.hip)
 VOL2 = 109          # parity-staged 3x3x3 stride-2 kernel (conv_vol2.hip), 128-pixel boxes
+SP2 = 110           # frame-stacked 1x3x3 stride-(1,2,2) kernel (conv_sp2.hip), <= 256-pixel boxes
 SPECIAL_NAMES = {HALO: "halo", TEMPORAL: "temporal", HALO4: "halo4", HALO4B: "halo4b",
                  HALOWS: "halows", VOL: "vol", VOLS: "vols", VOLN: "voln", STEM3D: "stem3d",
-                 VOL2: "vol2"}
+                 VOL2: "vol2", SP2: "sp2"}
 HALO_VARIANT = {HALO: 2, HALO4: 4, HALO4B: 5, HALOWS: 6}   # variant of rnb_halo_launch_v
 VOL_VARIANT = {VOL: 0, VOLS: 1, VOLN: 2}                   # variant of rnb_vol_launch
 VOL2_VARIANT = {VOL2: 0}                                   # variant of rnb_vol2_launch
+SP2_VARIANT = {SP2: 0}                                     # variant of rnb_sp2_launch
 LDS_LIMIT = 160 * 1024
 KTAB_MAX = 640      # K_pad / 8 limit of the 3-stage conv_igemm configs (conv_igemm.hip)
 
@@ -69,6 +71,15 @@ VOLS_FIRST_MAX_W = 14      # up to this width the 128-pixel-box variant is the f
 # 14-wide conv (0.054 against 0.060), which autotune finds.
 VOL2_DEFAULT: Dict[int, int] = {}
 
+# Input frame width -> the frame-stacked (1x3x3 stride-(1,2,2)) id that is the
+# conv's default there, under the same rule. None passes
+# (profiles/mc3_sp2_bf16.txt, ms at 128 clips, sp2's best round against the
+# generic config's worst): 64->128 on 8x56x56 0.320 against 0.245; 128->256 on
+# 8x28x28 0.239 against 0.186; 256->512 on 8x14x14 0.183 against 0.131; R(2+1)D's
+# 64->144 on 8x56x56 0.551 against 0.264. So the id is an autotune candidate
+# only on every width.
+SP2_DEFAULT: Dict[int, int] = {}
+
 
 def vol_enabled() -> bool:
     """RNB_VOL=0 leaves the volume-halo kernel family out."""
@@ -78,6 +89,11 @@ def vol_enabled() -> bool:
 def vol2_enabled() -> bool:
     """RNB_VOL2=0 leaves the parity-staged stride-2 kernel family out."""
     return os.environ.get("RNB_VOL2", "1") != "0"
+
+
+def sp2_enabled() -> bool:
+    """RNB_SP2=0 leaves the frame-stacked 1x3x3 stride-(1,2,2) kernel family out."""
+    return os.environ.get("RNB_SP2", "1") != "0"
 
 
 def stem3d_enabled() -> bool:
@@ -207,6 +223,7 @@ class ConvLayer:
         self.use_halo_ws = True   # allow the weight-stationary halo kernel (conv2 spatial)
         self.use_vol = vol_enabled()   # allow the volume-halo kernel for 3x3x3 stride-1 convs
         self.use_vol2 = vol2_enabled()   # allow the parity-staged kernel for 3x3x3 stride-2 convs
+        self.use_sp2 = sp2_enabled()     # allow the frame-stacked kernel for 1x3x3 stride-(1,2,2)
         self.use_stem3d = stem3d_enabled()   # allow the patch-staged kernel for 3x7x7 stems
         self.stem3d_grid = 0      # blocks of the stem3d kernel's persistent grid (0: one per CU)
         self._stem3d_w: Optional[torch.Tensor] = None
@@ -359,6 +376,24 @@ class ConvLayer:
             self._config[key] = ids
         return list(ids)
 
+    def sp2_candidates(self, x_shape):
+        """Frame-stacked ids (conv_sp2.hip) that can run this input: 1x3x3 /
+        stride (1,2,2) / pad (0,1,1) with Cin_p % 32 == 0, for every variant
+        whose box and patch fit (rnb_sp2_box, LDS_LIMIT)."""
+        g = self.geom
+        if not (g.kernel == (1, 3, 3) and g.stride == (1, 2, 2) and g.padding == (0, 1, 1)
+                and g.cin_p >= 32 and g.cin_p % 32 == 0 and self.use_sp2):
+            return []
+        N, T, H, W, _ = x_shape
+        key = ("sp2", T, H, W)
+        ids = self._config.get(key)
+        if ids is None:
+            from .native import kernels
+            ids = tuple(cid for cid, v in SP2_VARIANT.items()
+                        if 0 < kernels().sp2_lds_bytes(v, T, H, W, g.cin_p) <= LDS_LIMIT)
+            self._config[key] = ids
+        return list(ids)
+
     def stem3d_candidates(self, x_shape):
         """[STEM3D] if conv_stem3d.hip can run this input: 3x7x7 / stride
         (1,2,2) / pad (1,3,3) over at most 4 input channels to Cout_p <= 64, a
@@ -419,6 +454,9 @@ class ConvLayer:
         if x_shape[3] in VOL2_DEFAULT:
             first = VOL2_DEFAULT[x_shape[3]]
             out += sorted(self.vol2_candidates(x_shape), key=lambda c: c != first)
+        if x_shape[3] in SP2_DEFAULT:
+            first = SP2_DEFAULT[x_shape[3]]
+            out += sorted(self.sp2_candidates(x_shape), key=lambda c: c != first)
         if self.halo_ws_eligible(x_shape):
             out.append(HALOWS)
         if self.halo_eligible(x_shape):
@@ -482,6 +520,25 @@ class ConvLayer:
         p.Cout_p, p.y_stride = g.cout_p, y.shape[-1]
         p.res_stride = residual.shape[-1] if residual is not None else 0
         p.K_pad, p.M = g.k_pad, N * p.To * p.Ho * p.Wo
+        p.relu = 1 if self.relu else 0
+        p.w_rows = self.wmat.shape[0]
+        return p
+
+    def sp2_params(self, x, y, residual):
+        from .native import Sp2Params
+        g = self.geom
+        N, T, H, W, C = x.shape
+        if C != g.cin_p:
+            raise ValueError("%s: input has %d channels, expected %d" % (self.name, C, g.cin_p))
+        p = Sp2Params()
+        p.x, p.w, p.bias = x.data_ptr(), self.wmat.data_ptr(), self.bias.data_ptr()
+        p.res = residual.data_ptr() if residual is not None else None
+        p.y = y.data_ptr()
+        p.N, p.T, p.H, p.W, p.Cin = N, T, H, W, C
+        p.Ho, p.Wo = y.shape[2:4]
+        p.Cout_p, p.y_stride = g.cout_p, y.shape[-1]
+        p.res_stride = residual.shape[-1] if residual is not None else 0
+        p.K_pad, p.M = g.k_pad, N * T * p.Ho * p.Wo
         p.relu = 1 if self.relu else 0
         p.w_rows = self.wmat.shape[0]
         return p
@@ -550,7 +607,8 @@ class ConvLayer:
         best, best_t = None, None
         cands = self.generic_candidates() + self.special_candidates(x.shape)
         cands += [c for c in self.vol_candidates(x.shape) + self.vol2_candidates(x.shape)
-                  + self.stem3d_candidates(x.shape) if c not in cands]
+                  + self.sp2_candidates(x.shape) + self.stem3d_candidates(x.shape)
+                  if c not in cands]
         for cid in cands:
             p = self.params(x, y, residual)
             self._launch(p, cid, x, y, residual, stream)    # warm
@@ -585,6 +643,13 @@ class ConvLayer:
                                  "multiple of 32 channels" % (self.name, cid))
             kernels().vol2(self.vol2_params(x, y, residual), VOL2_VARIANT[cid],
                            stream.cuda_stream)
+        elif cid in SP2_VARIANT:
+            if (self.geom.kernel, self.geom.stride, self.geom.padding) != \
+                    ((1, 3, 3), (1, 2, 2), (0, 1, 1)) or self.geom.cin_p % 32:
+                raise ValueError("%s: config %d serves 1x3x3 stride-(1,2,2) pad-(0,1,1) convs "
+                                 "over a multiple of 32 channels" % (self.name, cid))
+            kernels().sp2(self.sp2_params(x, y, residual), SP2_VARIANT[cid],
+                          stream.cuda_stream)
         elif cid == STEM3D:
             if (self.geom.kernel, self.geom.stride, self.geom.padding) != \
                     ((3, 7, 7), (1, 2, 2), (1, 3, 3)) or self.geom.cin > 4:

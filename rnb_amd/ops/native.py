@@ -162,6 +162,22 @@ class Vol2Params(ctypes.Structure):
     ]
 
 
+class Sp2Params(ctypes.Structure):
+    """Mirror of ``struct Sp2Params`` in csrc/conv_sp2.hip (the launcher fills
+    in n_ctiles .. x_bytes)."""
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+        ("res", ctypes.c_void_p), ("y", ctypes.c_void_p),
+        ("N", ctypes.c_int), ("T", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+        ("Cin", ctypes.c_int), ("Ho", ctypes.c_int), ("Wo", ctypes.c_int),
+        ("Cout_p", ctypes.c_int), ("y_stride", ctypes.c_int), ("res_stride", ctypes.c_int),
+        ("K_pad", ctypes.c_int), ("M", ctypes.c_int), ("relu", ctypes.c_int),
+        ("w_rows", ctypes.c_int), ("n_ctiles", ctypes.c_int), ("F", ctypes.c_int),
+        ("Ro", ctypes.c_int), ("bands", ctypes.c_int), ("fgroups", ctypes.c_int),
+        ("np", ctypes.c_int), ("x_bytes", ctypes.c_uint32),
+    ]
+
+
 class Stem3dParams(ctypes.Structure):
     """Mirror of ``struct Stem3dParams`` in csrc/conv_stem3d.hip (the launcher
     fills in R .. x_bytes)."""
@@ -405,6 +421,13 @@ class Kernels:
         lib.rnb_vol2_occupancy.argtypes = [ctypes.c_int] * 2
         if lib.rnb_vol2_params_size() != ctypes.sizeof(Vol2Params):
             raise NativeUnavailable("Vol2Params layout mismatch: rebuild")
+        lib.rnb_sp2_launch.argtypes = [ctypes.POINTER(Sp2Params), ctypes.c_int, ctypes.c_void_p]
+        lib.rnb_sp2_launch.restype = ctypes.c_int
+        lib.rnb_sp2_box.argtypes = [ctypes.c_int] * 4
+        lib.rnb_sp2_lds_bytes.argtypes = [ctypes.c_int] * 5
+        lib.rnb_sp2_occupancy.argtypes = [ctypes.c_int] * 2
+        if lib.rnb_sp2_params_size() != ctypes.sizeof(Sp2Params):
+            raise NativeUnavailable("Sp2Params layout mismatch: rebuild")
         lib.rnb_stem3d_launch.argtypes = [ctypes.POINTER(Stem3dParams), ctypes.c_void_p]
         lib.rnb_stem3d_launch.restype = ctypes.c_int
         lib.rnb_stem3d_box.argtypes = [ctypes.c_int] * 4
@@ -918,6 +941,25 @@ class Kernels:
     def vol2_occupancy(self, variant: int, lds: int) -> int:
         """Blocks per CU of the variant's kernel at ``lds`` bytes; needs a GPU."""
         return self.lib.rnb_vol2_occupancy(variant, lds)
+
+    def sp2(self, params: Sp2Params, variant: int, stream: int) -> None:
+        """bf16 frame-stacked 1x3x3 stride-(1,2,2) pad-(0,1,1) conv
+        (csrc/conv_sp2.hip): variant 0 = boxes of up to 256 pixels, 8 waves."""
+        _check(self.lib.rnb_sp2_launch(ctypes.byref(params), variant, stream),
+               "conv_sp2 (variant %d)" % variant)
+
+    def sp2_box(self, variant: int, T: int, H: int, W: int):
+        """(frames, output rows) of the variant's box on T x H x W input clips
+        ((0, 0): cannot run)."""
+        box = self.lib.rnb_sp2_box(variant, T, H, W)
+        return box >> 16, box & 0xFFFF
+
+    def sp2_lds_bytes(self, variant: int, T: int, H: int, W: int, cin: int) -> int:
+        return self.lib.rnb_sp2_lds_bytes(variant, T, H, W, cin)
+
+    def sp2_occupancy(self, variant: int, lds: int) -> int:
+        """Blocks per CU of the variant's kernel at ``lds`` bytes; needs a GPU."""
+        return self.lib.rnb_sp2_occupancy(variant, lds)
 
     def stem3d(self, params: Stem3dParams, stream: int) -> None:
         """bf16 patch-staged 3x7x7 stride-(1,2,2) pad-(1,3,3) conv over up to 4
